@@ -16,6 +16,12 @@ min-reduces the watermark on the device (--valve device, the default: one RCCL a
 result fw_advance_device reads from device memory; --valve host keeps a host gloo all-reduce for
 A/B), then runs its own operator subtask -- no host synchronisation inside a step.  Weak scaling: per-GPU events, keys and event rate stay fixed as
 N grows.
+
+A plain run sets up, warms up, times the steps and prints the result line (value, ms_per_step, the
+per-kernel device times the timed region itself collected).  --full adds every other leg: the exact
+G_b count and the two kernels' rooflines, the host-staged end-to-end leg, the CPU baseline and (N > 1)
+the per-rank load.  --dump-outputs DIR writes the rows the last timed step emitted, and the rows one
+more watermark fires from the state the timed steps left, as DIR/<name>.npy.
 """
 import argparse
 import ctypes as C
@@ -155,6 +161,32 @@ def cpu_baseline(wl, sample_events, threads=1):
     return steps * B / dt, steps * B, dt, sum(n_out)
 
 
+DUMP_BUDGET_BYTES = 56 << 20   # all .npy files of one --dump-outputs together stay below 64 MB
+
+
+def dump_rows(out_dir, prefix, res, wl, cap_rows):
+    """One watermark's result rows (the dict WindowAggHandle.results() returns) as
+    out_dir/<prefix>_<column>.npy, float64.  Rows are sorted by (window_end, key): the operator emits
+    them in no fixed order.  More than cap_rows rows: a fixed sample (numpy default_rng(0), in sorted
+    order); <prefix>_rows.npy holds the full count.  DOUBLE aggregates are their values; BIGINT
+    columns are converted, and one holding a value of 2^53 or more also gets <column>_low32.npy (its
+    low 32 bits), so that no bit is lost to the conversion."""
+    n = len(res["key"])
+    order = np.lexsort((res["key"], res["window_end"]))
+    if n > cap_rows:
+        order = order[np.sort(np.random.default_rng(0).choice(n, cap_rows, replace=False))]
+    cols = {"key": res["key"], "window_end": res["window_end"], "null_mask": res["null_mask"].astype(np.int64)}
+    for a, (kind, _, ty) in enumerate(wl["aggs"]):
+        v = res["values"][a]
+        cols[f"agg{a}_{kind.lower()}"] = v.view(np.float64) if ty == "DOUBLE" else v
+    np.save(os.path.join(out_dir, f"{prefix}_rows.npy"), np.array([n], dtype=np.float64))
+    for name, c in cols.items():
+        c = c[order]
+        np.save(os.path.join(out_dir, f"{prefix}_{name}.npy"), c.astype(np.float64))
+        if c.dtype == np.int64 and c.size and int(np.abs(c).max()) >= 1 << 53:
+            np.save(os.path.join(out_dir, f"{prefix}_{name}_low32.npy"), (c & 0xFFFFFFFF).astype(np.float64))
+
+
 def rank_load(owned, elapsed_s, partials, world):
     """N > 1 per-rank load, collective over the job's process group (after the timed region).
     owned: int64 tensor [world] of THIS rank's timed rows by destination subtask (its share of the
@@ -183,6 +215,14 @@ def main():
     ap.add_argument("--steps", type=int, default=24)
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--workload", default="cfg2", choices=sorted(WORKLOADS))
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also run every other leg: exact G_b count and rooflines, "
+                         "host-staged end-to-end leg, CPU baseline, per-rank load (N > 1); a plain run "
+                         "only sets up, warms up, times the steps and prints value and ms_per_step")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="write the result rows of the last timed step, and (N = 1) the rows one further "
+                         "watermark fires from the state the timed steps left, as DIR/<name>.npy (float64, "
+                         "sorted by window_end and key, a fixed seeded sample above the size budget)")
     ap.add_argument("--force-collectives", action="store_true",
                     help="rehearsal: run one rank (torch.distributed.run --nproc-per-node 1) through the N > 1 "
                          "code path and its collectives (RCCL with --dist-backend nccl)")
@@ -229,6 +269,8 @@ def main():
                          "one-GPU box: ranks share the GPUs round robin and the exchange is staged "
                          "through host memory; never used for reported numbers")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     import torch
     import torch.distributed as dist
@@ -359,6 +401,9 @@ def main():
         def settle(self):
             self.tp.settle()
 
+        def results(self):
+            return self.tp.glob.results()
+
         def set_profiling(self, *a, **k):
             self.tp.local.set_profiling(*a, **k)
             self.tp.glob.set_profiling(*a, **k)
@@ -439,7 +484,7 @@ def main():
         import math
         interval = math.gcd(wl["window"][1], wl["window"][2])
     groups = []
-    for b in range(args.warmup, total_steps):
+    for b in (range(args.warmup, total_steps) if args.full else ()):
         # one-phase: the batch this subtask ingests after the exchange; two-phase: the LOCAL
         # operator's own batch (its k_ingest is the segmented reduce measured below)
         k, t = (gk[b], gt[b]) if two_phase else exchange(b)[:2]
@@ -484,13 +529,34 @@ def main():
     if st["error_flags"]:
         raise SystemExit(f"device error flags {st['error_flags']}")
 
+    # ---------------- --dump-outputs: what the timed steps computed -----------------------------
+    # `last`: the rows the last timed step's watermark fired, which the timed loop left unread (every
+    # step's sink consumes the PREVIOUS watermark's rows), read back through fw_results.  A TUMBLE
+    # window fires only every few steps, so `last` can be empty; `next` (N = 1) is what one further
+    # watermark without new input fires -- the next step's watermark, for TUMBLE the last one + the
+    # window size (exactly one window end) -- i.e. the aggregates the timed steps left in the state.
+    if args.dump_outputs:
+        os.makedirs(args.dump_outputs, exist_ok=True)
+        sets = 1 if dpath else 2
+        cap_rows = DUMP_BUDGET_BYTES // (sets * 8 * (3 + 2 * len(wl["aggs"])))
+        sfx = f"_rank{rank}" if world > 1 else ""
+        dump_rows(args.dump_outputs, "last" + sfx, h.results(), wl, cap_rows)
+        if not dpath:
+            if wl["window"][0] == "TUMBLE":
+                h.advance(watermark(total_steps - 1, wl["rate"]) + wl["window"][1])
+            else:
+                h.advance(watermark(total_steps, wl["rate"]))
+            dump_rows(args.dump_outputs, "next", h.results(), wl, cap_rows)
+            if h.stats()["error_flags"]:
+                raise SystemExit(f"device error flags {h.stats()['error_flags']} after the --dump-outputs watermark")
+
     # ---------------- N > 1: per-rank load (after the timed region) ---------------------------
     # key-group skew limits linearity, so the line reports each subtask's share of the
     # timed events -- the rows whose key group it owns (KeyGroupRangeAssignment
     # .computeKeyGroupRangeForOperatorIndex :93-106, as KeyGroupStreamPartitioner.selectChannel routes
     # them) -- and every rank's own timed wall clock; the shares sum to N * B * steps
     ranks = None
-    if dpath:
+    if dpath and args.full:
         cdev = dev if args.dist_backend == "nccl" else torch.device("cpu")
         owned = torch.zeros(world, dtype=torch.int64, device=dev)
         kg_b = torch.empty(B, dtype=torch.int32, device=dev)
@@ -503,6 +569,26 @@ def main():
 
     n_total = args.steps * B * world
     value = n_total / elapsed
+    if not args.full:
+        if rank == 0:
+            print(json.dumps({
+                "metric": "windowed-agg events/sec (whole node) at 1/2/4/8 GPU + % of HBM peak",
+                "value": value, "unit": "events/s", "n_gpus": world, "steps": args.steps,
+                "warmup": args.warmup, "ms_per_step": elapsed / args.steps * 1e3,
+                "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
+                "dtype": "int64" if wl["value_kind"] != 1 else "f64",
+                "data": "synthetic (SplitMix64 Nexmark-shaped generator, seed 42, device-resident)",
+                "config": {"workload": f"{args.workload}: {wl['desc']}", "events_per_gpu_per_step": B,
+                           "plan": "two-phase" if two_phase else "one-phase", "keys_total": keys_total,
+                           "result_sink": args.sink, "superbuckets": st["num_superbuckets"]},
+                "full": False,
+                "device_ms_per_step": None if args.no_kernel_events else
+                {k: v[0] / args.steps for k, v in kt.items() if v[1]},
+                "host_issue_ms_per_step": t_issued / args.steps * 1e3}), flush=True)
+        h.close()
+        if dpath:
+            dist.destroy_process_group()
+        return
     if args.no_kernel_events:
         if rank == 0:
             print(json.dumps({"diagnostic": "no per-launch events", "value": value,
@@ -753,6 +839,7 @@ def main():
                                "avg_launch_us": avg_merge_s * 1e6, "launches": mg_n, "traffic": traffic_m,
                                "counter_rate_GBps": (traffic_m / avg_merge_s / 1e9) if traffic_m else None,
                                "traffic_over_algorithmic": (traffic_m / merge_bytes) if traffic_m else None},
+            "full": True,
             "cpu_baseline": cpu,
             "end_to_end": e2e,
             "per_rank": ranks,

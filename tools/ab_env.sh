@@ -10,7 +10,7 @@ REPS=${REPS:-1}
 STEPS=${STEPS:-24}
 mkdir -p "$OUT"
 one() {  # label env workload
-  timeout -k 10 200 env $2 python -u bench.py --workload "$3" --steps "$STEPS" --no-cpu-baseline --no-e2e > "$OUT/ab_$3_$1.json" 2> "$OUT/ab_$3_$1.err" || { tail -20 "$OUT/ab_$3_$1.err"; exit 1; }
+  timeout -k 10 200 env $2 python -u bench.py --full --workload "$3" --steps "$STEPS" --no-cpu-baseline --no-e2e > "$OUT/ab_$3_$1.json" 2> "$OUT/ab_$3_$1.err" || { tail -20 "$OUT/ab_$3_$1.err"; exit 1; }
   python3 -c "import json;d=json.load(open('$OUT/ab_$3_$1.json'));print('$3 $1', round(d['value']/1e9,2), 'G ev/s', round(d['ms_per_step']*1e3,1), 'us/step', {k: round(v*1e3,1) for k,v in d['device_ms_per_step'].items()}, 'merge_us', round(d['roofline_merge']['avg_launch_us'] or 0,1), 'ingest_us', round(d['roofline']['avg_launch_us'],1))"
 }
 for r in $(seq $REPS); do

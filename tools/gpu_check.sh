@@ -10,7 +10,7 @@ mkdir -p "$OUT"
 timeout -k 10 300 python -u -m pytest tests -m gpu -x -v --timeout 120 --timeout-method thread > "$OUT/gpu_tests.log" 2>&1 || { tail -30 "$OUT/gpu_tests.log"; exit 1; }
 tail -2 "$OUT/gpu_tests.log"
 for w in $WLS; do
-  timeout -k 10 240 python -u bench.py --workload "$w" --steps "$STEPS" --warmup 3 --no-cpu-baseline > "$OUT/bench_$w.json" 2> "$OUT/bench_$w.err" || { tail -20 "$OUT/bench_$w.err"; exit 1; }
+  timeout -k 10 240 python -u bench.py --full --workload "$w" --steps "$STEPS" --warmup 3 --no-cpu-baseline > "$OUT/bench_$w.json" 2> "$OUT/bench_$w.err" || { tail -20 "$OUT/bench_$w.err"; exit 1; }
   cat "$OUT/bench_$w.json"
 done
 if [ -n "$PROF" ]; then

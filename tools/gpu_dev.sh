@@ -16,7 +16,7 @@ fi
 for e in $ENVS; do
   for w in $WLS; do
     tag=$(echo "$e" | tr '=,' '__')_$w
-    ( [ "$e" != "-" ] && export ${e//,/ }; timeout -k 10 240 python -u bench.py --workload "$w" --steps "$STEPS" --warmup 3 --no-cpu-baseline ${BENCH_ARGS} ) > "$OUT/bench_$tag.json" 2> "$OUT/bench_$tag.err" || { tail -20 "$OUT/bench_$tag.err"; exit 1; }
+    ( [ "$e" != "-" ] && export ${e//,/ }; timeout -k 10 240 python -u bench.py --full --workload "$w" --steps "$STEPS" --warmup 3 --no-cpu-baseline ${BENCH_ARGS} ) > "$OUT/bench_$tag.json" 2> "$OUT/bench_$tag.err" || { tail -20 "$OUT/bench_$tag.err"; exit 1; }
     python3 tools/summ.py "$e" "$OUT/bench_$tag.json"
   done
 done

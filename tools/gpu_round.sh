@@ -11,5 +11,5 @@ rc=$?
 tail -40 "$OUT/gpu_tests.log"
 [ $rc -eq 0 ] || exit $rc
 [ -n "${SKIP_BENCH:-}" ] && exit 0
-timeout -k 10 300 python bench.py ${BENCH_ARGS:-} > "$OUT/bench.json" 2> "$OUT/bench.err" || { tail -20 "$OUT/bench.err"; exit 1; }
+timeout -k 10 300 python bench.py --full ${BENCH_ARGS:-} > "$OUT/bench.json" 2> "$OUT/bench.err" || { tail -20 "$OUT/bench.err"; exit 1; }
 cat "$OUT/bench.json"

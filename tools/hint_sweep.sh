@@ -8,7 +8,7 @@ for wl in ${WLS:-cfg4_10m}; do
   for h in ${HINTS:-0}; do
     extra=""
     [ "$h" != "0" ] && extra="--state-per-key $h"
-    timeout -k 10 240 python -u bench.py --workload "$wl" --no-e2e --no-cpu-baseline $extra > "$OUT/${wl}_h${h}.json" 2> "$OUT/${wl}_h${h}.err"
+    timeout -k 10 240 python -u bench.py --full --workload "$wl" --no-e2e --no-cpu-baseline $extra > "$OUT/${wl}_h${h}.json" 2> "$OUT/${wl}_h${h}.err"
     python - "$OUT/${wl}_h${h}.json" <<'PY'
 import json, sys
 d = json.loads(open(sys.argv[1]).read().strip().splitlines()[-1])

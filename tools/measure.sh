@@ -14,7 +14,7 @@ mkdir -p "$OUT/profiles"
 cd /tmp && export TMPDIR=/tmp
 if [ -z "$SKIP_DEFAULT" ]; then
 timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/prof_default" -o run \
-  -- python3 "$R/bench.py" > "$OUT/bench_default.json" 2> "$OUT/prof_default.log" || { tail -20 "$OUT/prof_default.log"; exit 1; }
+  -- python3 "$R/bench.py" --full > "$OUT/bench_default.json" 2> "$OUT/prof_default.log" || { tail -20 "$OUT/prof_default.log"; exit 1; }
 cat "$OUT/bench_default.json"
 fi
 for w in $PMC_WLS; do
@@ -25,7 +25,7 @@ for w in $PMC_WLS; do
   python3 "$R/tools/traffic.py" "$w" "$OUT/pmc_fetch_$w" "$OUT/pmc_write_$w" "$OUT/profiles/traffic_$w.json" || exit 1
 done
 for w in $BENCH_WLS; do
-  timeout -k 10 240 python3 "$R/bench.py" --workload "$w" --no-cpu-baseline \
+  timeout -k 10 240 python3 "$R/bench.py" --full --workload "$w" --no-cpu-baseline \
     --traffic-json "$OUT/profiles/traffic_$w.json" > "$OUT/bench_$w.json" 2> "$OUT/bench_$w.err" || { tail -20 "$OUT/bench_$w.err"; exit 1; }
   cat "$OUT/bench_$w.json"
 done

@@ -7,7 +7,7 @@ cd /tmp && export TMPDIR=/tmp
 W=${W:-cfg2}
 timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d "$R/gpurun_out/prof_rccl" -o run \
   -- python3 -m torch.distributed.run --nnodes=1 --nproc-per-node 1 --master-addr 127.0.0.1 --master-port 29515 \
-  "$R/bench.py" --gpus 1 --dist-backend nccl --force-collectives --workload $W --no-cpu-baseline --steps 12 --warmup 2 \
+  "$R/bench.py" --full --gpus 1 --dist-backend nccl --force-collectives --workload $W --no-cpu-baseline --steps 12 --warmup 2 \
   > "$R/gpurun_out/prof_rccl.json" 2> "$R/gpurun_out/prof_rccl.err" || { tail -20 "$R/gpurun_out/prof_rccl.err"; exit 1; }
 python3 - "$R/gpurun_out/prof_rccl" <<'PY'
 import csv, glob, sys
