@@ -5,9 +5,10 @@ test-side oracle wrapper can build the same ``fw_config`` structure.
 """
 import ctypes as C
 
-FW_ABI_VERSION = 10
+FW_ABI_VERSION = 11
 FW_MAX_AGGS = 8
 FW_MAX_COLS = 8
+FW_COUNT_MAX_SLICES = 16  # WIN_COUNT: most count slices, size / gcd(size, slide), per window
 
 FW_OK = 0
 FW_E_INVALID = -1
@@ -23,6 +24,7 @@ API_DATASTREAM = 1
 WIN_TUMBLE = 0
 WIN_HOP = 1
 WIN_CUMULATE = 2
+WIN_COUNT = 3  # DataStream countWindow: size_ms / slide_ms carry element counts
 # fw_agg_kind
 AGG_COUNT_STAR = 0
 AGG_COUNT = 1

@@ -20,6 +20,7 @@
 #include <unordered_map>
 #include <vector>
 
+#include "fw_count.h"
 #include "fw_internal.h"
 
 using namespace fw;
@@ -123,8 +124,20 @@ struct EvTimer final : KTimer {
 
 }  // namespace
 
+// fw_last_error for the translation units beside this one (fw_count.hip)
+int fw::set_error(int code, const char* fmt, ...) {
+    char buf[512];
+    va_list ap;
+    va_start(ap, fmt);
+    vsnprintf(buf, sizeof buf, fmt, ap);
+    va_end(ap);
+    g_err = buf;
+    return code;
+}
+
 struct fw_handle {
     fw_config cfg;
+    CountOp cw;  // FW_WIN_COUNT: the count-window state (cw.on); the time-window members below stay unused
     hipStream_t stream = nullptr;
     WinDesc win{};
     KeySpace ks{};
@@ -304,6 +317,17 @@ int validate_and_plan(fw_handle* h) {
     if (c.parallelism < 1 || c.parallelism > c.max_parallelism) return fail(FW_E_INVALID, "parallelism out of range");
     if (c.subtask_index < 0 || c.subtask_index >= c.parallelism) return fail(FW_E_INVALID, "subtask_index out of range");
     if (c.key_hash < FW_KEYHASH_LONG || c.key_hash > FW_KEYHASH_KEYROW) return fail(FW_E_INVALID, "bad key_hash");
+    if (c.window_kind == FW_WIN_COUNT) {  // count windows: a plan of their own (fw_count.hip)
+        int rc = cw_plan(c, &h->cw);
+        if (rc) return rc;
+        h->ks = h->cw.ks;
+        h->nv = h->cw.is_count ? 0 : 1;
+        h->slot_col[0] = h->cw.val_col;
+        h->n_out = 1;
+        h->out_cap = c.output_capacity;
+        h->stage_cap = c.max_batch_rows;
+        return FW_OK;
+    }
     h->keyrow = c.key_hash == FW_KEYHASH_KEYROW;
     if (h->keyrow) {
         if (c.api != FW_API_SQL) return fail(FW_E_INVALID, "key rows (FW_KEYHASH_KEYROW) are SQL keys");
@@ -753,6 +777,12 @@ int allocate(fw_handle* h) {
     int rc;
     const int PW = 2 + h->nw_t, PWE = h->pwe;
     if ((rc = dalloc(&h->ctrl, 1))) return rc;
+    if (h->cw.on) {  // a count handle holds its control block and the count path's own buffers
+        if ((rc = cw_allocate(&h->cw, h->stream, h->ctrl))) return rc;
+        HIP_TRY(launch_init_ctrl(h->ctrl, h->stream));
+        HIP_TRY(hipStreamSynchronize(h->stream));
+        return FW_OK;
+    }
     if ((rc = dalloc(&h->parts, (size_t)FW_MAX_PENDING * h->cap_rows * PW))) return rc;
     if ((rc = dalloc(&h->cells, (size_t)FW_MAX_PENDING * (h->ks.n_sb >> h->ks.pass_log2) * h->cell_cols))) return rc;
     if ((rc = dalloc(&h->slot_nch, FW_MAX_PENDING))) return rc;
@@ -1203,6 +1233,10 @@ int64_t entry_timer_end(const fw_handle* h, int64_t slice, uint64_t flags) {
 // ======================================================================================
 extern "C" {
 
+// entry points a count handle (FW_WIN_COUNT) does not have
+#define CW_REFUSE(h, name) \
+    if ((h)->cw.on) return fail(FW_E_INVALID, name ": not for count windows")
+
 const char* fw_last_error(void) { return g_err.c_str(); }
 int fw_abi_version(void) { return FW_ABI_VERSION; }
 
@@ -1239,6 +1273,7 @@ int fw_create(const fw_config* cfg, fw_handle** out) {
 int fw_destroy(fw_handle* h) {
     if (!h) return FW_OK;
     if (h->stream) hipStreamSynchronize(h->stream);
+    cw_free(&h->cw);
     hipFree(h->ctrl);
     hipFree(h->parts);
     hipFree(h->runs);
@@ -1466,7 +1501,9 @@ static int commit_impl(fw_handle* h, int64_t n, uint32_t packed, const int64_t* 
         vals[v] = h->d_val[b][v];
         nuls[v] = h->d_nul[b][v];
     }
-    const int rc = h->keyrow ? push_key_rows(h, n, h->d_kro[b], h->d_krb[b], h->d_ts[b], vals, nuls)
+    const int rc = h->cw.on  ? cw_push(&h->cw, n, h->d_key[b], h->cfg.key_hash == FW_KEYHASH_PRECOMPUTED ? h->d_kh[b] : nullptr,
+                                       (const uint64_t*)vals[h->slot_col[0]])
+                   : h->keyrow ? push_key_rows(h, n, h->d_kro[b], h->d_krb[b], h->d_ts[b], vals, nuls)
                              : push(h, n, h->d_key[b], h->d_ts[b],
                                     h->cfg.key_hash == FW_KEYHASH_PRECOMPUTED ? h->d_kh[b] : nullptr, vals, nuls);
     HIP_TRY(hipEventRecord(h->dstage_free[b], h->stream));
@@ -1476,6 +1513,7 @@ static int commit_impl(fw_handle* h, int64_t n, uint32_t packed, const int64_t* 
 int fw_push_device_key_rows(fw_handle* h, int64_t n, const int64_t* d_key_row_offsets, const uint8_t* d_key_row_bytes,
                             const int64_t* d_ts, const void* const* d_values, const uint8_t* const* d_nulls) {
     if (!h) return fail(FW_E_INVALID, "null handle");
+    CW_REFUSE(h, "fw_push_device_key_rows");
     if (!h->keyrow) return fail(FW_E_INVALID, "fw_push_device_key_rows needs a FW_KEYHASH_KEYROW operator");
     if (n < 0) return fail(FW_E_INVALID, "negative n");
     if (n == 0) return FW_OK;
@@ -1496,6 +1534,12 @@ int fw_push_device(fw_handle* h, int64_t n, const int64_t* d_key, const int64_t*
     if (n < 0) return fail(FW_E_INVALID, "negative n");
     ar_kick(h);
     if (n == 0) return FW_OK;
+    if (h->cw.on) {  // count windows ignore the ts column (d_ts may be NULL)
+        if (!d_key) return fail(FW_E_INVALID, "null key column");
+        if (h->cfg.key_hash == FW_KEYHASH_PRECOMPUTED && !d_key_hash) return fail(FW_E_INVALID, "key_hash column required");
+        if (h->nv > 0 && (!d_values || !d_values[h->slot_col[0]])) return fail(FW_E_INVALID, "value column %d is NULL", h->slot_col[0]);
+        return cw_push(&h->cw, n, d_key, d_key_hash, h->nv > 0 ? (const uint64_t*)d_values[h->slot_col[0]] : nullptr);
+    }
     if (!d_key || !d_ts) return fail(FW_E_INVALID, "null key/ts column");
     if (h->keyrow) return fail(FW_E_INVALID, "a FW_KEYHASH_KEYROW operator takes key rows (fw_push_device_key_rows)");
     if (h->cfg.key_hash == FW_KEYHASH_PRECOMPUTED && !d_key_hash) return fail(FW_E_INVALID, "key_hash column required");
@@ -1513,6 +1557,7 @@ int fw_push_device_segments(fw_handle* h, int32_t n_segs, int64_t seg_len, const
                             const int64_t* d_key, const int64_t* d_ts, const int32_t* d_key_hash,
                             const void* const* d_values, const uint8_t* const* d_nulls) {
     if (!h) return fail(FW_E_INVALID, "null handle");
+    CW_REFUSE(h, "fw_push_device_segments");
     if (n_segs < 0 || seg_len < 1 || (n_segs > 0 && !d_seg_counts)) return fail(FW_E_INVALID, "bad segments");
     if (h->keyrow) return fail(FW_E_INVALID, "a FW_KEYHASH_KEYROW operator takes key rows (fw_push_device_key_rows)");
     const int64_t n = (int64_t)n_segs * seg_len;
@@ -1532,6 +1577,7 @@ int fw_push_device_segments(fw_handle* h, int32_t n_segs, int64_t seg_len, const
 int fw_push_device_packed_segments(fw_handle* h, int32_t n_segs, int64_t seg_len, const int64_t* d_seg_counts,
                                    const int64_t* d_rows, int32_t row_words) {
     if (!h) return fail(FW_E_INVALID, "null handle");
+    CW_REFUSE(h, "fw_push_device_packed_segments");
     if (n_segs < 0 || seg_len < 1 || (n_segs > 0 && !d_seg_counts)) return fail(FW_E_INVALID, "bad segments");
     if (row_words != 2 + h->cfg.n_value_cols) return fail(FW_E_INVALID, "row_words %d != 2 + value columns", row_words);
     if (h->cfg.key_hash == FW_KEYHASH_PRECOMPUTED || h->keyrow || h->cfg.nullable_cols)
@@ -1546,6 +1592,11 @@ int fw_push_device_packed_segments(fw_handle* h, int32_t n_segs, int64_t seg_len
 
 int fw_advance(fw_handle* h, int64_t watermark) {
     if (!h) return fail(FW_E_INVALID, "null handle");
+    if (h->cw.on) {  // CountTrigger.onEventTime: CONTINUE -- the watermark is recorded, nothing fires
+        if (watermark > h->host_cur) h->host_cur = watermark;
+        h->cw.watermark = h->host_cur;
+        return FW_OK;
+    }
     ar_kick(h);
     // A SQL watermark below the next trigger watermark crosses no slice end: no window fires, no
     // buffer flush is due (AbstractSliceSyncStateWindowAggProcessor.advanceProgress :139-153 only
@@ -1575,6 +1626,10 @@ int fw_advance(fw_handle* h, int64_t watermark) {
 
 int fw_advance_device(fw_handle* h, const int64_t* d_watermark) {
     if (!h || !d_watermark) return fail(FW_E_INVALID, "null argument");
+    if (h->cw.on) {  // recorded on the device (fw_stats.current_watermark), nothing fires
+        HIP_TRY(hipMemcpyAsync(&h->ctrl->cur, d_watermark, sizeof(int64_t), hipMemcpyDeviceToDevice, h->stream));
+        return FW_OK;
+    }
     MergeArgs a = merge_args(h, INT64_MIN, 0);
     a.wm_dev = d_watermark;
     HIP_TRY(launch_merge_fire(a, h->stream, h->timer));
@@ -1592,11 +1647,57 @@ int fw_advance_device(fw_handle* h, const int64_t* d_watermark) {
 
 int fw_flush(fw_handle* h) {
     if (!h) return fail(FW_E_INVALID, "null handle");
+    if (h->cw.on) return FW_OK;  // every push is folded into the state when it is pushed
     return force_flush(h);
+}
+
+// a count handle's rows: one per fire, in the device's order; first_ord orders them as the reference emits
+static int cw_results(fw_handle* h, fw_result* out, int copy_to_host) {
+    CountOp& w = h->cw;
+    Ctrl c;
+    int rc = read_ctrl(h, &c);
+    if (rc) return rc;
+    const int64_t n = (int64_t)c.out_count[0];
+    if (n > w.out_cap)
+        return fail(FW_E_CAPACITY, "%lld result rows exceed output_capacity %lld (read results more often)", (long long)n,
+                    (long long)w.out_cap);
+    memset(out, 0, sizeof *out);
+    out->n = n;
+    if (!copy_to_host) {
+        out->key = w.out_key;
+        out->window_start = w.out_ws;
+        out->window_end = w.out_we;
+        out->values[0] = (int64_t*)w.out_val;
+        out->first_ord = w.out_ord;
+        out->null_mask = w.out_null;
+        return FW_OK;
+    }
+    h->r_key.resize(n);
+    h->r_ws.resize(n);
+    h->r_we.resize(n);
+    h->r_val[0].resize(n);
+    h->r_val[1].resize(n);
+    h->r_null.assign(n, 0u);
+    if (n) {
+        HIP_TRY(hipMemcpyAsync(h->r_key.data(), w.out_key, n * 8, hipMemcpyDeviceToHost, h->stream));
+        HIP_TRY(hipMemcpyAsync(h->r_ws.data(), w.out_ws, n * 8, hipMemcpyDeviceToHost, h->stream));
+        HIP_TRY(hipMemcpyAsync(h->r_we.data(), w.out_we, n * 8, hipMemcpyDeviceToHost, h->stream));
+        HIP_TRY(hipMemcpyAsync(h->r_val[0].data(), w.out_val, n * 8, hipMemcpyDeviceToHost, h->stream));
+        HIP_TRY(hipMemcpyAsync(h->r_val[1].data(), w.out_ord, n * 8, hipMemcpyDeviceToHost, h->stream));
+        HIP_TRY(hipStreamSynchronize(h->stream));
+    }
+    out->key = h->r_key.data();
+    out->window_start = h->r_ws.data();
+    out->window_end = h->r_we.data();
+    out->values[0] = (int64_t*)h->r_val[0].data();
+    out->first_ord = (int64_t*)h->r_val[1].data();
+    out->null_mask = h->r_null.data();
+    return FW_OK;
 }
 
 int fw_results(fw_handle* h, fw_result* out, int copy_to_host) {
     if (!h || !out) return fail(FW_E_INVALID, "null argument");
+    if (h->cw.on) return cw_results(h, out, copy_to_host);
     if (h->reset_pending) {  // consumed and nothing emitted since
         Ctrl c;
         int rc = read_ctrl(h, &c);
@@ -1696,6 +1797,7 @@ int fw_results(fw_handle* h, fw_result* out, int copy_to_host) {
 
 int fw_results_async(fw_handle* h) {
     if (!h) return fail(FW_E_INVALID, "null handle");
+    CW_REFUSE(h, "fw_results_async");
     if (h->keyrow) return fail(FW_E_INVALID, "key-row operators return their rows through fw_results");
     int rc = alloc_async_results(h);
     if (rc) return rc;
@@ -1765,6 +1867,7 @@ int fw_results_async(fw_handle* h) {
 
 int fw_results_device_segments(fw_handle* h, fw_result_segments* out) {
     if (!h || !out) return fail(FW_E_INVALID, "null argument");
+    CW_REFUSE(h, "fw_results_device_segments");
     if (h->keyrow) return fail(FW_E_INVALID, "key-row operators return their rows through fw_results");
     memset(out, 0, sizeof *out);
     const int na = h->n_out;
@@ -1786,6 +1889,7 @@ int fw_results_device_segments(fw_handle* h, fw_result_segments* out) {
 
 int fw_results_device(fw_handle* h, fw_result* out, int64_t** d_n) {
     if (!h || !out || !d_n) return fail(FW_E_INVALID, "null argument");
+    CW_REFUSE(h, "fw_results_device");
     if (h->keyrow) return fail(FW_E_INVALID, "key-row operators return their rows through fw_results");
     memset(out, 0, sizeof *out);
     *d_n = h->coff + h->ks.n_sb + 1;
@@ -1830,6 +1934,7 @@ int fw_results_device(fw_handle* h, fw_result* out, int64_t** d_n) {
 
 int fw_results_ready(fw_handle* h, fw_result* out) {
     if (!h || !out) return fail(FW_E_INVALID, "null argument");
+    CW_REFUSE(h, "fw_results_ready");
     memset(out, 0, sizeof *out);
     if (h->ar_qn == 0) return fail(FW_E_STATE, "fw_results_ready without an outstanding fw_results_async");
     const int b = h->ar_q[h->ar_qhead];  // the oldest outstanding collection
@@ -1864,6 +1969,7 @@ int fw_results_ready(fw_handle* h, fw_result* out) {
 
 int fw_first_element_events(fw_handle* h, fw_ordinal_events* out) {
     if (!h || !out) return fail(FW_E_INVALID, "null argument");
+    CW_REFUSE(h, "fw_first_element_events");
     memset(out, 0, sizeof *out);
     if (!h->ordev_cap) return fail(FW_E_STATE, "the operator does not track first elements (ds_first_ordinals = 0)");
     Ctrl c;
@@ -1889,6 +1995,7 @@ int fw_first_element_events(fw_handle* h, fw_ordinal_events* out) {
 
 int fw_late_records(fw_handle* h, fw_late_rows* out) {
     if (!h || !out) return fail(FW_E_INVALID, "null argument");
+    CW_REFUSE(h, "fw_late_records");
     memset(out, 0, sizeof *out);
     if (!h->side_cap) return fail(FW_E_STATE, "the operator has no late side output (late_side_output = 0)");
     Ctrl c;
@@ -1923,6 +2030,10 @@ int fw_late_records(fw_handle* h, fw_late_rows* out) {
 
 int fw_results_reset(fw_handle* h) {
     if (!h) return fail(FW_E_INVALID, "null handle");
+    if (h->cw.on) {  // stream-ordered: rows of pushes issued before the call are consumed, later ones kept
+        HIP_TRY(hipMemsetAsync(&h->ctrl->out_count[0], 0, sizeof(uint64_t), h->stream));
+        return FW_OK;
+    }
     // no launch: the next merge launch starts every output slab and the overflow region afresh
     h->reset_pending = true;
     return FW_OK;
@@ -1930,6 +2041,21 @@ int fw_results_reset(fw_handle* h) {
 
 int fw_get_stats(fw_handle* h, fw_stats* out) {
     if (!h || !out) return fail(FW_E_INVALID, "null argument");
+    if (h->cw.on) {
+        Ctrl cc;
+        HIP_TRY(hipMemcpyAsync(&cc, h->ctrl, sizeof(Ctrl), hipMemcpyDeviceToHost, h->stream));
+        HIP_TRY(hipStreamSynchronize(h->stream));
+        memset(out, 0, sizeof *out);
+        out->current_watermark = std::max<int64_t>(cc.cur, h->host_cur);
+        out->next_trigger_progress = INT64_MAX;  // no watermark triggers a count window
+        out->live_state_entries = cc.live_entries;  // keys in the table
+        out->results_available = std::min<int64_t>((int64_t)cc.out_count[0], h->cw.out_cap);
+        out->num_fired_windows = (int64_t)cc.fired;
+        out->error_flags = (int32_t)cc.error;
+        out->num_superbuckets = h->ks.n_sb;
+        out->superbucket_capacity = h->cw.cap_e;
+        return FW_OK;
+    }
     Ctrl c;
     const int nsb = h->ks.n_sb;
     std::vector<int32_t> cnt(nsb), sbo(nsb);
@@ -1972,6 +2098,7 @@ int fw_get_stats(fw_handle* h, fw_stats* out) {
 
 int fw_set_profiling(fw_handle* h, int enable) {
     if (!h) return fail(FW_E_INVALID, "null handle");
+    CW_REFUSE(h, "fw_set_profiling");
     HIP_TRY(hipStreamSynchronize(h->stream));
     delete h->timer;
     h->timer = nullptr;
@@ -1990,6 +2117,7 @@ int fw_set_profiling(fw_handle* h, int enable) {
 
 int fw_get_kernel_times(fw_handle* h, fw_kernel_times* out) {
     if (!h || !out) return fail(FW_E_INVALID, "null argument");
+    CW_REFUSE(h, "fw_get_kernel_times");
     memset(out, 0, sizeof *out);
     unsigned long long st[N_STAMPS];
     HIP_TRY(hipMemcpyAsync(st, h->stamps, sizeof st, hipMemcpyDeviceToHost, h->stream));
@@ -2158,6 +2286,10 @@ static int64_t kr_lookup(const std::vector<std::pair<int64_t, int64_t>>& map, in
 
 int fw_snapshot(fw_handle* h, void* buf, int64_t capacity, int64_t* size) {
     if (!h || !size) return fail(FW_E_INVALID, "null argument");
+    if (h->cw.on) {
+        h->cw.watermark = h->host_cur;
+        return cw_snapshot(&h->cw, -1, buf, capacity, size);
+    }
     int rc = force_flush(h);  // prepareSnapshotPreBarrier -> windowBuffer.flush()
     if (rc) return rc;
     Ctrl c;
@@ -2197,6 +2329,11 @@ int fw_snapshot(fw_handle* h, void* buf, int64_t capacity, int64_t* size) {
 
 int fw_restore(fw_handle* h, const void* buf, int64_t size) {
     if (!h || !buf) return fail(FW_E_INVALID, "null argument");
+    if (h->cw.on) {
+        const int rc = cw_restore(&h->cw, false, buf, size);
+        if (!rc) h->host_cur = h->cw.watermark;
+        return rc;
+    }
     SnapHeader hd;
     if (size < (int64_t)sizeof hd) return fail(FW_E_INVALID, "snapshot truncated");
     memcpy(&hd, buf, sizeof hd);
@@ -2296,6 +2433,11 @@ static const uint64_t KG_MAGIC = 0x464c4b574b473033ull;  // "FLKWKG03"
 
 int fw_snapshot_key_group(fw_handle* h, int32_t key_group, void* buf, int64_t capacity, int64_t* size) {
     if (!h || !size) return fail(FW_E_INVALID, "null argument");
+    if (h->cw.on) {
+        if (key_group < 0) return fail(FW_E_INVALID, "key group %d is not owned by this subtask", key_group);
+        h->cw.watermark = h->host_cur;
+        return cw_snapshot(&h->cw, key_group, buf, capacity, size);
+    }
     const KeySpace& ks = h->ks;
     const int li = key_group - ks.kg_start;
     if (li < 0 || li >= ks.n_kg) return fail(FW_E_INVALID, "key group %d is not owned by this subtask", key_group);
@@ -2334,6 +2476,7 @@ int fw_snapshot_key_group(fw_handle* h, int32_t key_group, void* buf, int64_t ca
 
 int fw_restore_key_group(fw_handle* h, const void* buf, int64_t size) {
     if (!h || !buf) return fail(FW_E_INVALID, "null argument");
+    if (h->cw.on) return cw_restore(&h->cw, true, buf, size);
     KgHeader hd;
     if (size < (int64_t)sizeof hd) return fail(FW_E_INVALID, "key-group snapshot truncated");
     memcpy(&hd, buf, sizeof hd);
@@ -2618,6 +2761,7 @@ int heap_check(const fw_handle* h, const fw_heap_state_ids* ids) {
 int fw_snapshot_key_group_heap(fw_handle* h, int32_t key_group, const fw_heap_state_ids* ids, void* buf,
                                int64_t capacity, int64_t* size) {
     if (!h || !size) return fail(FW_E_INVALID, "null argument");
+    CW_REFUSE(h, "fw_snapshot_key_group_heap");
     int rc = heap_check(h, ids);
     if (rc) return rc;
     // the device state of the key group, in this library's own key-group format
@@ -2739,6 +2883,7 @@ int fw_snapshot_key_group_heap(fw_handle* h, int32_t key_group, const fw_heap_st
 
 int fw_restore_key_group_heap(fw_handle* h, const void* buf, int64_t size, const fw_heap_state_ids* ids) {
     if (!h || !buf || size < 0) return fail(FW_E_INVALID, "null argument");
+    CW_REFUSE(h, "fw_restore_key_group_heap");
     int rc = heap_check(h, ids);
     if (rc) return rc;
     HeapReader r{(const uint8_t*)buf, (size_t)size};
@@ -2947,6 +3092,7 @@ void ds_words_of(const fw_handle* h, uint64_t value, int64_t first, uint64_t* ac
 
 int fw_ds_snapshot_key_group(fw_handle* h, int32_t key_group, fw_ds_window* out, int64_t capacity, int64_t* n) {
     if (!h || !n) return fail(FW_E_INVALID, "null argument");
+    CW_REFUSE(h, "fw_ds_snapshot_key_group");
     int rc = ds_state_check(h);
     if (rc) return rc;
     int64_t sz = 0;
@@ -2982,6 +3128,7 @@ int fw_ds_snapshot_key_group(fw_handle* h, int32_t key_group, fw_ds_window* out,
 
 int fw_ds_restore_key_group(fw_handle* h, int32_t key_group, const fw_ds_window* in, int64_t n, int64_t next_push_seq) {
     if (!h || (n > 0 && !in) || n < 0) return fail(FW_E_INVALID, "null argument");
+    CW_REFUSE(h, "fw_ds_restore_key_group");
     int rc = ds_state_check(h);
     if (rc) return rc;
     const WinDesc& win = h->win;
@@ -3066,6 +3213,7 @@ int fw_host_time_op(const fw_config* cfg, int32_t what, int64_t x, int64_t* out)
     h.cfg = *cfg;
     const int rc = validate_and_plan(&h);  // host-only planning; w.tz points at h's host copy
     if (rc) return rc;
+    CW_REFUSE(&h, "fw_host_time_op");
     const WinDesc& w = h.win;
     switch (what) {
         case 0: *out = tz_to_utc_ts(w.tz, x); break;
@@ -3075,6 +3223,20 @@ int fw_host_time_op(const fw_config* cfg, int32_t what, int64_t x, int64_t* out)
         case 4: *out = window_start_of(w, x); break;
         default: return fail(FW_E_INVALID, "bad time op %d", what);
     }
+    return FW_OK;
+}
+
+
+int fw_host_count_step(const fw_config* cfg, int64_t index, int64_t* slice, int32_t* ring_slot, int32_t* fires,
+                       int64_t* window_start, int32_t* n_slices) {
+    if (!cfg || !slice || !ring_slot || !fires || !window_start || !n_slices) return fail(FW_E_INVALID, "null argument");
+    if (cfg->window_kind != FW_WIN_COUNT) return fail(FW_E_INVALID, "fw_host_count_step needs a FW_WIN_COUNT configuration");
+    if (index < 0) return fail(FW_E_INVALID, "negative element index");
+    fw_handle h;
+    h.cfg = *cfg;
+    const int rc = validate_and_plan(&h);
+    if (rc) return rc;
+    count_step(h.cw.d, index, slice, ring_slot, fires, window_start, n_slices);
     return FW_OK;
 }
 

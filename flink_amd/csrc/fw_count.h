@@ -1,0 +1,122 @@
+// fw_count.h -- DataStream count windows (KeyedStream.countWindow) as count slices.
+//
+// countWindow(size, slide) is GlobalWindows + CountTrigger.of(slide) + CountEvictor.of(size), run by
+// EvictingWindowOperator; countWindow(size) is GlobalWindows + PurgingTrigger(CountTrigger.of(size)).
+// A key fires when its element count c reaches a multiple of slide, and the fired window holds the
+// key's last min(c, size) elements.  With g = gcd(size, slide) both c and c - size are multiples of
+// g, so every fired window is exactly the last R = size / g complete count slices of g elements:
+// the state per key is a count and a ring of R slice accumulators (DESIGN.md "Count windows").
+//
+// This header holds the slice arithmetic the kernel and fw_host_count_step share (FW_HD), the
+// per-handle state of a count operator (CountOp) and the entry points fw_api.hip dispatches to.
+#pragma once
+#include "fw_internal.h"
+
+namespace fw {
+
+// accumulator classes of a count window's one word
+enum CountWordOp : int32_t { CW_ADD_I = 0, CW_ADD_F = 1, CW_MIN = 2, CW_MAX = 3 };
+
+struct CountDesc {
+    int64_t size;       // CountEvictor.of(size)
+    int64_t slide;      // CountTrigger.of(slide)
+    int64_t g;          // gcd(size, slide): elements per count slice
+    int32_t R;          // size / g: ring slots per key (<= FW_COUNT_MAX_SLICES)
+    int32_t op;         // CountWordOp
+    UDiv g_div;         // divisor g
+    UDiv slide_div;     // divisor slide
+    UDiv r_div;         // divisor R
+};
+
+// One element of a key, 0-based per-key index `index`: the count slice it falls in, that slice's
+// ring slot, whether the element triggers a fire (CountTrigger: the count reached a multiple of
+// slide) and, if so, the window's first element index max(0, c - size) and the ring slots the window
+// reads (the slices [slice - n_slices + 1, slice], oldest first).
+FW_HD void count_step(const CountDesc& d, int64_t index, int64_t* slice, int32_t* ring_slot, int32_t* fires,
+                      int64_t* window_start, int32_t* n_slices) {
+    const uint64_t s = udiv((uint64_t)index, d.g_div);
+    *slice = (int64_t)s;
+    *ring_slot = (int32_t)(s - udiv(s, d.r_div) * (uint64_t)d.R);
+    const uint64_t c = (uint64_t)index + 1;
+    const bool f = c - udiv(c, d.slide_div) * (uint64_t)d.slide == 0;
+    *fires = f ? 1 : 0;
+    const int64_t held = (int64_t)c < d.size ? (int64_t)c : d.size;  // min(c, size), a multiple of g at a fire
+    *window_start = f ? (int64_t)c - held : 0;
+    *n_slices = f ? (int32_t)udiv((uint64_t)held, d.g_div) : 0;
+}
+
+// op(older, newer): the reduce of two partial aggregates, the older one on the left (DOUBLE sums are
+// added in that order; min / max compare the sortable keys of fw_device.h dkey)
+FW_HD uint64_t count_fold(int32_t op, uint64_t a, uint64_t b) {
+    switch (op) {
+        case CW_ADD_I: return a + b;
+        case CW_ADD_F: {
+            double x, y;
+            __builtin_memcpy(&x, &a, 8);
+            __builtin_memcpy(&y, &b, 8);
+            x += y;
+            uint64_t r;
+            __builtin_memcpy(&r, &x, 8);
+            return r;
+        }
+        case CW_MIN: return (int64_t)b < (int64_t)a ? b : a;
+        default: return (int64_t)b > (int64_t)a ? b : a;
+    }
+}
+
+// the table's own slot hash of a key inside its superbucket (not a Flink-visible hash)
+FW_HD uint32_t count_slot_hash(int64_t key, uint32_t mask) { return (uint32_t)mix64((uint64_t)key) & mask; }
+
+constexpr int CW_TILE = 1024;                       // rows per tile = threads per workgroup
+constexpr int64_t CW_CLAIMED = INT64_MIN;           // count word of an entry claimed in the running tile
+constexpr int64_t CW_MAX_HIST = (int64_t)1 << 26;   // [superbucket][chunk] partition counters a handle may hold
+
+// Per-handle state of a count operator.  The key table is open addressed, partitioned by
+// superbucket: entry e of superbucket sb is table[(sb * cap_e + e) * pwe ..]: key, count, ring[R].
+// count == 0 marks an empty slot (a key enters the table with its first element).
+struct CountOp {
+    bool on = false;
+    CountDesc d{};
+    KeySpace ks{};
+    int32_t vtype = 0;      // fw_value_type of the aggregated field
+    int32_t is_count = 0;   // COUNT_STAR: every element counts 1, no value column is read
+    int32_t val_col = 0;    // value column the aggregate reads
+    int32_t cap_e = 0;      // table slots per superbucket (power of two)
+    int32_t pwe = 0;        // words per entry: 2 + R
+    int64_t cap_rows = 0;   // rows per launch (max_batch_rows)
+    int64_t max_nch = 0;    // partition chunks per launch
+    int64_t out_cap = 0;
+    hipStream_t stream = nullptr;  // the handle's
+    Ctrl* ctrl = nullptr;          // the handle's control block: out_count[0], fired, live_entries, error
+    uint64_t* table = nullptr;
+    // partition scratch of one launch
+    int32_t* hist = nullptr;       // [n_sb][n_chunks]: rows of chunk in superbucket, then their exclusive scan
+    int32_t* seg = nullptr;        // [n_sb + 1]: rows per superbucket, then segment starts
+    int32_t* s_sb = nullptr;       // [cap_rows] chunk-sorted: superbucket (-1: dropped), row, rank in (chunk, sb)
+    uint32_t* s_row = nullptr;
+    int32_t* s_rank = nullptr;
+    uint32_t* perm = nullptr;      // [cap_rows] row indices grouped by superbucket, arrival order inside
+    // result rows
+    int64_t* out_key = nullptr;
+    int64_t* out_ws = nullptr;
+    int64_t* out_we = nullptr;
+    uint64_t* out_val = nullptr;
+    int64_t* out_ord = nullptr;
+    uint32_t* out_null = nullptr;  // zeros
+    int64_t push_seq = 0;
+    int64_t watermark = INT64_MIN;
+};
+
+// error reporting of fw_api.hip (fw_last_error): returns code
+int set_error(int code, const char* fmt, ...) __attribute__((format(printf, 2, 3)));
+
+// validation + plan of a FW_WIN_COUNT configuration; no device call
+int cw_plan(const fw_config& c, CountOp* op);
+int cw_allocate(CountOp* op, hipStream_t stream, Ctrl* ctrl);
+void cw_free(CountOp* op);
+// folds n rows into the state and appends the fired rows (stream-ordered, asynchronous)
+int cw_push(CountOp* op, int64_t n, const int64_t* d_key, const int32_t* d_khash, const uint64_t* d_val);
+int cw_snapshot(CountOp* op, int32_t key_group, void* buf, int64_t capacity, int64_t* size);
+int cw_restore(CountOp* op, bool key_group, const void* buf, int64_t size);
+
+}  // namespace fw

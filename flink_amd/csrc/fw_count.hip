@@ -1,0 +1,723 @@
+// fw_count.hip -- the count-window path (fw_count.h): kernels and the per-handle host code.
+//
+// One push is folded into the key table when it is pushed, in six stream-ordered launches:
+//   k_cw_part     per chunk of CW_TILE rows: route every key to its superbucket, sort (superbucket,
+//                 position) in LDS, and write the chunk's rows grouped by superbucket with each row's
+//                 rank inside its (chunk, superbucket) group, and the group sizes (hist)
+//   k_cw_scan     per superbucket: exclusive scan of its group sizes over the chunks
+//   k_cw_seg      exclusive scan of the superbucket totals: segment starts
+//   k_cw_scatter  row indices to their segment, input order kept inside a superbucket
+//   k_cw_fold     one workgroup per superbucket walks its segment in arrival order, a tile at a time
+// No workgroup waits on another: the only cross-workgroup traffic is counters (atomic adds).
+#include <hip/hip_runtime.h>
+
+#include <algorithm>
+#include <cstring>
+#include <vector>
+
+#include "fw_count.h"
+
+namespace fw {
+namespace {
+
+#define CW_TRY(expr)                                                                                 \
+    do {                                                                                             \
+        hipError_t e_ = (expr);                                                                      \
+        if (e_ != hipSuccess) return set_error(FW_E_DEVICE, "%s: %s", #expr, hipGetErrorString(e_)); \
+    } while (0)
+
+constexpr uint32_t CW_PAD = 0x80000000u;  // position word of a padding element: sorts after every row
+
+// (padding, key, position) order; positions are unique, so the order is total and the sort stable
+__device__ __forceinline__ bool cw_less(uint64_t ka, uint32_t pa, uint64_t kb, uint32_t pb) {
+    const uint32_t ia = pa >> 31, ib = pb >> 31;
+    if (ia != ib) return ia < ib;
+    if (ka != kb) return ka < kb;
+    return pa < pb;
+}
+
+// bitonic sort of the first n2 (a power of two <= CW_TILE) pairs; every thread of the workgroup
+// calls it, after a barrier behind the stores that filled k / p; it ends with a barrier
+__device__ void cw_sort(uint64_t* k, uint32_t* p, int n2) {
+    const int t = threadIdx.x;
+    for (int kk = 2; kk <= n2; kk <<= 1)
+        for (int j = kk >> 1; j > 0; j >>= 1) {
+            const int x = t ^ j;
+            if (t < n2 && x > t) {
+                const bool asc = (t & kk) == 0;
+                const uint64_t ka = k[t], kb = k[x];
+                const uint32_t pa = p[t], pb = p[x];
+                if (cw_less(kb, pb, ka, pa) == asc) {
+                    k[t] = kb;
+                    k[x] = ka;
+                    p[t] = pb;
+                    p[x] = pa;
+                }
+            }
+            __syncthreads();
+        }
+}
+
+// inclusive max scan of a[0 .. n2); every thread calls it after a barrier; ends with a barrier
+__device__ void cw_max_scan(int32_t* a, int n2) {
+    const int t = threadIdx.x;
+    for (int d = 1; d < n2; d <<= 1) {
+        const bool on = t < n2 && t >= d;
+        const int32_t v = on ? a[t - d] : 0;
+        __syncthreads();
+        if (on && v > a[t]) a[t] = v;
+        __syncthreads();
+    }
+}
+
+__device__ __forceinline__ int cw_pow2(int n) {
+    int p = 2;
+    while (p < n) p <<= 1;
+    return p;
+}
+
+struct CwPartArgs {
+    const int64_t* key;
+    const int32_t* khash;
+    int64_t n;
+    int32_t n_chunks;
+    KeySpace ks;
+    Ctrl* ctrl;
+    int32_t* hist;
+    int32_t* s_sb;
+    uint32_t* s_row;
+    int32_t* s_rank;
+};
+
+__global__ __launch_bounds__(CW_TILE) void k_cw_part(CwPartArgs a) {
+    __shared__ uint64_t sk[CW_TILE];
+    __shared__ uint32_t sp[CW_TILE];
+    __shared__ int32_t hx[CW_TILE];
+    const int t = threadIdx.x;
+    const int64_t c0 = (int64_t)blockIdx.x * CW_TILE;
+    const int nrows = (int)(a.n - c0 < CW_TILE ? a.n - c0 : CW_TILE);
+    const int n2 = cw_pow2(nrows);
+    int32_t sb = -1;
+    if (t < nrows) {
+        uint32_t m;
+        sb = route_key(a.ks, a.key[c0 + t], a.khash ? a.khash[c0 + t] : 0, &m);
+        if (sb < 0 || sb >= a.ks.n_sb) {  // key group outside the subtask's range: the row is dropped
+            atomicOr(&a.ctrl->error, ERR_KEYGROUP);
+            sb = -1;
+        }
+    }
+    sk[t] = sb >= 0 ? (uint64_t)sb : ~0ull;
+    sp[t] = sb >= 0 ? (uint32_t)t : (CW_PAD | (uint32_t)t);
+    __syncthreads();
+    cw_sort(sk, sp, n2);
+    const bool v = t < n2 && !(sp[t] >> 31);
+    const bool head = v && (t == 0 || sk[t - 1] != sk[t]);
+    hx[t] = head ? t : 0;
+    __syncthreads();
+    cw_max_scan(hx, n2);
+    if (v) {
+        const int32_t rank = t - hx[t];
+        const int32_t s = (int32_t)sk[t];
+        a.s_sb[c0 + t] = s;
+        a.s_row[c0 + t] = (uint32_t)(c0 + sp[t]);
+        a.s_rank[c0 + t] = rank;
+        const bool tail = t == n2 - 1 || (sp[t + 1] >> 31) || sk[t + 1] != sk[t];
+        if (tail) a.hist[(size_t)s * a.n_chunks + blockIdx.x] = rank + 1;
+    } else if (t < nrows) {
+        a.s_sb[c0 + t] = -1;
+    }
+}
+
+// inclusive scan over the workgroup's NT threads; every thread calls it; *total = the sum
+template <int NT>
+__device__ int32_t cw_block_scan(int32_t x, int32_t* buf, int32_t* total) {
+    const int t = threadIdx.x;
+    buf[t] = x;
+    __syncthreads();
+    for (int d = 1; d < NT; d <<= 1) {
+        const int32_t v = t >= d ? buf[t - d] : 0;
+        __syncthreads();
+        buf[t] += v;
+        __syncthreads();
+    }
+    const int32_t r = buf[t];
+    *total = buf[NT - 1];
+    __syncthreads();
+    return r;
+}
+
+// superbucket blockIdx.x: hist[sb][0 .. n_chunks) -> its exclusive scan; seg[sb] = the total
+__global__ __launch_bounds__(256) void k_cw_scan(int32_t* hist, int32_t* seg, int32_t n_chunks) {
+    __shared__ int32_t buf[256];
+    int32_t* row = hist + (size_t)blockIdx.x * n_chunks;
+    int32_t carry = 0;
+    for (int base = 0; base < n_chunks; base += 256) {
+        const int i = base + threadIdx.x;
+        const int32_t x = i < n_chunks ? row[i] : 0;
+        int32_t tot;
+        const int32_t inc = cw_block_scan<256>(x, buf, &tot);
+        if (i < n_chunks) row[i] = carry + inc - x;
+        carry += tot;
+    }
+    if (threadIdx.x == 0) seg[blockIdx.x] = carry;
+}
+
+// seg[0 .. n_sb) totals -> seg[0 .. n_sb] segment starts (one workgroup)
+__global__ __launch_bounds__(CW_TILE) void k_cw_seg(int32_t* seg, int32_t n_sb) {
+    __shared__ int32_t buf[CW_TILE];
+    int32_t carry = 0;
+    for (int base = 0; base < n_sb; base += CW_TILE) {
+        const int i = base + threadIdx.x;
+        const int32_t x = i < n_sb ? seg[i] : 0;
+        int32_t tot;
+        const int32_t inc = cw_block_scan<CW_TILE>(x, buf, &tot);
+        if (i < n_sb) seg[i] = carry + inc - x;
+        carry += tot;
+    }
+    if (threadIdx.x == 0) seg[n_sb] = carry;
+}
+
+__global__ __launch_bounds__(256) void k_cw_scatter(int64_t n, int32_t n_chunks, const int32_t* hist, const int32_t* seg,
+                                                     const int32_t* s_sb, const uint32_t* s_row, const int32_t* s_rank,
+                                                     uint32_t* perm) {
+    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (i >= n) return;
+    const int32_t sb = s_sb[i];
+    if (sb < 0) return;
+    const int64_t dst = (int64_t)seg[sb] + hist[(size_t)sb * n_chunks + (i / CW_TILE)] + s_rank[i];
+    if (dst < n) perm[dst] = s_row[i];  // (always: the groups' sizes sum to the kept rows)
+}
+
+struct CwFoldArgs {
+    const int64_t* key;
+    const uint64_t* val;
+    const uint32_t* perm;
+    const int32_t* seg;
+    CountDesc d;
+    int32_t cap_e, pwe, is_count, vtype;
+    uint64_t* table;
+    Ctrl* ctrl;
+    int64_t* out_key;
+    int64_t* out_ws;
+    int64_t* out_we;
+    uint64_t* out_val;
+    int64_t* out_ord;
+    int64_t out_cap;
+    int64_t ord_base;  // push_seq << 32 | row offset of this launch within its call
+};
+
+__global__ __launch_bounds__(CW_TILE) void k_cw_fold(CwFoldArgs a) {
+    __shared__ uint64_t sk[CW_TILE];     // sorted keys
+    __shared__ uint32_t sp[CW_TILE];     // their positions in the tile (arrival order)
+    __shared__ uint64_t pv[CW_TILE];     // by position: value word, row index
+    __shared__ uint32_t prow[CW_TILE];
+    __shared__ uint64_t sv[CW_TILE];     // segmented scan over (key, slice) runs
+    __shared__ uint32_t sf[CW_TILE];
+    __shared__ int32_t hx[CW_TILE];      // sorted index of the row's key run head
+    __shared__ int32_t hslot[CW_TILE];   // by head: table slot (-1: table full), count before the tile, run length
+    __shared__ int64_t hc0[CW_TILE];
+    __shared__ int32_t hlen[CW_TILE];
+    __shared__ uint32_t n_fire, n_new;
+    __shared__ unsigned long long fire_base;
+
+    const int t = threadIdx.x;
+    const CountDesc& d = a.d;
+    const int op = d.op, R = d.R, pwe = a.pwe;
+    const uint32_t mask = (uint32_t)a.cap_e - 1u;
+    const int64_t seg0 = a.seg[blockIdx.x], seg1 = a.seg[blockIdx.x + 1];
+    uint64_t* tab = a.table + (size_t)blockIdx.x * a.cap_e * pwe;
+    const bool dbl_cmp = a.vtype == FW_T_F64 && (op == CW_MIN || op == CW_MAX);
+
+    for (int64_t base = seg0; base < seg1; base += CW_TILE) {
+        const int nt = (int)(seg1 - base < CW_TILE ? seg1 - base : CW_TILE);
+        const int n2 = cw_pow2(nt);
+        if (t == 0) {
+            n_fire = 0;
+            n_new = 0;
+        }
+        if (t < nt) {
+            const uint32_t row = a.perm[base + t];
+            uint64_t v = a.is_count ? 1ull : a.val[row];
+            if (dbl_cmp) v = (uint64_t)dkey(v);
+            sk[t] = (uint64_t)a.key[row];
+            sp[t] = (uint32_t)t;
+            pv[t] = v;
+            prow[t] = row;
+        } else {
+            sk[t] = ~0ull;
+            sp[t] = CW_PAD | (uint32_t)t;
+        }
+        __syncthreads();
+        cw_sort(sk, sp, n2);
+        const bool valid = t < nt;  // the padding sorted behind the rows
+        const bool head = valid && (t == 0 || sk[t - 1] != sk[t]);
+        hx[t] = head ? t : 0;
+        __syncthreads();
+        cw_max_scan(hx, n2);
+
+        // ---- the key's table slot: look every distinct key up, then insert the new ones
+        int32_t slot = -1;
+        int64_t cnt0 = 0;
+        bool ins = false;
+        const int64_t mykey = (int64_t)sk[t];
+        if (head) {
+            uint32_t e = count_slot_hash(mykey, mask);
+            for (int p = 0; p < a.cap_e; p++, e = (e + 1) & mask) {
+                const int64_t c = (int64_t)tab[(size_t)e * pwe + 1];
+                if (c == 0) {
+                    ins = true;
+                    break;
+                }
+                if ((int64_t)tab[(size_t)e * pwe] == mykey) {
+                    slot = (int32_t)e;
+                    cnt0 = c;
+                    break;
+                }
+            }
+        }
+        __syncthreads();
+        if (head && ins) {  // the heads' keys are distinct: a slot another head claimed is just occupied
+            uint32_t e = count_slot_hash(mykey, mask);
+            for (int p = 0; p < a.cap_e; p++, e = (e + 1) & mask) {
+                const unsigned long long old = atomicCAS((unsigned long long*)&tab[(size_t)e * pwe + 1], 0ull,
+                                                         (unsigned long long)CW_CLAIMED);
+                if (old == 0ull) {
+                    tab[(size_t)e * pwe] = (uint64_t)mykey;
+                    slot = (int32_t)e;
+                    cnt0 = 0;
+                    atomicAdd(&n_new, 1u);
+                    break;
+                }
+            }
+        }
+        if (head) {
+            if (slot < 0) atomicOr(&a.ctrl->error, ERR_STATE);  // table full: the key's rows are dropped
+            hslot[t] = slot;
+            hc0[t] = cnt0;
+        }
+        if (valid && (t == nt - 1 || sk[t + 1] != sk[t])) hlen[hx[t]] = t - hx[t] + 1;
+        __syncthreads();
+
+        // ---- per row: its per-key index and count slice; segmented scan over (key, slice) runs
+        const int hi = valid ? hx[t] : 0;
+        slot = valid ? hslot[hi] : -1;
+        cnt0 = valid ? hc0[hi] : 0;
+        const bool live = valid && slot >= 0;
+        const int rank = t - hi;
+        const int64_t idx = cnt0 + rank;
+        int64_t sl = 0, ws = 0;
+        int32_t rs = 0, fires = 0, ns = 0;
+        if (valid) count_step(d, idx, &sl, &rs, &fires, &ws, &ns);
+        const int64_t s0k = (int64_t)udiv((uint64_t)cnt0, d.g_div);  // the key's first slice in this tile
+        const bool partial0 = cnt0 - s0k * d.g != 0;                 // ... began before the tile
+        if (t < n2) {
+            sv[t] = valid ? pv[sp[t]] : 0;
+            sf[t] = (!valid || rank == 0 || idx - sl * d.g == 0) ? 1u : 0u;
+        }
+        __syncthreads();
+        for (int dd = 1; dd < n2; dd <<= 1) {
+            const bool take = t < n2 && t >= dd && !sf[t];
+            uint64_t ov = 0;
+            uint32_t of = 0;
+            if (take) {
+                ov = sv[t - dd];
+                of = sf[t - dd];
+            }
+            __syncthreads();
+            if (take) {
+                sv[t] = count_fold(op, ov, sv[t]);
+                sf[t] = of;
+            }
+            __syncthreads();
+        }
+
+        // ---- fires: the window's slices oldest first; older ones from the ring as it stood before
+        // the tile, the tile's own from the scan (the last row of slice j of this key run)
+        const bool fire = live && fires;
+        uint64_t acc = 0;
+        uint32_t loc = 0;
+        if (fire) {
+            bool first = true;
+            for (int k = ns - 1; k >= 0; k--) {
+                const int64_t j = sl - k;
+                int rj = rs - k % R;
+                if (rj < 0) rj += R;
+                uint64_t part;
+                if (j < s0k) {
+                    part = tab[(size_t)slot * pwe + 2 + rj];
+                } else {
+                    part = sv[hi + (int)((j + 1) * d.g - 1 - cnt0)];
+                    if (j == s0k && partial0) part = count_fold(op, tab[(size_t)slot * pwe + 2 + rj], part);
+                }
+                acc = first ? part : count_fold(op, acc, part);
+                first = false;
+            }
+            loc = atomicAdd(&n_fire, 1u);
+        }
+        __syncthreads();
+        if (t == 0) {
+            if (n_fire) {
+                fire_base = atomicAdd((unsigned long long*)&a.ctrl->out_count[0], (unsigned long long)n_fire);
+                atomicAdd((unsigned long long*)&a.ctrl->fired, (unsigned long long)n_fire);
+            }
+            if (n_new) atomicAdd((unsigned long long*)&a.ctrl->live_entries, (unsigned long long)n_new);
+        }
+        __syncthreads();
+        if (fire) {
+            const unsigned long long o = fire_base + loc;
+            if (o < (unsigned long long)a.out_cap) {
+                uint64_t r = acc;
+                if (dbl_cmp) r = dkey_inv((int64_t)acc);
+                else if (a.vtype == FW_T_I32 && !a.is_count && op == CW_ADD_I) r = (uint64_t)(int64_t)(int32_t)(uint32_t)acc;
+                a.out_key[o] = mykey;
+                a.out_val[o] = r;
+                a.out_ws[o] = ws;
+                a.out_we[o] = idx + 1;
+                a.out_ord[o] = a.ord_base + (int64_t)prow[sp[t]];
+            } else {
+                atomicOr(&a.ctrl->error, ERR_OUTPUT);
+            }
+        }
+
+        // ---- write back (every ring read of the fires is behind the barriers above): the last row
+        // of each (key, slice) run stores the slice, unless a later slice of the tile took its slot
+        if (live) {
+            const int len = hlen[hi];
+            const int64_t s_last = (int64_t)udiv((uint64_t)(cnt0 + len - 1), d.g_div);
+            const bool slice_end = rank == len - 1 || idx + 1 == (sl + 1) * d.g;
+            if (slice_end && sl + R > s_last) {
+                uint64_t part = sv[t];
+                if (sl == s0k && partial0) part = count_fold(op, tab[(size_t)slot * pwe + 2 + rs], part);
+                tab[(size_t)slot * pwe + 2 + rs] = part;
+            }
+            if (rank == len - 1) tab[(size_t)slot * pwe + 1] = (uint64_t)(cnt0 + len);
+        }
+        __threadfence_block();
+        __syncthreads();
+    }
+}
+
+int64_t cw_next_pow2(int64_t x) {
+    int64_t p = 1;
+    while (p < x) p <<= 1;
+    return p;
+}
+
+int64_t cw_gcd(int64_t a, int64_t b) {
+    while (b) {
+        const int64_t t = a % b;
+        a = b;
+        b = t;
+    }
+    return a;
+}
+
+template <typename T>
+int cw_dalloc(T** p, size_t count) {
+    void* v = nullptr;
+    CW_TRY(hipMalloc(&v, std::max<size_t>(count, 1) * sizeof(T)));
+    *p = (T*)v;
+    return FW_OK;
+}
+
+}  // namespace
+
+int cw_plan(const fw_config& c, CountOp* op) {
+    if (c.api != FW_API_DATASTREAM) return set_error(FW_E_INVALID, "FW_WIN_COUNT (countWindow) is a DataStream window: api must be FW_API_DATASTREAM");
+    if (c.n_aggs != 1) return set_error(FW_E_INVALID, "count windows take one aggregation (n_aggs == 1), got %d", c.n_aggs);
+    const fw_agg_desc& g = c.aggs[0];
+    if (g.kind == FW_AGG_MINBY || g.kind == FW_AGG_MAXBY)
+        return set_error(FW_E_INVALID, "count windows: minBy / maxBy run on the reference operator");
+    if (g.kind != FW_AGG_SUM && g.kind != FW_AGG_MIN && g.kind != FW_AGG_MAX && g.kind != FW_AGG_COUNT_STAR)
+        return set_error(FW_E_INVALID, "count windows: aggregate kind %d is not sum / min / max / count", g.kind);
+    if (g.type != FW_T_I64 && g.type != FW_T_I32 && g.type != FW_T_F64)
+        return set_error(FW_E_INVALID, "count windows: bad aggregate type %d", g.type);
+    if (g.flags) return set_error(FW_E_INVALID, "count windows: bad aggregate flags %d", g.flags);
+    op->is_count = g.kind == FW_AGG_COUNT_STAR;
+    if (!op->is_count) {
+        if (g.input_col < 0 || g.input_col >= c.n_value_cols) return set_error(FW_E_INVALID, "count windows: bad input_col");
+        if (c.value_col_types[g.input_col] != g.type)
+            return set_error(FW_E_INVALID, "count windows: type does not match value column type");
+    }
+    if (c.size_ms < 1) return set_error(FW_E_INVALID, "count window size must be >= 1");
+    if (c.slide_ms < 0) return set_error(FW_E_INVALID, "count window slide must be >= 1");
+    const int64_t size = c.size_ms, slide = c.slide_ms ? c.slide_ms : c.size_ms;
+    const int64_t gg = cw_gcd(size, slide);
+    if (size / gg > FW_COUNT_MAX_SLICES)
+        return set_error(FW_E_INVALID, "count window size / gcd(size, slide) = %lld exceeds FW_COUNT_MAX_SLICES (%d)",
+                         (long long)(size / gg), FW_COUNT_MAX_SLICES);
+    if (c.offset_ms != 0) return set_error(FW_E_INVALID, "count windows have no offset (offset_ms must be 0)");
+    if (c.allowed_lateness_ms != 0) return set_error(FW_E_INVALID, "count windows have no lateness (allowed_lateness_ms must be 0)");
+    if (c.late_side_output) return set_error(FW_E_INVALID, "count windows have no late elements (late_side_output must be 0)");
+    if (c.ds_first_ordinals) return set_error(FW_E_INVALID, "count windows are (key, aggregate) shaped (ds_first_ordinals must be 0)");
+    if (c.nullable_cols) return set_error(FW_E_INVALID, "count windows take no NULL inputs (nullable_cols must be 0)");
+    if (c.tz_n != 0) return set_error(FW_E_INVALID, "count windows have no time zone (tz_n must be 0)");
+    if (c.agg_phase != FW_PHASE_ONE) return set_error(FW_E_INVALID, "count windows are one-phase (agg_phase must be FW_PHASE_ONE)");
+    if (c.key_hash != FW_KEYHASH_LONG && c.key_hash != FW_KEYHASH_INT && c.key_hash != FW_KEYHASH_PRECOMPUTED)
+        return set_error(FW_E_INVALID, "count windows take LONG, INT or PRECOMPUTED keys (key_hash %d: KEYROW / BINROW keys are not supported)",
+                         c.key_hash);
+    if (c.max_batch_rows <= 0 || c.max_batch_rows >= (1ll << 31)) return set_error(FW_E_INVALID, "max_batch_rows must be in (0, 2^31)");
+    if (c.output_capacity <= 0) return set_error(FW_E_INVALID, "output_capacity must be > 0");
+
+    CountDesc& d = op->d;
+    d.size = size;
+    d.slide = slide;
+    d.g = gg;
+    d.R = (int32_t)(size / gg);
+    d.g_div = make_udiv((uint64_t)gg);
+    d.slide_div = make_udiv((uint64_t)slide);
+    d.r_div = make_udiv((uint64_t)d.R);
+    const bool f = g.type == FW_T_F64;
+    d.op = op->is_count ? CW_ADD_I : g.kind == FW_AGG_SUM ? (f ? CW_ADD_F : CW_ADD_I) : g.kind == FW_AGG_MIN ? CW_MIN : CW_MAX;
+    op->vtype = g.type;
+    op->val_col = op->is_count ? 0 : g.input_col;
+    op->pwe = 2 + d.R;
+
+    KeySpace& ks = op->ks;
+    ks.hash_kind = c.key_hash;
+    ks.max_p = c.max_parallelism;
+    ks.maxp_div = make_udiv32((uint32_t)c.max_parallelism);
+    ks.kg_start = (c.subtask_index * c.max_parallelism + c.parallelism - 1) / c.parallelism;
+    const int kg_end = ((c.subtask_index + 1) * c.max_parallelism - 1) / c.parallelism;
+    ks.n_kg = kg_end - ks.kg_start + 1;
+    ks.pass_log2 = 0;
+    // about 512 hinted keys per superbucket, at most 2048 superbuckets (one fold workgroup each)
+    const int64_t keys = std::max<int64_t>(c.state_capacity, 1024);
+    op->cap_rows = c.max_batch_rows;
+    op->max_nch = (c.max_batch_rows + CW_TILE - 1) / CW_TILE;
+    int64_t sbk = cw_next_pow2(((keys + 511) / 512 + ks.n_kg - 1) / ks.n_kg);
+    while (sbk > 1 && ((int64_t)ks.n_kg * sbk > 2048 || (int64_t)ks.n_kg * sbk * op->max_nch > CW_MAX_HIST)) sbk >>= 1;
+    if ((int64_t)ks.n_kg * sbk * op->max_nch > CW_MAX_HIST)
+        return set_error(FW_E_INVALID, "count windows: key groups per subtask x max_batch_rows too large for the partition table");
+    ks.sb_per_kg_log2 = 0;
+    while ((1ll << ks.sb_per_kg_log2) < sbk) ks.sb_per_kg_log2++;
+    ks.n_sb = ks.n_kg << ks.sb_per_kg_log2;
+    // <= 50% load at the hinted capacity
+    const int64_t ce = cw_next_pow2(std::max<int64_t>(64, 2 * ((keys + ks.n_sb - 1) / ks.n_sb)));
+    if (ce > (1ll << 24)) return set_error(FW_E_INVALID, "count windows: state_capacity too large per superbucket");
+    op->cap_e = (int32_t)ce;
+    op->out_cap = c.output_capacity;
+    op->on = true;
+    return FW_OK;
+}
+
+int cw_allocate(CountOp* op, hipStream_t stream, Ctrl* ctrl) {
+    op->stream = stream;
+    op->ctrl = ctrl;
+    int rc;
+    const size_t tw = (size_t)op->ks.n_sb * op->cap_e * op->pwe;
+    if ((rc = cw_dalloc(&op->table, tw))) return rc;
+    CW_TRY(hipMemsetAsync(op->table, 0, tw * 8, stream));
+    if ((rc = cw_dalloc(&op->hist, (size_t)op->ks.n_sb * op->max_nch))) return rc;
+    if ((rc = cw_dalloc(&op->seg, (size_t)op->ks.n_sb + 1))) return rc;
+    if ((rc = cw_dalloc(&op->s_sb, (size_t)op->cap_rows))) return rc;
+    if ((rc = cw_dalloc(&op->s_row, (size_t)op->cap_rows))) return rc;
+    if ((rc = cw_dalloc(&op->s_rank, (size_t)op->cap_rows))) return rc;
+    if ((rc = cw_dalloc(&op->perm, (size_t)op->cap_rows))) return rc;
+    const size_t oc = (size_t)op->out_cap;
+    if ((rc = cw_dalloc(&op->out_key, oc))) return rc;
+    if ((rc = cw_dalloc(&op->out_ws, oc))) return rc;
+    if ((rc = cw_dalloc(&op->out_we, oc))) return rc;
+    if ((rc = cw_dalloc(&op->out_val, oc))) return rc;
+    if ((rc = cw_dalloc(&op->out_ord, oc))) return rc;
+    if ((rc = cw_dalloc(&op->out_null, oc))) return rc;
+    CW_TRY(hipMemsetAsync(op->out_null, 0, oc * 4, stream));
+    return FW_OK;
+}
+
+void cw_free(CountOp* op) {
+    hipFree(op->table);
+    hipFree(op->hist);
+    hipFree(op->seg);
+    hipFree(op->s_sb);
+    hipFree(op->s_row);
+    hipFree(op->s_rank);
+    hipFree(op->perm);
+    hipFree(op->out_key);
+    hipFree(op->out_ws);
+    hipFree(op->out_we);
+    hipFree(op->out_val);
+    hipFree(op->out_ord);
+    hipFree(op->out_null);
+}
+
+int cw_push(CountOp* op, int64_t n, const int64_t* d_key, const int32_t* d_khash, const uint64_t* d_val) {
+    if (n >= (1ll << 32) || op->push_seq >= (1ll << 30))
+        return set_error(FW_E_INVALID, "arrival ordinals need < 2^32 rows per call and < 2^30 calls");
+    hipStream_t s = op->stream;
+    const int n_sb = op->ks.n_sb;
+    for (int64_t o = 0; o < n; o += op->cap_rows) {
+        const int64_t m = std::min(op->cap_rows, n - o);
+        const int32_t nch = (int32_t)((m + CW_TILE - 1) / CW_TILE);
+        CW_TRY(hipMemsetAsync(op->hist, 0, (size_t)n_sb * nch * 4, s));
+        CwPartArgs pa{};
+        pa.key = d_key + o;
+        pa.khash = d_khash ? d_khash + o : nullptr;
+        pa.n = m;
+        pa.n_chunks = nch;
+        pa.ks = op->ks;
+        pa.ctrl = op->ctrl;
+        pa.hist = op->hist;
+        pa.s_sb = op->s_sb;
+        pa.s_row = op->s_row;
+        pa.s_rank = op->s_rank;
+        hipLaunchKernelGGL(k_cw_part, dim3(nch), dim3(CW_TILE), 0, s, pa);
+        hipLaunchKernelGGL(k_cw_scan, dim3(n_sb), dim3(256), 0, s, op->hist, op->seg, nch);
+        hipLaunchKernelGGL(k_cw_seg, dim3(1), dim3(CW_TILE), 0, s, op->seg, (int32_t)n_sb);
+        hipLaunchKernelGGL(k_cw_scatter, dim3((unsigned)((m + 255) / 256)), dim3(256), 0, s, m, nch, op->hist, op->seg,
+                           op->s_sb, op->s_row, op->s_rank, op->perm);
+        CwFoldArgs fa{};
+        fa.key = d_key + o;
+        fa.val = op->is_count ? nullptr : d_val + o;
+        fa.perm = op->perm;
+        fa.seg = op->seg;
+        fa.d = op->d;
+        fa.cap_e = op->cap_e;
+        fa.pwe = op->pwe;
+        fa.is_count = op->is_count;
+        fa.vtype = op->vtype;
+        fa.table = op->table;
+        fa.ctrl = op->ctrl;
+        fa.out_key = op->out_key;
+        fa.out_ws = op->out_ws;
+        fa.out_we = op->out_we;
+        fa.out_val = op->out_val;
+        fa.out_ord = op->out_ord;
+        fa.out_cap = op->out_cap;
+        fa.ord_base = (op->push_seq << 32) + o;
+        hipLaunchKernelGGL(k_cw_fold, dim3(n_sb), dim3(CW_TILE), 0, s, fa);
+        CW_TRY(hipGetLastError());
+    }
+    op->push_seq++;
+    return FW_OK;
+}
+
+// ---- checkpoint: the library's own blob.  Entries are (key, count, key group << 32 | sub-bucket,
+// ring[R]); precomputed-hash keys carry no hash in the state, so they are placed by the recorded
+// sub-bucket (a restore may not split them finer than the snapshot's), the others are routed again.
+namespace {
+struct CwHeader {
+    uint64_t magic;
+    int64_t push_seq;   // at byte 8 of both blobs (runtime/handle.py _snapshot_push_seq)
+    int64_t watermark;
+    int64_t size, slide;
+    int32_t op, vtype, hash_kind, max_p;
+    int32_t R, key_group, sb_log2, reserved;
+    int64_t n;
+};
+const uint64_t CW_MAGIC = 0x464c4b5743573031ull;     // "FLKWCW01"
+const uint64_t CW_KG_MAGIC = 0x464c4b57434b3031ull;  // "FLKWCK01"
+}  // namespace
+
+int cw_snapshot(CountOp* op, int32_t key_group, void* buf, int64_t capacity, int64_t* size) {
+    const KeySpace& ks = op->ks;
+    const int L = ks.sb_per_kg_log2, pwe = op->pwe;
+    int sb0 = 0, sb1 = ks.n_sb;
+    if (key_group >= 0) {
+        const int li = key_group - ks.kg_start;
+        if (li < 0 || li >= ks.n_kg) return set_error(FW_E_INVALID, "key group %d is not owned by this subtask", key_group);
+        sb0 = li << L;
+        sb1 = (li + 1) << L;
+    }
+    CW_TRY(hipStreamSynchronize(op->stream));
+    const size_t words = (size_t)(sb1 - sb0) * op->cap_e * pwe;
+    std::vector<uint64_t> tab(words);
+    CW_TRY(hipMemcpy(tab.data(), op->table + (size_t)sb0 * op->cap_e * pwe, words * 8, hipMemcpyDeviceToHost));
+    std::vector<uint64_t> ent;
+    int64_t n = 0;
+    for (int sb = sb0; sb < sb1; sb++)
+        for (int e = 0; e < op->cap_e; e++) {
+            const uint64_t* p = tab.data() + ((size_t)(sb - sb0) * op->cap_e + e) * pwe;
+            if (p[1] == 0) continue;
+            ent.push_back(p[0]);
+            ent.push_back(p[1]);
+            ent.push_back((uint64_t)(ks.kg_start + (sb >> L)) << 32 | (uint32_t)(sb & ((1 << L) - 1)));
+            ent.insert(ent.end(), p + 2, p + pwe);
+            n++;
+        }
+    const int64_t need = (int64_t)sizeof(CwHeader) + (int64_t)ent.size() * 8;
+    *size = need;
+    if (!buf) return FW_OK;
+    if (capacity < need) return set_error(FW_E_INVALID, "snapshot buffer too small (%lld < %lld)", (long long)capacity, (long long)need);
+    CwHeader hd{key_group >= 0 ? CW_KG_MAGIC : CW_MAGIC, op->push_seq, op->watermark, op->d.size, op->d.slide, op->d.op, op->vtype,
+                ks.hash_kind, ks.max_p, op->d.R, key_group, L, 0, n};
+    memcpy(buf, &hd, sizeof hd);
+    if (!ent.empty()) memcpy((char*)buf + sizeof hd, ent.data(), ent.size() * 8);
+    return FW_OK;
+}
+
+int cw_restore(CountOp* op, bool key_group, const void* buf, int64_t size) {
+    CwHeader hd;
+    if (size < (int64_t)sizeof hd) return set_error(FW_E_INVALID, "count-window snapshot truncated");
+    memcpy(&hd, buf, sizeof hd);
+    const KeySpace& ks = op->ks;
+    const int L = ks.sb_per_kg_log2, pwe = op->pwe, bw = pwe + 1;
+    if (hd.magic != (key_group ? CW_KG_MAGIC : CW_MAGIC)) return set_error(FW_E_INVALID, "not a count-window %ssnapshot", key_group ? "key-group " : "");
+    if (hd.size != op->d.size || hd.slide != op->d.slide || hd.op != op->d.op || hd.vtype != op->vtype || hd.R != op->d.R ||
+        hd.hash_kind != ks.hash_kind || hd.max_p != ks.max_p)
+        return set_error(FW_E_INVALID, "count-window snapshot of a different operator configuration");
+    if (hd.n < 0 || size < (int64_t)sizeof hd + hd.n * bw * 8) return set_error(FW_E_INVALID, "count-window snapshot truncated");
+    if (ks.hash_kind == KH_PRE && L > hd.sb_log2)
+        return set_error(FW_E_INVALID, "precomputed-hash keys cannot be split finer than the snapshot's sub-buckets");
+    int sb0 = 0, sb1 = ks.n_sb;
+    if (key_group) {
+        const int li = hd.key_group - ks.kg_start;
+        if (li < 0 || li >= ks.n_kg) return set_error(FW_E_INVALID, "key group %d is not owned by this subtask", hd.key_group);
+        sb0 = li << L;
+        sb1 = (li + 1) << L;
+    }
+    CW_TRY(hipStreamSynchronize(op->stream));
+    const size_t words = (size_t)(sb1 - sb0) * op->cap_e * pwe;
+    std::vector<uint64_t> tab(words, 0);
+    if (key_group) CW_TRY(hipMemcpy(tab.data(), op->table + (size_t)sb0 * op->cap_e * pwe, words * 8, hipMemcpyDeviceToHost));
+    std::vector<uint64_t> src((size_t)hd.n * bw);
+    if (hd.n) memcpy(src.data(), (const char*)buf + sizeof hd, src.size() * 8);
+    const uint32_t mask = (uint32_t)op->cap_e - 1u;
+    for (int64_t i = 0; i < hd.n; i++) {
+        const uint64_t* e = src.data() + (size_t)i * bw;
+        const int kg = (int)(e[2] >> 32);
+        int sb;
+        if (ks.hash_kind == KH_PRE) {
+            sb = ((kg - ks.kg_start) << L) + (int)((uint32_t)e[2] & (uint32_t)((1 << L) - 1));
+        } else {
+            uint32_t m;
+            sb = route_key(ks, (int64_t)e[0], 0, &m);
+            if (sb >= 0 && sb < ks.n_sb && ks.kg_start + (sb >> L) != kg)
+                return set_error(FW_E_INVALID, "entry key does not belong to key group %d", kg);
+        }
+        if (sb < sb0 || sb >= sb1) return set_error(FW_E_INVALID, "snapshot entry of key group %d is not owned by this subtask", kg);
+        uint64_t* t = tab.data() + (size_t)(sb - sb0) * op->cap_e * pwe;
+        uint32_t s = count_slot_hash((int64_t)e[0], mask);
+        int p = 0;
+        for (; p < op->cap_e; p++, s = (s + 1) & mask) {
+            uint64_t* q = t + (size_t)s * pwe;
+            if (q[1] == 0) {
+                q[0] = e[0];
+                q[1] = e[1];
+                memcpy(q + 2, e + 3, (size_t)op->d.R * 8);
+                break;
+            }
+            if (q[0] == e[0]) return set_error(FW_E_STATE, "key group %d already holds state for a restored key", kg);
+        }
+        if (p == op->cap_e)
+            return set_error(FW_E_CAPACITY, "restored state exceeds the key table (%d entries per superbucket)", op->cap_e);
+    }
+    CW_TRY(hipMemcpy(op->table + (size_t)sb0 * op->cap_e * pwe, tab.data(), words * 8, hipMemcpyHostToDevice));
+    Ctrl c;
+    CW_TRY(hipMemcpy(&c, op->ctrl, sizeof c, hipMemcpyDeviceToHost));
+    if (key_group) {
+        c.live_entries += hd.n;
+        op->push_seq = std::max(op->push_seq, hd.push_seq);
+    } else {
+        c.live_entries = hd.n;
+        c.error = 0;
+        c.out_count[0] = 0;
+        op->push_seq = hd.push_seq;
+        op->watermark = hd.watermark;
+        c.cur = hd.watermark;
+    }
+    CW_TRY(hipMemcpy(op->ctrl, &c, sizeof c, hipMemcpyHostToDevice));
+    return FW_OK;
+}
+
+}  // namespace fw

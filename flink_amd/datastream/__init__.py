@@ -1,3 +1,7 @@
-"""DataStream event-time window operator (tumbling / sliding + built-in sum/min/max) on MI355X."""
+"""DataStream window operators on MI355X: event-time windows (tumbling / sliding + built-in
+sum/min/max) and count windows (countWindow)."""
 from .windowing import EventTimeTrigger, SlidingEventTimeWindows, TumblingEventTimeWindows  # noqa: F401
+from .windowing import CountEvictor, CountTrigger, GlobalWindows, PurgingTrigger  # noqa: F401
 from .window_operator import WindowOperator, is_gpu_eligible  # noqa: F401
+from .count_window_operator import CountWindowOperator  # noqa: F401
+from .count_window_operator import is_gpu_eligible as is_count_window_gpu_eligible  # noqa: F401

@@ -56,3 +56,54 @@ class EventTimeTrigger:
     @staticmethod
     def create():
         return EventTimeTrigger()
+
+
+# ---- count windows: what KeyedStream.countWindow builds (KeyedStream.java countWindow(size) /
+# countWindow(size, slide)): GlobalWindows with a CountTrigger, purging for the tumbling form, and a
+# CountEvictor for the sliding form
+class GlobalWindows:
+    """GlobalWindows.create(): every element goes to the one GlobalWindow
+    (flink-runtime/.../windowing/assigners/GlobalWindows.java); its maxTimestamp is Long.MAX_VALUE."""
+
+    @staticmethod
+    def create():
+        return GlobalWindows()
+
+    def is_event_time(self):
+        return False
+
+
+class CountTrigger:
+    """CountTrigger.of(maxCount) (triggers/CountTrigger.java): FIRE once the count reaches maxCount."""
+
+    def __init__(self, max_count):
+        self.max_count = int(max_count)
+
+    @staticmethod
+    def of(max_count):
+        return CountTrigger(max_count)
+
+
+class PurgingTrigger:
+    """PurgingTrigger.of(nestedTrigger) (triggers/PurgingTrigger.java): FIRE becomes FIRE_AND_PURGE."""
+
+    def __init__(self, nested):
+        if nested is None:
+            raise ValueError("nested trigger must not be null")
+        self.nested = nested
+
+    @staticmethod
+    def of(nested):
+        return PurgingTrigger(nested)
+
+
+class CountEvictor:
+    """CountEvictor.of(maxCount[, doEvictAfter]) (evictors/CountEvictor.java): keeps up to maxCount
+    elements, evicting from the beginning of the window before (or after) the window function."""
+
+    def __init__(self, max_count, do_evict_after=False):
+        self.max_count, self.do_evict_after = int(max_count), bool(do_evict_after)
+
+    @staticmethod
+    def of(max_count, do_evict_after=False):
+        return CountEvictor(max_count, do_evict_after)

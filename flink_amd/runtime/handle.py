@@ -173,7 +173,8 @@ class WindowAggHandle:
         uint8 tensor}).  The handle's stream waits for the producer's current stream before
         reading them -- unless ``producer_synced``: the caller guarantees the columns are complete
         (synchronised) and stay unmodified until the handle has read them (the C-ABI contract of
-        fw_push_device, as a JNI shim calls it), and no stream events are recorded."""
+        fw_push_device, as a JNI shim calls it), and no stream events are recorded.  A count-window
+        handle ignores the ts column: ``ts`` may be None (d_ts = NULL)."""
         n = keys.numel()
         if n == 0:
             return
@@ -182,7 +183,7 @@ class WindowAggHandle:
             nul = (C.c_void_p * abi.FW_MAX_COLS)()
             for c, v in (nulls or {}).items():
                 nul[c] = v.data_ptr()
-            check(lib().fw_push_device(self._h, n, keys.data_ptr(), ts.data_ptr(),
+            check(lib().fw_push_device(self._h, n, keys.data_ptr(), ts.data_ptr() if ts is not None else None,
                                        key_hashes.data_ptr() if key_hashes is not None else None, arr, nul))
             self.push_seq += 1
             return
@@ -193,7 +194,7 @@ class WindowAggHandle:
         nul = (C.c_void_p * abi.FW_MAX_COLS)()
         for c, v in (nulls or {}).items():
             nul[c] = v.data_ptr()
-        check(lib().fw_push_device(self._h, n, keys.data_ptr(), ts.data_ptr(),
+        check(lib().fw_push_device(self._h, n, keys.data_ptr(), ts.data_ptr() if ts is not None else None,
                                    key_hashes.data_ptr() if key_hashes is not None else None, arr, nul))
         self.push_seq += 1
         self._end_read(cur)
@@ -258,6 +259,8 @@ class WindowAggHandle:
             "null_mask": _np_view(r.null_mask, n, np.uint32).copy(),
         }
         if self.cfg.ds_first_ordinals:  # DataStream: arrival ordinal of each window's first element
+            out["first_ord"] = _np_view(r.first_ord, n, np.int64).copy()
+        elif self.cfg.window_kind == abi.WIN_COUNT:  # count windows: the ordinal of the triggering element
             out["first_ord"] = _np_view(r.first_ord, n, np.int64).copy()
         if self.cfg.key_hash == abi.KEYHASH_KEYROW:  # each row's key row (BinaryRowData image)
             lens = _np_view(r.key_row_len, n, np.int32)
@@ -531,7 +534,9 @@ class WindowAggHandle:
 
 
 def _snapshot_push_seq(blob):
-    """The push counter a snapshot blob carries (SnapHeader / KgHeader .push_seq, the last field)."""
+    """The push counter a snapshot blob carries (SnapHeader / KgHeader .push_seq, the last field; the
+    count-window blobs keep it right behind their magic)."""
     import struct
-    off = {0x464c4b57494e3033: 8 + 16 + 32 + 8, 0x464c4b574b473033: 8 + 24 + 32 + 8}.get(struct.unpack_from("<Q", blob, 0)[0])
+    off = {0x464c4b57494e3033: 8 + 16 + 32 + 8, 0x464c4b574b473033: 8 + 24 + 32 + 8,
+           0x464c4b5743573031: 8, 0x464c4b57434b3031: 8}.get(struct.unpack_from("<Q", blob, 0)[0])
     return struct.unpack_from("<q", blob, off)[0] if off is not None else 0

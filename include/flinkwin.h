@@ -65,9 +65,10 @@
 extern "C" {
 #endif
 
-#define FW_ABI_VERSION 10
+#define FW_ABI_VERSION 11
 #define FW_MAX_AGGS 8
 #define FW_MAX_COLS 8
+#define FW_COUNT_MAX_SLICES 16   /* v11, FW_WIN_COUNT: most count slices (size / gcd(size, slide)) per window */
 
 /* ---- error codes ---------------------------------------------------------------- */
 #define FW_OK 0
@@ -87,7 +88,23 @@ typedef enum {
 typedef enum {
     FW_WIN_TUMBLE = 0,      /* SQL TUMBLE / DataStream TumblingEventTimeWindows         */
     FW_WIN_HOP = 1,         /* SQL HOP / DataStream SlidingEventTimeWindows (size%slide==0) */
-    FW_WIN_CUMULATE = 2     /* SQL CUMULATE                                             */
+    FW_WIN_CUMULATE = 2,    /* SQL CUMULATE                                             */
+    /* v11, DataStream only: KeyedStream.countWindow.  size_ms carries the window size in ELEMENTS
+       (CountEvictor.of(size)), slide_ms the slide in elements (CountTrigger.of(slide)); slide_ms 0 or
+       == size_ms is the tumbling form countWindow(size) (PurgingTrigger(CountTrigger.of(size)), no
+       evictor).  A key fires at every slide-th element with the aggregate of its last min(count, size)
+       elements.  One aggregate (SUM / MIN / MAX / COUNT_STAR over I64 / I32 / F64), keys LONG / INT /
+       PRECOMPUTED, size / gcd(size, slide) <= FW_COUNT_MAX_SLICES; offset, lateness, late side
+       output, ds_first_ordinals, nullable columns, time zones and two-phase plans must be unset.
+       Every push is folded into the state when it is pushed (fw_stats.pending_rows stays 0; the ts
+       column is ignored, d_ts may be NULL); watermarks are recorded and fire nothing (fw_advance,
+       fw_advance_device, fw_flush).  Results come from fw_results / fw_results_reset only: one row
+       per fire with window_start = the per-key 0-based index of the window's first element,
+       max(0, c - size), window_end = c, the key's element count at the fire, and first_ord (below).
+       The async / device / segment result calls, the segment and key-row pushes, fw_late_records,
+       fw_first_element_events, the heap-format and fw_ds_* key-group calls and the profiling calls
+       return FW_E_INVALID on a count handle.  A full key table raises FW_ERRF_STATE. */
+    FW_WIN_COUNT = 3
 } fw_window_kind;
 
 typedef enum {
@@ -232,7 +249,11 @@ typedef struct {
     int64_t* values[FW_MAX_AGGS];      /* per agg: int64, or double bits for DOUBLE results */
     uint32_t* null_mask;               /* bit a set => agg a is SQL NULL                */
     int64_t* first_ord;                /* v5, DataStream with ds_first_ordinals: arrival ordinal of
-                                          the window's first element (value1), else NULL */
+                                          the window's first element (value1), else NULL.
+                                          v11, FW_WIN_COUNT: always filled -- the arrival ordinal of
+                                          the element that TRIGGERED the fire; the device's row order
+                                          is unspecified, sorting by first_ord gives the order in
+                                          which the reference emits the rows */
     /* v5, FW_KEYHASH_KEYROW: row i's key row image is key_row_bytes[i * key_row_stride ..
        + key_row_len[i]) (BinaryRowData.pointTo); key[] holds the handle's internal key ids */
     int32_t* key_row_len;
@@ -683,6 +704,15 @@ int64_t fw_host_next_trigger_watermark(int64_t watermark, int64_t interval);
    slice end x (SliceAssigner.getWindowStart).  *out receives the value; returns FW_E_INVALID for a
    configuration fw_create would reject. */
 int fw_host_time_op(const fw_config* cfg, int32_t what, int64_t x, int64_t* out);
+/* v11: the count-slice arithmetic of a FW_WIN_COUNT configuration, as the kernel runs it.  For a
+   key's element with 0-based per-key index `index`: the count slice (of gcd(size, slide) elements)
+   it falls in, that slice's slot in the key's ring of size / gcd slots, whether the element fires
+   (CountTrigger: the key's count reached a multiple of slide) and, if it does, the index of the
+   window's first element (CountEvictor: max(0, count - size)) and how many ring slots the window
+   reads: the slices [slice - n_slices + 1, slice], oldest first.  A slice's slot is reset when its
+   first element arrives.  Returns FW_E_INVALID for a configuration fw_create would reject. */
+int fw_host_count_step(const fw_config* cfg, int64_t index, int64_t* slice, int32_t* ring_slot, int32_t* fires,
+                       int64_t* window_start, int32_t* n_slices);
 
 #ifdef __cplusplus
 }
