@@ -25,6 +25,7 @@ WIN_TUMBLE = 0
 WIN_HOP = 1
 WIN_CUMULATE = 2
 WIN_COUNT = 3  # DataStream countWindow: size_ms / slide_ms carry element counts
+WIN_SESSION = 4  # DataStream EventTimeSessionWindows.withGap: size_ms carries the gap
 # fw_agg_kind
 AGG_COUNT_STAR = 0
 AGG_COUNT = 1

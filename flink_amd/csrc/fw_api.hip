@@ -21,6 +21,7 @@
 #include <vector>
 
 #include "fw_count.h"
+#include "fw_session.h"
 #include "fw_internal.h"
 
 using namespace fw;
@@ -138,6 +139,7 @@ int fw::set_error(int code, const char* fmt, ...) {
 struct fw_handle {
     fw_config cfg;
     CountOp cw;  // FW_WIN_COUNT: the count-window state (cw.on); the time-window members below stay unused
+    SessionOp sw;  // FW_WIN_SESSION: the session-window state (sw.on), likewise
     hipStream_t stream = nullptr;
     WinDesc win{};
     KeySpace ks{};
@@ -323,6 +325,17 @@ int validate_and_plan(fw_handle* h) {
         h->ks = h->cw.ks;
         h->nv = h->cw.is_count ? 0 : 1;
         h->slot_col[0] = h->cw.val_col;
+        h->n_out = 1;
+        h->out_cap = c.output_capacity;
+        h->stage_cap = c.max_batch_rows;
+        return FW_OK;
+    }
+    if (c.window_kind == FW_WIN_SESSION) {  // session windows: a plan of their own (fw_session.hip)
+        int rc = sw_plan(c, &h->sw);
+        if (rc) return rc;
+        h->ks = h->sw.ks;
+        h->nv = h->sw.d.is_count ? 0 : 1;
+        h->slot_col[0] = h->sw.val_col;
         h->n_out = 1;
         h->out_cap = c.output_capacity;
         h->stage_cap = c.max_batch_rows;
@@ -783,6 +796,12 @@ int allocate(fw_handle* h) {
         HIP_TRY(hipStreamSynchronize(h->stream));
         return FW_OK;
     }
+    if (h->sw.on) {  // likewise a session handle
+        if ((rc = sw_allocate(&h->sw, h->stream, h->ctrl))) return rc;
+        HIP_TRY(launch_init_ctrl(h->ctrl, h->stream));
+        HIP_TRY(hipStreamSynchronize(h->stream));
+        return FW_OK;
+    }
     if ((rc = dalloc(&h->parts, (size_t)FW_MAX_PENDING * h->cap_rows * PW))) return rc;
     if ((rc = dalloc(&h->cells, (size_t)FW_MAX_PENDING * (h->ks.n_sb >> h->ks.pass_log2) * h->cell_cols))) return rc;
     if ((rc = dalloc(&h->slot_nch, FW_MAX_PENDING))) return rc;
@@ -1233,9 +1252,10 @@ int64_t entry_timer_end(const fw_handle* h, int64_t slice, uint64_t flags) {
 // ======================================================================================
 extern "C" {
 
-// entry points a count handle (FW_WIN_COUNT) does not have
-#define CW_REFUSE(h, name) \
-    if ((h)->cw.on) return fail(FW_E_INVALID, name ": not for count windows")
+// entry points a count handle (FW_WIN_COUNT) or a session handle (FW_WIN_SESSION) does not have
+#define CW_REFUSE(h, name)                                                       \
+    if ((h)->cw.on) return fail(FW_E_INVALID, name ": not for count windows");   \
+    if ((h)->sw.on) return fail(FW_E_INVALID, name ": not for session windows")
 
 const char* fw_last_error(void) { return g_err.c_str(); }
 int fw_abi_version(void) { return FW_ABI_VERSION; }
@@ -1274,6 +1294,7 @@ int fw_destroy(fw_handle* h) {
     if (!h) return FW_OK;
     if (h->stream) hipStreamSynchronize(h->stream);
     cw_free(&h->cw);
+    sw_free(&h->sw);
     hipFree(h->ctrl);
     hipFree(h->parts);
     hipFree(h->runs);
@@ -1503,6 +1524,9 @@ static int commit_impl(fw_handle* h, int64_t n, uint32_t packed, const int64_t* 
     }
     const int rc = h->cw.on  ? cw_push(&h->cw, n, h->d_key[b], h->cfg.key_hash == FW_KEYHASH_PRECOMPUTED ? h->d_kh[b] : nullptr,
                                        (const uint64_t*)vals[h->slot_col[0]])
+                   : h->sw.on ? sw_push(&h->sw, h->host_cur, n, h->d_key[b], h->d_ts[b],
+                                        h->cfg.key_hash == FW_KEYHASH_PRECOMPUTED ? h->d_kh[b] : nullptr,
+                                        (const uint64_t*)vals[h->slot_col[0]])
                    : h->keyrow ? push_key_rows(h, n, h->d_kro[b], h->d_krb[b], h->d_ts[b], vals, nuls)
                              : push(h, n, h->d_key[b], h->d_ts[b],
                                     h->cfg.key_hash == FW_KEYHASH_PRECOMPUTED ? h->d_kh[b] : nullptr, vals, nuls);
@@ -1541,6 +1565,11 @@ int fw_push_device(fw_handle* h, int64_t n, const int64_t* d_key, const int64_t*
         return cw_push(&h->cw, n, d_key, d_key_hash, h->nv > 0 ? (const uint64_t*)d_values[h->slot_col[0]] : nullptr);
     }
     if (!d_key || !d_ts) return fail(FW_E_INVALID, "null key/ts column");
+    if (h->sw.on) {  // session windows: folded into the state now, under the current watermark
+        if (h->cfg.key_hash == FW_KEYHASH_PRECOMPUTED && !d_key_hash) return fail(FW_E_INVALID, "key_hash column required");
+        if (h->nv > 0 && (!d_values || !d_values[h->slot_col[0]])) return fail(FW_E_INVALID, "value column %d is NULL", h->slot_col[0]);
+        return sw_push(&h->sw, h->host_cur, n, d_key, d_ts, d_key_hash, h->nv > 0 ? (const uint64_t*)d_values[h->slot_col[0]] : nullptr);
+    }
     if (h->keyrow) return fail(FW_E_INVALID, "a FW_KEYHASH_KEYROW operator takes key rows (fw_push_device_key_rows)");
     if (h->cfg.key_hash == FW_KEYHASH_PRECOMPUTED && !d_key_hash) return fail(FW_E_INVALID, "key_hash column required");
     if (h->nv > 0 && !d_values) return fail(FW_E_INVALID, "value columns required");
@@ -1597,6 +1626,12 @@ int fw_advance(fw_handle* h, int64_t watermark) {
         h->cw.watermark = h->host_cur;
         return FW_OK;
     }
+    if (h->sw.on) {  // EventTimeTrigger: every session with end - 1 <= watermark fires; W' <= W changes nothing
+        if (watermark <= h->host_cur) return FW_OK;
+        h->host_cur = watermark;
+        HIP_TRY(hipMemcpyAsync(&h->ctrl->cur, &h->host_cur, sizeof(int64_t), hipMemcpyHostToDevice, h->stream));
+        return sw_advance(&h->sw, watermark);
+    }
     ar_kick(h);
     // A SQL watermark below the next trigger watermark crosses no slice end: no window fires, no
     // buffer flush is due (AbstractSliceSyncStateWindowAggProcessor.advanceProgress :139-153 only
@@ -1626,6 +1661,7 @@ int fw_advance(fw_handle* h, int64_t watermark) {
 
 int fw_advance_device(fw_handle* h, const int64_t* d_watermark) {
     if (!h || !d_watermark) return fail(FW_E_INVALID, "null argument");
+    if (h->sw.on) return fail(FW_E_INVALID, "fw_advance_device: not for session windows (the late test needs the watermark on the host)");
     if (h->cw.on) {  // recorded on the device (fw_stats.current_watermark), nothing fires
         HIP_TRY(hipMemcpyAsync(&h->ctrl->cur, d_watermark, sizeof(int64_t), hipMemcpyDeviceToDevice, h->stream));
         return FW_OK;
@@ -1647,13 +1683,24 @@ int fw_advance_device(fw_handle* h, const int64_t* d_watermark) {
 
 int fw_flush(fw_handle* h) {
     if (!h) return fail(FW_E_INVALID, "null handle");
-    if (h->cw.on) return FW_OK;  // every push is folded into the state when it is pushed
+    if (h->cw.on || h->sw.on) return FW_OK;  // every push is folded into the state when it is pushed
     return force_flush(h);
 }
 
 // a count handle's rows: one per fire, in the device's order; first_ord orders them as the reference emits
+struct FoldedOut {
+    int64_t *key, *ws, *we;
+    uint64_t* val;
+    int64_t* ord;  // NULL: a session handle's rows carry no ordinal
+    uint32_t* null_mask;
+    int64_t out_cap;
+};
+static FoldedOut folded_out(fw_handle* h) {
+    if (h->cw.on) return {h->cw.out_key, h->cw.out_ws, h->cw.out_we, h->cw.out_val, h->cw.out_ord, h->cw.out_null, h->cw.out_cap};
+    return {h->sw.out_key, h->sw.out_ws, h->sw.out_we, h->sw.out_val, nullptr, h->sw.out_null, h->sw.out_cap};
+}
 static int cw_results(fw_handle* h, fw_result* out, int copy_to_host) {
-    CountOp& w = h->cw;
+    const FoldedOut w = folded_out(h);
     Ctrl c;
     int rc = read_ctrl(h, &c);
     if (rc) return rc;
@@ -1664,12 +1711,12 @@ static int cw_results(fw_handle* h, fw_result* out, int copy_to_host) {
     memset(out, 0, sizeof *out);
     out->n = n;
     if (!copy_to_host) {
-        out->key = w.out_key;
-        out->window_start = w.out_ws;
-        out->window_end = w.out_we;
-        out->values[0] = (int64_t*)w.out_val;
-        out->first_ord = w.out_ord;
-        out->null_mask = w.out_null;
+        out->key = w.key;
+        out->window_start = w.ws;
+        out->window_end = w.we;
+        out->values[0] = (int64_t*)w.val;
+        out->first_ord = w.ord;
+        out->null_mask = w.null_mask;
         return FW_OK;
     }
     h->r_key.resize(n);
@@ -1679,25 +1726,25 @@ static int cw_results(fw_handle* h, fw_result* out, int copy_to_host) {
     h->r_val[1].resize(n);
     h->r_null.assign(n, 0u);
     if (n) {
-        HIP_TRY(hipMemcpyAsync(h->r_key.data(), w.out_key, n * 8, hipMemcpyDeviceToHost, h->stream));
-        HIP_TRY(hipMemcpyAsync(h->r_ws.data(), w.out_ws, n * 8, hipMemcpyDeviceToHost, h->stream));
-        HIP_TRY(hipMemcpyAsync(h->r_we.data(), w.out_we, n * 8, hipMemcpyDeviceToHost, h->stream));
-        HIP_TRY(hipMemcpyAsync(h->r_val[0].data(), w.out_val, n * 8, hipMemcpyDeviceToHost, h->stream));
-        HIP_TRY(hipMemcpyAsync(h->r_val[1].data(), w.out_ord, n * 8, hipMemcpyDeviceToHost, h->stream));
+        HIP_TRY(hipMemcpyAsync(h->r_key.data(), w.key, n * 8, hipMemcpyDeviceToHost, h->stream));
+        HIP_TRY(hipMemcpyAsync(h->r_ws.data(), w.ws, n * 8, hipMemcpyDeviceToHost, h->stream));
+        HIP_TRY(hipMemcpyAsync(h->r_we.data(), w.we, n * 8, hipMemcpyDeviceToHost, h->stream));
+        HIP_TRY(hipMemcpyAsync(h->r_val[0].data(), w.val, n * 8, hipMemcpyDeviceToHost, h->stream));
+        if (w.ord) HIP_TRY(hipMemcpyAsync(h->r_val[1].data(), w.ord, n * 8, hipMemcpyDeviceToHost, h->stream));
         HIP_TRY(hipStreamSynchronize(h->stream));
     }
     out->key = h->r_key.data();
     out->window_start = h->r_ws.data();
     out->window_end = h->r_we.data();
     out->values[0] = (int64_t*)h->r_val[0].data();
-    out->first_ord = (int64_t*)h->r_val[1].data();
+    out->first_ord = w.ord ? (int64_t*)h->r_val[1].data() : nullptr;
     out->null_mask = h->r_null.data();
     return FW_OK;
 }
 
 int fw_results(fw_handle* h, fw_result* out, int copy_to_host) {
     if (!h || !out) return fail(FW_E_INVALID, "null argument");
-    if (h->cw.on) return cw_results(h, out, copy_to_host);
+    if (h->cw.on || h->sw.on) return cw_results(h, out, copy_to_host);
     if (h->reset_pending) {  // consumed and nothing emitted since
         Ctrl c;
         int rc = read_ctrl(h, &c);
@@ -1993,8 +2040,44 @@ int fw_first_element_events(fw_handle* h, fw_ordinal_events* out) {
     return FW_OK;
 }
 
+// a session handle's late side output: the elements dropped as late since the last call
+static int sw_late_records(fw_handle* h, fw_late_rows* out) {
+    memset(out, 0, sizeof *out);
+    SessionOp& w = h->sw;
+    if (!w.side_cap) return fail(FW_E_STATE, "the operator has no late side output (late_side_output = 0)");
+    Ctrl c;
+    int rc = read_ctrl(h, &c);
+    if (rc) return rc;
+    const int64_t n = std::min<int64_t>(c.n_side, w.side_cap);
+    std::vector<int64_t> raw((size_t)n * SW_SIDE_WORDS);
+    if (n) HIP_TRY(hipMemcpy(raw.data(), w.side, raw.size() * 8, hipMemcpyDeviceToHost));
+    const int64_t zero = 0;
+    HIP_TRY(hipMemcpy(&h->ctrl->n_side, &zero, 8, hipMemcpyHostToDevice));
+    h->lr_key.resize(n);
+    h->lr_ts.resize(n);
+    h->lr_seq.resize(n);
+    h->lr_row.resize(n);
+    for (int v = 0; v < h->cfg.n_value_cols; v++) h->lr_val[v].assign(n, 0);
+    for (int64_t i = 0; i < n; i++) {
+        const int64_t* p = raw.data() + (size_t)i * SW_SIDE_WORDS;
+        h->lr_key[i] = p[0];
+        h->lr_ts[i] = p[1];
+        h->lr_seq[i] = (int64_t)((uint64_t)p[2] >> 32);
+        h->lr_row[i] = p[2] & 0xffffffffll;
+        if (h->nv > 0) h->lr_val[h->slot_col[0]][i] = p[3];
+    }
+    out->n = n;
+    out->key = h->lr_key.data();
+    out->ts = h->lr_ts.data();
+    out->push_seq = h->lr_seq.data();
+    out->row = h->lr_row.data();
+    for (int v = 0; v < h->cfg.n_value_cols; v++) out->values[v] = h->lr_val[v].data();
+    return FW_OK;
+}
+
 int fw_late_records(fw_handle* h, fw_late_rows* out) {
     if (!h || !out) return fail(FW_E_INVALID, "null argument");
+    if (h->sw.on) return sw_late_records(h, out);
     CW_REFUSE(h, "fw_late_records");
     memset(out, 0, sizeof *out);
     if (!h->side_cap) return fail(FW_E_STATE, "the operator has no late side output (late_side_output = 0)");
@@ -2030,7 +2113,7 @@ int fw_late_records(fw_handle* h, fw_late_rows* out) {
 
 int fw_results_reset(fw_handle* h) {
     if (!h) return fail(FW_E_INVALID, "null handle");
-    if (h->cw.on) {  // stream-ordered: rows of pushes issued before the call are consumed, later ones kept
+    if (h->cw.on || h->sw.on) {  // stream-ordered: rows of pushes issued before the call are consumed, later ones kept
         HIP_TRY(hipMemsetAsync(&h->ctrl->out_count[0], 0, sizeof(uint64_t), h->stream));
         return FW_OK;
     }
@@ -2054,6 +2137,22 @@ int fw_get_stats(fw_handle* h, fw_stats* out) {
         out->error_flags = (int32_t)cc.error;
         out->num_superbuckets = h->ks.n_sb;
         out->superbucket_capacity = h->cw.cap_e;
+        return FW_OK;
+    }
+    if (h->sw.on) {
+        Ctrl cc;
+        HIP_TRY(hipMemcpyAsync(&cc, h->ctrl, sizeof(Ctrl), hipMemcpyDeviceToHost, h->stream));
+        HIP_TRY(hipStreamSynchronize(h->stream));
+        memset(out, 0, sizeof *out);
+        out->current_watermark = h->host_cur;
+        out->next_trigger_progress = INT64_MAX;
+        out->num_late_records_dropped = (int64_t)cc.late_dropped;
+        out->live_state_entries = cc.live_entries;  // live sessions
+        out->results_available = std::min<int64_t>((int64_t)cc.out_count[0], h->sw.out_cap);
+        out->num_fired_windows = (int64_t)cc.fired;
+        out->error_flags = (int32_t)cc.error;
+        out->num_superbuckets = h->ks.n_sb;
+        out->superbucket_capacity = h->sw.cap_s;
         return FW_OK;
     }
     Ctrl c;
@@ -2290,6 +2389,7 @@ int fw_snapshot(fw_handle* h, void* buf, int64_t capacity, int64_t* size) {
         h->cw.watermark = h->host_cur;
         return cw_snapshot(&h->cw, -1, buf, capacity, size);
     }
+    if (h->sw.on) return sw_snapshot(&h->sw, h->host_cur, -1, buf, capacity, size);
     int rc = force_flush(h);  // prepareSnapshotPreBarrier -> windowBuffer.flush()
     if (rc) return rc;
     Ctrl c;
@@ -2334,6 +2434,7 @@ int fw_restore(fw_handle* h, const void* buf, int64_t size) {
         if (!rc) h->host_cur = h->cw.watermark;
         return rc;
     }
+    if (h->sw.on) return sw_restore(&h->sw, false, buf, size, &h->host_cur);
     SnapHeader hd;
     if (size < (int64_t)sizeof hd) return fail(FW_E_INVALID, "snapshot truncated");
     memcpy(&hd, buf, sizeof hd);
@@ -2438,6 +2539,10 @@ int fw_snapshot_key_group(fw_handle* h, int32_t key_group, void* buf, int64_t ca
         h->cw.watermark = h->host_cur;
         return cw_snapshot(&h->cw, key_group, buf, capacity, size);
     }
+    if (h->sw.on) {
+        if (key_group < 0) return fail(FW_E_INVALID, "key group %d is not owned by this subtask", key_group);
+        return sw_snapshot(&h->sw, h->host_cur, key_group, buf, capacity, size);
+    }
     const KeySpace& ks = h->ks;
     const int li = key_group - ks.kg_start;
     if (li < 0 || li >= ks.n_kg) return fail(FW_E_INVALID, "key group %d is not owned by this subtask", key_group);
@@ -2477,6 +2582,7 @@ int fw_snapshot_key_group(fw_handle* h, int32_t key_group, void* buf, int64_t ca
 int fw_restore_key_group(fw_handle* h, const void* buf, int64_t size) {
     if (!h || !buf) return fail(FW_E_INVALID, "null argument");
     if (h->cw.on) return cw_restore(&h->cw, true, buf, size);
+    if (h->sw.on) return sw_restore(&h->sw, true, buf, size, &h->host_cur);
     KgHeader hd;
     if (size < (int64_t)sizeof hd) return fail(FW_E_INVALID, "key-group snapshot truncated");
     memcpy(&hd, buf, sizeof hd);
@@ -3237,6 +3343,24 @@ int fw_host_count_step(const fw_config* cfg, int64_t index, int64_t* slice, int3
     const int rc = validate_and_plan(&h);
     if (rc) return rc;
     count_step(h.cw.d, index, slice, ring_slot, fires, window_start, n_slices);
+    return FW_OK;
+}
+
+int fw_host_session_add(const fw_config* cfg, int64_t watermark, int64_t ts, int64_t value, int64_t* starts, int64_t* ends,
+                        int64_t* accs, int32_t* n, int32_t capacity, int32_t* outcome) {
+    if (!cfg || !n || !outcome || (capacity > 0 && (!starts || !ends || !accs))) return fail(FW_E_INVALID, "null argument");
+    if (cfg->window_kind != FW_WIN_SESSION) return fail(FW_E_INVALID, "fw_host_session_add needs a FW_WIN_SESSION configuration");
+    fw_handle h;
+    h.cfg = *cfg;
+    const int rc = validate_and_plan(&h);
+    if (rc) return rc;
+    if (*n < 0 || *n > capacity) return fail(FW_E_INVALID, "bad session count %d (capacity %d)", *n, capacity);
+    const SessionDesc& d = h.sw.d;
+    for (int32_t i = 0; i < *n; i++) accs[i] = (int64_t)session_word_of_result(d, (uint64_t)accs[i]);
+    const int r = session_add(d, watermark, ts, session_word(d, (uint64_t)value), starts, ends, (uint64_t*)accs, 1, n, capacity);
+    for (int32_t i = 0; i < *n; i++) accs[i] = (int64_t)session_result(d, (uint64_t)accs[i]);
+    if (r < 0) return fail(FW_E_CAPACITY, "the session list is full (%d sessions)", capacity);
+    *outcome = r;
     return FW_OK;
 }
 

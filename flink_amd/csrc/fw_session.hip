@@ -1,0 +1,1018 @@
+// fw_session.hip -- the session-window path (fw_session.h): kernels and the per-handle host code.
+//
+// One push is folded into the state when it is pushed, in five stream-ordered launches: the stable
+// superbucket partition of the count path (k_sw_part / scan / seg / scatter, copies of k_cw_*), then
+//   k_sw_fold     one workgroup per superbucket walks its rows in arrival order, a tile at a time:
+//                 LDS sort by (key, ts, position), tile sessions by a segmented scan, merge with the
+//                 sorted state into a scratch list, coalesce by a segmented running max of `end`
+// and one launch per watermark:
+//   k_sw_advance  one workgroup per superbucket: emit the due sessions, compact the rest
+// No workgroup waits on another: the only cross-workgroup traffic is counters (atomic adds).
+#include <hip/hip_runtime.h>
+
+#include <algorithm>
+#include <cstring>
+#include <vector>
+
+#include "fw_session.h"
+
+namespace fw {
+namespace {
+
+#define SW_TRY(expr)                                                                                 \
+    do {                                                                                             \
+        hipError_t e_ = (expr);                                                                      \
+        if (e_ != hipSuccess) return set_error(FW_E_DEVICE, "%s: %s", #expr, hipGetErrorString(e_)); \
+    } while (0)
+
+constexpr uint32_t SW_PAD = 0x80000000u;  // position word of a padding element: sorts after every row
+
+__device__ __forceinline__ int sw_pow2(int n) {
+    int p = 2;
+    while (p < n) p <<= 1;
+    return p;
+}
+
+// (padding, key, ts, position) order; positions are unique, so the order is total
+__device__ __forceinline__ bool sw_less(uint64_t ka, int64_t ta, uint32_t pa, uint64_t kb, int64_t tb, uint32_t pb) {
+    const uint32_t ia = pa >> 31, ib = pb >> 31;
+    if (ia != ib) return ia < ib;
+    if (ka != kb) return ka < kb;
+    if (ta != tb) return ta < tb;
+    return pa < pb;
+}
+
+// bitonic sort of the first n2 (a power of two <= SW_TILE) triples; every thread of the workgroup
+// calls it, after a barrier behind the stores that filled the arrays; it ends with a barrier
+__device__ void sw_sort(uint64_t* k, int64_t* ts, uint32_t* p, int n2) {
+    const int t = threadIdx.x;
+    for (int kk = 2; kk <= n2; kk <<= 1)
+        for (int j = kk >> 1; j > 0; j >>= 1) {
+            const int x = t ^ j;
+            if (t < n2 && x > t) {
+                const bool asc = (t & kk) == 0;
+                const uint64_t ka = k[t], kb = k[x];
+                const int64_t ta = ts[t], tb = ts[x];
+                const uint32_t pa = p[t], pb = p[x];
+                if (sw_less(kb, tb, pb, ka, ta, pa) == asc) {
+                    k[t] = kb;
+                    k[x] = ka;
+                    ts[t] = tb;
+                    ts[x] = ta;
+                    p[t] = pb;
+                    p[x] = pa;
+                }
+            }
+            __syncthreads();
+        }
+}
+
+// bitonic sort of n2 distinct 32-bit words
+__device__ void sw_sort32(uint32_t* a, int n2) {
+    const int t = threadIdx.x;
+    for (int kk = 2; kk <= n2; kk <<= 1)
+        for (int j = kk >> 1; j > 0; j >>= 1) {
+            const int x = t ^ j;
+            if (t < n2 && x > t) {
+                const bool asc = (t & kk) == 0;
+                const uint32_t va = a[t], vb = a[x];
+                if ((vb < va) == asc) {
+                    a[t] = vb;
+                    a[x] = va;
+                }
+            }
+            __syncthreads();
+        }
+}
+
+// inclusive max scan of a[0 .. n2); every thread calls it after a barrier; ends with a barrier
+__device__ void sw_max_scan(int32_t* a, int n2) {
+    const int t = threadIdx.x;
+    for (int d = 1; d < n2; d <<= 1) {
+        const bool on = t < n2 && t >= d;
+        const int32_t v = on ? a[t - d] : 0;
+        __syncthreads();
+        if (on && v > a[t]) a[t] = v;
+        __syncthreads();
+    }
+}
+
+// ---- the stable superbucket partition: k_cw_part / k_cw_scan / k_cw_seg / k_cw_scatter of
+// fw_count.hip, copied unchanged in behaviour (they are local to that translation unit)
+struct SwPartArgs {
+    const int64_t* key;
+    const int32_t* khash;
+    int64_t n;
+    int32_t n_chunks;
+    KeySpace ks;
+    Ctrl* ctrl;
+    int32_t* hist;
+    int32_t* s_sb;
+    uint32_t* s_row;
+    int32_t* s_rank;
+};
+
+__global__ __launch_bounds__(SW_TILE) void k_sw_part(SwPartArgs a) {
+    __shared__ uint64_t sk[SW_TILE];
+    __shared__ int64_t sz[SW_TILE];
+    __shared__ uint32_t sp[SW_TILE];
+    __shared__ int32_t hx[SW_TILE];
+    const int t = threadIdx.x;
+    const int64_t c0 = (int64_t)blockIdx.x * SW_TILE;
+    const int nrows = (int)(a.n - c0 < SW_TILE ? a.n - c0 : SW_TILE);
+    const int n2 = sw_pow2(nrows);
+    int32_t sb = -1;
+    if (t < nrows) {
+        uint32_t m;
+        sb = route_key(a.ks, a.key[c0 + t], a.khash ? a.khash[c0 + t] : 0, &m);
+        if (sb < 0 || sb >= a.ks.n_sb) {  // key group outside the subtask's range: the row is dropped
+            atomicOr(&a.ctrl->error, ERR_KEYGROUP);
+            sb = -1;
+        }
+    }
+    sk[t] = sb >= 0 ? (uint64_t)sb : ~0ull;
+    sz[t] = 0;
+    sp[t] = sb >= 0 ? (uint32_t)t : (SW_PAD | (uint32_t)t);
+    __syncthreads();
+    sw_sort(sk, sz, sp, n2);
+    const bool v = t < n2 && !(sp[t] >> 31);
+    const bool head = v && (t == 0 || sk[t - 1] != sk[t]);
+    hx[t] = head ? t : 0;
+    __syncthreads();
+    sw_max_scan(hx, n2);
+    if (v) {
+        const int32_t rank = t - hx[t];
+        const int32_t s = (int32_t)sk[t];
+        a.s_sb[c0 + t] = s;
+        a.s_row[c0 + t] = (uint32_t)(c0 + sp[t]);
+        a.s_rank[c0 + t] = rank;
+        const bool tail = t == n2 - 1 || (sp[t + 1] >> 31) || sk[t + 1] != sk[t];
+        if (tail) a.hist[(size_t)s * a.n_chunks + blockIdx.x] = rank + 1;
+    } else if (t < nrows) {
+        a.s_sb[c0 + t] = -1;
+    }
+}
+
+// inclusive scan over the workgroup's NT threads; every thread calls it; *total = the sum
+template <int NT>
+__device__ int32_t sw_block_scan(int32_t x, int32_t* buf, int32_t* total) {
+    const int t = threadIdx.x;
+    buf[t] = x;
+    __syncthreads();
+    for (int d = 1; d < NT; d <<= 1) {
+        const int32_t v = t >= d ? buf[t - d] : 0;
+        __syncthreads();
+        buf[t] += v;
+        __syncthreads();
+    }
+    const int32_t r = buf[t];
+    *total = buf[NT - 1];
+    __syncthreads();
+    return r;
+}
+
+__global__ __launch_bounds__(256) void k_sw_scan(int32_t* hist, int32_t* seg, int32_t n_chunks) {
+    __shared__ int32_t buf[256];
+    int32_t* row = hist + (size_t)blockIdx.x * n_chunks;
+    int32_t carry = 0;
+    for (int base = 0; base < n_chunks; base += 256) {
+        const int i = base + threadIdx.x;
+        const int32_t x = i < n_chunks ? row[i] : 0;
+        int32_t tot;
+        const int32_t inc = sw_block_scan<256>(x, buf, &tot);
+        if (i < n_chunks) row[i] = carry + inc - x;
+        carry += tot;
+    }
+    if (threadIdx.x == 0) seg[blockIdx.x] = carry;
+}
+
+__global__ __launch_bounds__(SW_TILE) void k_sw_seg(int32_t* seg, int32_t n_sb) {
+    __shared__ int32_t buf[SW_TILE];
+    int32_t carry = 0;
+    for (int base = 0; base < n_sb; base += SW_TILE) {
+        const int i = base + threadIdx.x;
+        const int32_t x = i < n_sb ? seg[i] : 0;
+        int32_t tot;
+        const int32_t inc = sw_block_scan<SW_TILE>(x, buf, &tot);
+        if (i < n_sb) seg[i] = carry + inc - x;
+        carry += tot;
+    }
+    if (threadIdx.x == 0) seg[n_sb] = carry;
+}
+
+__global__ __launch_bounds__(256) void k_sw_scatter(int64_t n, int32_t n_chunks, const int32_t* hist, const int32_t* seg,
+                                                     const int32_t* s_sb, const uint32_t* s_row, const int32_t* s_rank,
+                                                     uint32_t* perm) {
+    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (i >= n) return;
+    const int32_t sb = s_sb[i];
+    if (sb < 0) return;
+    const int64_t dst = (int64_t)seg[sb] + hist[(size_t)sb * n_chunks + (i / SW_TILE)] + s_rank[i];
+    if (dst < n) perm[dst] = s_row[i];  // (always: the groups' sizes sum to the kept rows)
+}
+
+// ---- the fold ------------------------------------------------------------------------------------
+struct SwFoldArgs {
+    const int64_t* key;
+    const int64_t* ts;
+    const uint64_t* val;
+    const uint32_t* perm;
+    const int32_t* seg;
+    SessionDesc d;
+    int64_t watermark;
+    int32_t cap_s;
+    int32_t late_side;
+    uint64_t* state;
+    uint64_t* scratch;
+    int32_t* n_s;
+    int64_t* min_end;
+    Ctrl* ctrl;
+    int64_t* side;
+    int64_t side_cap;
+    int64_t ord_base;  // push_seq << 32 | row offset of this launch within its call
+};
+
+// first index in [lo, hi) of the sorted session list whose (key, start) is not below (k, s)
+__device__ __forceinline__ int sw_lower(const uint64_t* st, int lo, int hi, uint64_t k, int64_t s) {
+    while (lo < hi) {  // <= 32 steps
+        const int mid = (lo + hi) >> 1;
+        const uint64_t mk = st[(size_t)mid * SW_WORDS];
+        const int64_t ms = (int64_t)st[(size_t)mid * SW_WORDS + 1];
+        if (mk < k || (mk == k && ms < s)) lo = mid + 1;
+        else hi = mid;
+    }
+    return lo;
+}
+
+__global__ __launch_bounds__(SW_TILE) void k_sw_fold(SwFoldArgs a) {
+    __shared__ uint64_t sk[SW_TILE];     // sorted keys; then the coalesce chunk's keys
+    __shared__ int64_t sts[SW_TILE];     // their timestamps; then the chunk's ends
+    __shared__ uint64_t sa[SW_TILE];     // scan: accumulators
+    __shared__ int64_t se[SW_TILE];      // scan: ends
+    __shared__ uint32_t sp[SW_TILE];     // positions in the tile (arrival order)
+    __shared__ uint32_t sf[SW_TILE];     // scan: segment flags
+    __shared__ int32_t hx[SW_TILE];      // sorted index of the row's key run head
+    __shared__ uint32_t ord[SW_TILE];    // key runs with a late candidate re-sorted by position: sorted index
+    __shared__ int32_t hlo[SW_TILE];     // by head: the key's sessions are state[hlo, hhi)
+    __shared__ int32_t hhi[SW_TILE];
+    __shared__ int32_t hlen[SW_TILE];    // by head: run length | late-candidate flag << 30
+    __shared__ int64_t c_max, c_end;     // coalesce carries: running max end of the last key, open group's end
+    __shared__ uint64_t c_key, c_acc;
+    __shared__ int32_t c_groups, c_valid;
+    __shared__ uint32_t n_drop;
+
+    const int t = threadIdx.x;
+    const SessionDesc d = a.d;
+    const int64_t gap = d.gap, W = a.watermark;
+    const int op = d.op;
+    const int64_t seg0 = a.seg[blockIdx.x], seg1 = a.seg[blockIdx.x + 1];
+    if (seg0 >= seg1) return;
+    uint64_t* st = a.state + (size_t)blockIdx.x * a.cap_s * SW_WORDS;
+    uint64_t* M = a.scratch + (size_t)blockIdx.x * ((size_t)a.cap_s + SW_TILE) * SW_WORDS;
+    int ns = a.n_s[blockIdx.x];
+    const int ns_at_entry = ns;
+    int64_t tile_min_end = INT64_MAX;
+
+    for (int64_t base = seg0; base < seg1; base += SW_TILE) {
+        const int nt = (int)(seg1 - base < SW_TILE ? seg1 - base : SW_TILE);
+        const int n2 = sw_pow2(nt);
+        if (t == 0) n_drop = 0;
+        if (t < nt) {
+            const uint32_t row = a.perm[base + t];
+            sk[t] = (uint64_t)a.key[row];
+            sts[t] = a.ts[row];
+            sp[t] = (uint32_t)t;
+        } else {
+            sk[t] = ~0ull;
+            sts[t] = 0;
+            sp[t] = SW_PAD | (uint32_t)t;
+        }
+        hlen[t] = 0;
+        __syncthreads();
+        sw_sort(sk, sts, sp, n2);
+        const bool valid = t < nt;  // the padding sorted behind the rows
+        const uint64_t mykey = sk[t];
+        const int64_t myts = sts[t];
+        const bool head = valid && (t == 0 || sk[t - 1] != mykey);
+        hx[t] = head ? t : 0;
+        __syncthreads();
+        sw_max_scan(hx, n2);
+        const int hi_ = valid ? hx[t] : 0;
+        const int rank = t - hi_;
+        // a key run that holds a late candidate is folded in arrival order (rule: an element that is
+        // late when it arrives stays only if a session intersects it then)
+        if (valid && session_late(myts, gap, W)) atomicOr((uint32_t*)&hlen[hi_], 1u << 30);
+        const bool runtail = valid && (t == nt - 1 || sk[t + 1] != mykey);
+        if (runtail) atomicOr((uint32_t*)&hlen[hi_], (uint32_t)(rank + 1));
+        if (head) {
+            hlo[t] = sw_lower(st, 0, ns, mykey, INT64_MIN);
+            hhi[t] = mykey == ~0ull ? ns : sw_lower(st, 0, ns, mykey + 1, INT64_MIN);
+        }
+        __syncthreads();
+        const bool slow = valid && (hlen[hi_] >> 30) != 0;
+        const int len = valid ? (hlen[hi_] & 0xFFFF) : 0;
+        const int lo = valid ? hlo[hi_] : 0, hi = valid ? hhi[hi_] : 0;
+        // tile sessions of the other runs: a new one where the gap to the previous row is exceeded
+        const bool shead = valid && !slow && (rank == 0 || myts - sts[t - 1] > gap);
+        const bool stail = valid && !slow && (runtail || sts[t + 1] - myts > gap);
+        tile_min_end = valid && myts + gap < tile_min_end ? myts + gap : tile_min_end;
+        // the sessions the tile can add at most; if they might not fit, the coalesce pass below runs
+        // once more in front, only counting (uniform)
+        const int may_add = __syncthreads_count(shead || slow);
+        const bool tight = ns + may_add > a.cap_s;
+        // the run's rows in arrival order, for the late-candidate runs
+        ord[t] = valid ? ((uint32_t)hi_ << 20 | (slow ? sp[t] : (uint32_t)rank) << 10 | (uint32_t)rank) : (0x7FF00000u | (uint32_t)t);
+        // reverse segmented scan: a tile session's first row gets the reduce of its rows and its end
+        uint64_t myword = session_identity(op);
+        if (valid) myword = session_word(d, d.is_count ? 1ull : a.val[a.perm[base + sp[t]]]);
+        if (t < n2) {
+            sa[t] = myword;
+            se[t] = myts + gap;
+            sf[t] = (!valid || slow || stail) ? 1u : 0u;
+        }
+        __syncthreads();
+        for (int dd = 1; dd < n2; dd <<= 1) {
+            const bool take = t + dd < n2 && !sf[t];
+            uint64_t ov = 0;
+            int64_t oe = 0;
+            uint32_t of = 0;
+            if (take) {
+                ov = sa[t + dd];
+                oe = se[t + dd];
+                of = sf[t + dd];
+            }
+            __syncthreads();
+            if (take) {
+                sa[t] = session_fold(op, sa[t], ov);
+                if (oe > se[t]) se[t] = oe;
+                sf[t] = of;
+            }
+            __syncthreads();
+        }
+        sw_sort32(ord, n2);
+
+        // ---- the merged list M: every state session and every tile row by merge path.  A row that
+        // starts no tile session is a dead slot.  A late-candidate key's sessions and rows share the
+        // region M[lo + head, hi + head + len), which the run's head lane fills below.
+        for (int i = t; i < ns; i += SW_TILE) {
+            const uint64_t k = st[(size_t)i * SW_WORDS];
+            const int64_t s = (int64_t)st[(size_t)i * SW_WORDS + 1];
+            int l = 0, h = nt;  // rows with key < k
+            while (l < h) {
+                const int mid = (l + h) >> 1;
+                if (sk[mid] < k) l = mid + 1;
+                else h = mid;
+            }
+            int before = l;
+            if (l < nt && sk[l] == k && !(hlen[l] >> 30)) {  // rows of the key with ts < s
+                h = l + (hlen[l] & 0xFFFF);
+                while (l < h) {
+                    const int mid = (l + h) >> 1;
+                    if (sts[mid] < s) l = mid + 1;
+                    else h = mid;
+                }
+                before = l;
+            }
+            uint64_t* dst = M + (size_t)(i + before) * SW_WORDS;
+            dst[0] = k;
+            dst[1] = (uint64_t)s;
+            dst[2] = st[(size_t)i * SW_WORDS + 2];
+            dst[3] = st[(size_t)i * SW_WORDS + 3];
+        }
+        if (valid && !slow) {
+            // state sessions of the key with start <= ts sort before the row
+            const int c = sw_lower(st, lo, hi, mykey, myts + 1);
+            uint64_t* dst = M + (size_t)(t + c) * SW_WORDS;
+            dst[0] = mykey;
+            dst[1] = (uint64_t)myts;
+            dst[2] = shead ? (uint64_t)se[t] : (uint64_t)SW_DEAD;
+            dst[3] = shead ? sa[t] : session_identity(op);
+        }
+        __threadfence_block();
+        __syncthreads();
+        if (head && slow) {
+            uint64_t* reg = M + (size_t)(lo + t) * SW_WORDS;
+            int32_t n = hi - lo;
+            const int32_t room = n + len;
+            for (int r = 0; r < len; r++) {  // arrival order
+                const int u = hi_ + (int)(ord[t + r] & 0x3FFu);
+                const int64_t ts = sts[u];
+                const uint32_t row = a.perm[base + sp[u]];
+                const uint64_t raw = d.is_count ? 1ull : a.val[row];
+                const int rc = session_add(d, W, ts, session_word(d, raw), (int64_t*)reg + 1, (int64_t*)reg + 2, reg + 3, SW_WORDS,
+                                           &n, room);
+                if (rc == 0) {
+                    atomicAdd(&n_drop, 1u);
+                    if (a.late_side) {
+                        const unsigned long long o = atomicAdd((unsigned long long*)&a.ctrl->n_side, 1ull);
+                        if (o < (unsigned long long)a.side_cap) {
+                            int64_t* sd = a.side + (size_t)o * SW_SIDE_WORDS;
+                            sd[0] = (int64_t)mykey;
+                            sd[1] = ts;
+                            sd[2] = a.ord_base + (int64_t)row;
+                            sd[3] = (int64_t)raw;
+                        } else {
+                            atomicOr(&a.ctrl->error, ERR_LATE);
+                        }
+                    }
+                }
+            }
+            for (int32_t q = 0; q < room; q++) {
+                reg[(size_t)q * SW_WORDS] = mykey;
+                if (q >= n) {
+                    reg[(size_t)q * SW_WORDS + 1] = (uint64_t)INT64_MAX;
+                    reg[(size_t)q * SW_WORDS + 2] = (uint64_t)SW_DEAD;
+                    reg[(size_t)q * SW_WORDS + 3] = session_identity(op);
+                }
+            }
+        }
+        __threadfence_block();
+        __syncthreads();
+        if (t == 0 && n_drop) atomicAdd((unsigned long long*)&a.ctrl->late_dropped, (unsigned long long)n_drop);
+
+        // ---- coalesce M[0, L) into the state: a new session starts where the key changes or
+        // start > the key's running max end
+        const int L = ns + nt;
+        bool fits = true;
+        for (int pass = tight ? 0 : 1; pass < 2 && fits; pass++) {
+            if (t == 0) {
+                c_valid = 0;
+                c_groups = 0;
+                c_max = INT64_MIN;
+                c_end = INT64_MIN;
+                c_key = 0;
+                c_acc = session_identity(op);
+            }
+            __syncthreads();
+            for (int c0 = 0; c0 < L; c0 += SW_TILE) {
+                const int j = c0 + t;
+                const bool in = j < L;
+                uint64_t k = ~0ull, acc = session_identity(op);
+                int64_t s = INT64_MAX, e = SW_DEAD;
+                if (in) {
+                    const uint64_t* src = M + (size_t)j * SW_WORDS;
+                    k = src[0];
+                    s = (int64_t)src[1];
+                    e = (int64_t)src[2];
+                    acc = src[3];
+                }
+                const bool live = e != SW_DEAD;
+                const uint64_t pk = c_key;
+                const int64_t pmax = c_max, pend = c_end;
+                const uint64_t pacc = c_acc;
+                const int32_t pgroups = c_groups, pvalid = c_valid;
+                sk[t] = k;
+                sts[t] = e;
+                sf[t] = 0;
+                __syncthreads();
+                // inclusive running max of end inside the key
+                for (int dd = 1; dd < SW_TILE; dd <<= 1) {
+                    const bool take = t >= dd && sk[t - dd] == k;
+                    const int64_t ov = take ? sts[t - dd] : INT64_MIN;
+                    __syncthreads();
+                    if (take && ov > sts[t]) sts[t] = ov;
+                    __syncthreads();
+                }
+                const bool from_carry = pvalid && pk == sk[0];
+                int64_t mx = INT64_MIN;  // exclusive
+                if (t > 0 && sk[t - 1] == k) mx = sts[t - 1];
+                if (from_carry && k == pk && pmax > mx) mx = pmax;
+                const int64_t incl_last = sts[SW_TILE - 1];
+                const uint64_t last_key = sk[SW_TILE - 1];
+                const bool is_head = live && s > mx;
+                __syncthreads();
+                // group index and the reduce of each group
+                int32_t total_heads;
+                const int32_t hcount = sw_block_scan<SW_TILE>(is_head ? 1 : 0, hx, &total_heads);
+                sa[t] = acc;
+                se[t] = e;
+                sf[t] = is_head ? 1u : 0u;
+                __syncthreads();
+                for (int dd = 1; dd < SW_TILE; dd <<= 1) {
+                    const bool take = t >= dd && !sf[t];
+                    uint64_t ov = 0;
+                    int64_t oe = 0;
+                    uint32_t of = 0;
+                    if (take) {
+                        ov = sa[t - dd];
+                        oe = se[t - dd];
+                        of = sf[t - dd];
+                    }
+                    __syncthreads();
+                    if (take) {
+                        sa[t] = session_fold(op, ov, sa[t]);
+                        if (oe > se[t]) se[t] = oe;
+                        sf[t] = of;
+                    }
+                    __syncthreads();
+                }
+                uint64_t gacc = sa[t];
+                int64_t gend = se[t];
+                if (hcount == 0) {  // still the group the previous chunk left open
+                    gacc = session_fold(op, pacc, gacc);
+                    if (pend > gend) gend = pend;
+                }
+                const int32_t g = pgroups + hcount - 1;
+                const bool glast = t == SW_TILE - 1 || j + 1 >= L || hx[t + 1] != hcount;
+                if (pass == 1 && in && g >= 0 && g < a.cap_s) {
+                    uint64_t* dst = st + (size_t)g * SW_WORDS;
+                    if (is_head) {
+                        dst[0] = k;
+                        dst[1] = (uint64_t)s;
+                    }
+                    if (glast) {
+                        dst[2] = (uint64_t)gend;
+                        dst[3] = gacc;
+                    }
+                }
+                __syncthreads();
+                if (t == SW_TILE - 1) {
+                    c_valid = 1;
+                    c_key = last_key;
+                    c_max = (from_carry && last_key == pk && pmax > incl_last) ? pmax : incl_last;
+                    c_groups = pgroups + total_heads;
+                    c_acc = gacc;
+                    c_end = gend;
+                }
+                __threadfence_block();
+                __syncthreads();
+            }
+            if (pass == 0 && c_groups > a.cap_s) fits = false;
+            __syncthreads();
+        }
+        if (!fits) {  // the fold's result does not fit: the tile's rows are dropped, the state stays
+            if (t == 0) atomicOr(&a.ctrl->error, ERR_STATE);
+            continue;
+        }
+        ns = c_groups < a.cap_s ? c_groups : a.cap_s;
+        __syncthreads();
+    }
+    if (t == 0) {
+        a.n_s[blockIdx.x] = ns;
+        if (ns != ns_at_entry)
+            atomicAdd((unsigned long long*)&a.ctrl->live_entries, (unsigned long long)(long long)(ns - ns_at_entry));
+    }
+    // every session's end is at least the smaller of the old bound and the tile rows' ts + gap
+    sts[t] = tile_min_end;
+    __syncthreads();
+    for (int dd = SW_TILE >> 1; dd > 0; dd >>= 1) {
+        if (t < dd && sts[t + dd] < sts[t]) sts[t] = sts[t + dd];
+        __syncthreads();
+    }
+    if (t == 0 && sts[0] < a.min_end[blockIdx.x]) a.min_end[blockIdx.x] = sts[0];
+}
+
+// ---- the watermark -----------------------------------------------------------------------------
+struct SwAdvArgs {
+    SessionDesc d;
+    int64_t watermark;
+    int32_t cap_s;
+    uint64_t* state;
+    int32_t* n_s;
+    int64_t* min_end;
+    Ctrl* ctrl;
+    int64_t* out_key;
+    int64_t* out_ws;
+    int64_t* out_we;
+    uint64_t* out_val;
+    int64_t out_cap;
+};
+
+__global__ __launch_bounds__(SW_TILE) void k_sw_advance(SwAdvArgs a) {
+    __shared__ int32_t buf[SW_TILE];
+    __shared__ int64_t mn[SW_TILE];
+    __shared__ unsigned long long out_base;
+    const int t = threadIdx.x;
+    const int ns = a.n_s[blockIdx.x];
+    if (ns == 0 || !session_due(a.min_end[blockIdx.x], a.watermark)) return;  // nothing is due (uniform)
+    uint64_t* st = a.state + (size_t)blockIdx.x * a.cap_s * SW_WORDS;
+    // the due sessions, counted first: one device atomic per workgroup claims their output rows
+    int32_t mine = 0;
+    for (int i = t; i < ns; i += SW_TILE) mine += session_due((int64_t)st[(size_t)i * SW_WORDS + 2], a.watermark) ? 1 : 0;
+    int32_t n_due;
+    sw_block_scan<SW_TILE>(mine, buf, &n_due);
+    if (t == 0) {
+        out_base = 0;
+        if (n_due) {
+            out_base = atomicAdd((unsigned long long*)&a.ctrl->out_count[0], (unsigned long long)n_due);
+            atomicAdd((unsigned long long*)&a.ctrl->fired, (unsigned long long)n_due);
+            atomicAdd((unsigned long long*)&a.ctrl->live_entries, (unsigned long long)(long long)(-n_due));
+            if (out_base + (unsigned long long)n_due > (unsigned long long)a.out_cap) atomicOr(&a.ctrl->error, ERR_OUTPUT);
+        }
+    }
+    __syncthreads();
+    int32_t fired = 0, kept = 0;
+    int64_t min_end = INT64_MAX;
+    for (int c0 = 0; c0 < ns; c0 += SW_TILE) {
+        const int i = c0 + t;
+        const bool in = i < ns;
+        uint64_t k = 0, acc = 0;
+        int64_t s = 0, e = 0;
+        if (in) {
+            k = st[(size_t)i * SW_WORDS];
+            s = (int64_t)st[(size_t)i * SW_WORDS + 1];
+            e = (int64_t)st[(size_t)i * SW_WORDS + 2];
+            acc = st[(size_t)i * SW_WORDS + 3];
+        }
+        const bool due = in && session_due(e, a.watermark);
+        int32_t n_f;
+        const int32_t fi = sw_block_scan<SW_TILE>(due ? 1 : 0, buf, &n_f);  // (barriers: the chunk is in registers)
+        const int32_t n_in = ns - c0 < SW_TILE ? ns - c0 : SW_TILE;
+        if (due) {
+            const unsigned long long o = out_base + (unsigned long long)(fired + fi - 1);
+            if (o < (unsigned long long)a.out_cap) {
+                a.out_key[o] = (int64_t)k;
+                a.out_ws[o] = s;
+                a.out_we[o] = e;
+                a.out_val[o] = session_result(a.d, acc);
+            }
+        } else if (in) {  // stable compaction: the slot is at or before the session's own
+            uint64_t* dst = st + (size_t)(kept + (t + 1 - fi) - 1) * SW_WORDS;
+            dst[0] = k;
+            dst[1] = (uint64_t)s;
+            dst[2] = (uint64_t)e;
+            dst[3] = acc;
+            if (e < min_end) min_end = e;
+        }
+        fired += n_f;
+        kept += n_in - n_f;
+        __threadfence_block();
+        __syncthreads();
+    }
+    mn[t] = min_end;
+    __syncthreads();
+    for (int dd = SW_TILE >> 1; dd > 0; dd >>= 1) {
+        if (t < dd && mn[t + dd] < mn[t]) mn[t] = mn[t + dd];
+        __syncthreads();
+    }
+    if (t == 0) {
+        a.n_s[blockIdx.x] = kept;
+        a.min_end[blockIdx.x] = mn[0];
+    }
+}
+
+__global__ void k_sw_fill(int64_t* p, int64_t v, int n) {
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < n) p[i] = v;
+}
+
+int64_t sw_next_pow2(int64_t x) {
+    int64_t p = 1;
+    while (p < x) p <<= 1;
+    return p;
+}
+
+template <typename T>
+int sw_dalloc(T** p, size_t count) {
+    void* v = nullptr;
+    SW_TRY(hipMalloc(&v, std::max<size_t>(count, 1) * sizeof(T)));
+    *p = (T*)v;
+    return FW_OK;
+}
+
+}  // namespace
+
+int sw_plan(const fw_config& c, SessionOp* op) {
+    if (c.api != FW_API_DATASTREAM)
+        return set_error(FW_E_INVALID, "FW_WIN_SESSION (EventTimeSessionWindows) is a DataStream window: api must be FW_API_DATASTREAM");
+    if (c.n_aggs != 1) return set_error(FW_E_INVALID, "session windows take one aggregation (n_aggs == 1), got %d", c.n_aggs);
+    const fw_agg_desc& g = c.aggs[0];
+    if (g.kind == FW_AGG_MINBY || g.kind == FW_AGG_MAXBY)
+        return set_error(FW_E_INVALID, "session windows: minBy / maxBy run on the reference operator");
+    if (g.kind != FW_AGG_SUM && g.kind != FW_AGG_MIN && g.kind != FW_AGG_MAX && g.kind != FW_AGG_COUNT_STAR)
+        return set_error(FW_E_INVALID, "session windows: aggregate kind %d is not sum / min / max / count", g.kind);
+    if (g.type != FW_T_I64 && g.type != FW_T_I32 && g.type != FW_T_F64)
+        return set_error(FW_E_INVALID, "session windows: bad aggregate type %d", g.type);
+    if (g.flags) return set_error(FW_E_INVALID, "session windows: bad aggregate flags %d", g.flags);
+    const bool is_count = g.kind == FW_AGG_COUNT_STAR;
+    if (!is_count) {
+        if (g.input_col < 0 || g.input_col >= c.n_value_cols) return set_error(FW_E_INVALID, "session windows: bad input_col");
+        if (c.value_col_types[g.input_col] != g.type)
+            return set_error(FW_E_INVALID, "session windows: type does not match value column type");
+    }
+    if (c.size_ms < 1) return set_error(FW_E_INVALID, "session gap (size_ms) must be > 0");
+    if (c.size_ms > SW_MAX_GAP) return set_error(FW_E_INVALID, "session gap (size_ms) must be <= 2^40");
+    if (c.slide_ms != 0) return set_error(FW_E_INVALID, "session windows have no slide (slide_ms must be 0)");
+    if (c.offset_ms != 0) return set_error(FW_E_INVALID, "session windows have no offset (offset_ms must be 0)");
+    if (c.allowed_lateness_ms != 0)
+        return set_error(FW_E_INVALID, "session windows with allowed lateness run on the reference operator (allowed_lateness_ms must be 0)");
+    if (c.late_side_output != 0 && c.late_side_output != 1) return set_error(FW_E_INVALID, "late_side_output must be 0 or 1");
+    if (c.ds_first_ordinals) return set_error(FW_E_INVALID, "session windows are (key, aggregate) shaped (ds_first_ordinals must be 0)");
+    if (c.nullable_cols) return set_error(FW_E_INVALID, "session windows take no NULL inputs (nullable_cols must be 0)");
+    if (c.tz_n != 0) return set_error(FW_E_INVALID, "session windows have no time zone (tz_n must be 0)");
+    if (c.agg_phase != FW_PHASE_ONE) return set_error(FW_E_INVALID, "session windows are one-phase (agg_phase must be FW_PHASE_ONE)");
+    if (c.key_hash != FW_KEYHASH_LONG && c.key_hash != FW_KEYHASH_INT && c.key_hash != FW_KEYHASH_PRECOMPUTED)
+        return set_error(FW_E_INVALID, "session windows take LONG, INT or PRECOMPUTED keys (key_hash %d: KEYROW / BINROW keys are not supported)",
+                         c.key_hash);
+    if (c.max_batch_rows <= 0 || c.max_batch_rows >= (1ll << 31)) return set_error(FW_E_INVALID, "max_batch_rows must be in (0, 2^31)");
+    if (c.output_capacity <= 0) return set_error(FW_E_INVALID, "output_capacity must be > 0");
+
+    SessionDesc& d = op->d;
+    d.gap = c.size_ms;
+    const bool f = g.type == FW_T_F64;
+    d.op = is_count ? CW_ADD_I : g.kind == FW_AGG_SUM ? (f ? CW_ADD_F : CW_ADD_I) : g.kind == FW_AGG_MIN ? CW_MIN : CW_MAX;
+    d.vtype = g.type;
+    d.is_count = is_count;
+    d.dbl_cmp = f && !is_count && (d.op == CW_MIN || d.op == CW_MAX);
+    op->val_col = is_count ? 0 : g.input_col;
+    op->late_side = c.late_side_output;
+
+    KeySpace& ks = op->ks;
+    ks.hash_kind = c.key_hash;
+    ks.max_p = c.max_parallelism;
+    ks.maxp_div = make_udiv32((uint32_t)c.max_parallelism);
+    ks.kg_start = (c.subtask_index * c.max_parallelism + c.parallelism - 1) / c.parallelism;
+    const int kg_end = ((c.subtask_index + 1) * c.max_parallelism - 1) / c.parallelism;
+    ks.n_kg = kg_end - ks.kg_start + 1;
+    ks.pass_log2 = 0;
+    // about 512 hinted sessions per superbucket, at most 2048 superbuckets (one fold workgroup each)
+    const int64_t hint = std::max<int64_t>(c.state_capacity, 1024);
+    op->cap_rows = c.max_batch_rows;
+    op->max_nch = (c.max_batch_rows + SW_TILE - 1) / SW_TILE;
+    int64_t sbk = sw_next_pow2(((hint + 511) / 512 + ks.n_kg - 1) / ks.n_kg);
+    while (sbk > 1 && ((int64_t)ks.n_kg * sbk > 2048 || (int64_t)ks.n_kg * sbk * op->max_nch > SW_MAX_HIST)) sbk >>= 1;
+    if ((int64_t)ks.n_kg * sbk * op->max_nch > SW_MAX_HIST)
+        return set_error(FW_E_INVALID, "session windows: key groups per subtask x max_batch_rows too large for the partition table");
+    ks.sb_per_kg_log2 = 0;
+    while ((1ll << ks.sb_per_kg_log2) < sbk) ks.sb_per_kg_log2++;
+    ks.n_sb = ks.n_kg << ks.sb_per_kg_log2;
+    // twice the hinted share of a superbucket
+    const int64_t cs = sw_next_pow2(std::max<int64_t>(64, 2 * ((hint + ks.n_sb - 1) / ks.n_sb)));
+    if (cs > (1ll << 22)) return set_error(FW_E_INVALID, "session windows: state_capacity too large per superbucket");
+    op->cap_s = (int32_t)cs;
+    op->out_cap = c.output_capacity;
+    op->side_cap = c.late_side_output ? 2 * c.max_batch_rows : 0;
+    uint64_t x = 0xcbf29ce484222325ull;  // the semantics fingerprint of the blobs (FNV-1a, as the time windows')
+    for (int64_t v : {(int64_t)c.api, (int64_t)FW_WIN_SESSION, d.gap, (int64_t)d.op, (int64_t)d.vtype, (int64_t)d.is_count,
+                      (int64_t)ks.hash_kind, (int64_t)ks.max_p})
+        for (int b = 0; b < 8; b++) {
+            x ^= (uint64_t)((v >> (8 * b)) & 0xff);
+            x *= 0x100000001b3ull;
+        }
+    op->fingerprint = x;
+    op->on = true;
+    return FW_OK;
+}
+
+int sw_allocate(SessionOp* op, hipStream_t stream, Ctrl* ctrl) {
+    op->stream = stream;
+    op->ctrl = ctrl;
+    int rc;
+    const int n_sb = op->ks.n_sb;
+    if ((rc = sw_dalloc(&op->state, (size_t)n_sb * op->cap_s * SW_WORDS))) return rc;
+    if ((rc = sw_dalloc(&op->scratch, (size_t)n_sb * ((size_t)op->cap_s + SW_TILE) * SW_WORDS))) return rc;
+    if ((rc = sw_dalloc(&op->n_s, (size_t)n_sb))) return rc;
+    SW_TRY(hipMemsetAsync(op->n_s, 0, (size_t)n_sb * 4, stream));
+    if ((rc = sw_dalloc(&op->min_end, (size_t)n_sb))) return rc;
+    hipLaunchKernelGGL(k_sw_fill, dim3((n_sb + 255) / 256), dim3(256), 0, stream, op->min_end, INT64_MAX, n_sb);
+    if ((rc = sw_dalloc(&op->hist, (size_t)n_sb * op->max_nch))) return rc;
+    if ((rc = sw_dalloc(&op->seg, (size_t)n_sb + 1))) return rc;
+    if ((rc = sw_dalloc(&op->s_sb, (size_t)op->cap_rows))) return rc;
+    if ((rc = sw_dalloc(&op->s_row, (size_t)op->cap_rows))) return rc;
+    if ((rc = sw_dalloc(&op->s_rank, (size_t)op->cap_rows))) return rc;
+    if ((rc = sw_dalloc(&op->perm, (size_t)op->cap_rows))) return rc;
+    const size_t oc = (size_t)op->out_cap;
+    if ((rc = sw_dalloc(&op->out_key, oc))) return rc;
+    if ((rc = sw_dalloc(&op->out_ws, oc))) return rc;
+    if ((rc = sw_dalloc(&op->out_we, oc))) return rc;
+    if ((rc = sw_dalloc(&op->out_val, oc))) return rc;
+    if ((rc = sw_dalloc(&op->out_null, oc))) return rc;
+    SW_TRY(hipMemsetAsync(op->out_null, 0, oc * 4, stream));
+    if (op->side_cap && (rc = sw_dalloc(&op->side, (size_t)op->side_cap * SW_SIDE_WORDS))) return rc;
+    SW_TRY(hipGetLastError());
+    return FW_OK;
+}
+
+void sw_free(SessionOp* op) {
+    hipFree(op->state);
+    hipFree(op->scratch);
+    hipFree(op->n_s);
+    hipFree(op->min_end);
+    hipFree(op->hist);
+    hipFree(op->seg);
+    hipFree(op->s_sb);
+    hipFree(op->s_row);
+    hipFree(op->s_rank);
+    hipFree(op->perm);
+    hipFree(op->out_key);
+    hipFree(op->out_ws);
+    hipFree(op->out_we);
+    hipFree(op->out_val);
+    hipFree(op->out_null);
+    hipFree(op->side);
+}
+
+int sw_push(SessionOp* op, int64_t watermark, int64_t n, const int64_t* d_key, const int64_t* d_ts, const int32_t* d_khash,
+            const uint64_t* d_val) {
+    if (n >= (1ll << 32) || op->push_seq >= (1ll << 30))
+        return set_error(FW_E_INVALID, "arrival ordinals need < 2^32 rows per call and < 2^30 calls");
+    hipStream_t s = op->stream;
+    const int n_sb = op->ks.n_sb;
+    for (int64_t o = 0; o < n; o += op->cap_rows) {
+        const int64_t m = std::min(op->cap_rows, n - o);
+        const int32_t nch = (int32_t)((m + SW_TILE - 1) / SW_TILE);
+        SW_TRY(hipMemsetAsync(op->hist, 0, (size_t)n_sb * nch * 4, s));
+        SwPartArgs pa{};
+        pa.key = d_key + o;
+        pa.khash = d_khash ? d_khash + o : nullptr;
+        pa.n = m;
+        pa.n_chunks = nch;
+        pa.ks = op->ks;
+        pa.ctrl = op->ctrl;
+        pa.hist = op->hist;
+        pa.s_sb = op->s_sb;
+        pa.s_row = op->s_row;
+        pa.s_rank = op->s_rank;
+        hipLaunchKernelGGL(k_sw_part, dim3(nch), dim3(SW_TILE), 0, s, pa);
+        hipLaunchKernelGGL(k_sw_scan, dim3(n_sb), dim3(256), 0, s, op->hist, op->seg, nch);
+        hipLaunchKernelGGL(k_sw_seg, dim3(1), dim3(SW_TILE), 0, s, op->seg, (int32_t)n_sb);
+        hipLaunchKernelGGL(k_sw_scatter, dim3((unsigned)((m + 255) / 256)), dim3(256), 0, s, m, nch, op->hist, op->seg, op->s_sb,
+                           op->s_row, op->s_rank, op->perm);
+        SwFoldArgs fa{};
+        fa.key = d_key + o;
+        fa.ts = d_ts + o;
+        fa.val = op->d.is_count ? nullptr : d_val + o;
+        fa.perm = op->perm;
+        fa.seg = op->seg;
+        fa.d = op->d;
+        fa.watermark = watermark;
+        fa.cap_s = op->cap_s;
+        fa.late_side = op->late_side;
+        fa.state = op->state;
+        fa.scratch = op->scratch;
+        fa.n_s = op->n_s;
+        fa.min_end = op->min_end;
+        fa.ctrl = op->ctrl;
+        fa.side = op->side;
+        fa.side_cap = op->side_cap;
+        fa.ord_base = (op->push_seq << 32) + o;
+        hipLaunchKernelGGL(k_sw_fold, dim3(n_sb), dim3(SW_TILE), 0, s, fa);
+        SW_TRY(hipGetLastError());
+    }
+    op->push_seq++;
+    return FW_OK;
+}
+
+int sw_advance(SessionOp* op, int64_t watermark) {
+    SwAdvArgs a{};
+    a.d = op->d;
+    a.watermark = watermark;
+    a.cap_s = op->cap_s;
+    a.state = op->state;
+    a.n_s = op->n_s;
+    a.min_end = op->min_end;
+    a.ctrl = op->ctrl;
+    a.out_key = op->out_key;
+    a.out_ws = op->out_ws;
+    a.out_we = op->out_we;
+    a.out_val = op->out_val;
+    a.out_cap = op->out_cap;
+    hipLaunchKernelGGL(k_sw_advance, dim3(op->ks.n_sb), dim3(SW_TILE), 0, op->stream, a);
+    SW_TRY(hipGetLastError());
+    return FW_OK;
+}
+
+// ---- checkpoint: the library's own blob.  Entries are (key, start, end, acc, key group << 32 |
+// sub-bucket) in no particular order: a restore routes every key again (precomputed-hash keys carry
+// no hash in the state, so they are placed by the recorded sub-bucket and may not be split finer
+// than the snapshot's) and sorts each superbucket's list.
+namespace {
+struct SwHeader {
+    uint64_t magic;
+    int64_t push_seq;   // at byte 8 of both blobs (runtime/handle.py _snapshot_push_seq)
+    int64_t watermark;
+    uint64_t fingerprint;
+    int32_t key_group, sb_log2;
+    int64_t n;
+};
+const uint64_t SW_MAGIC = 0x464c4b5753573031ull;     // "FLKWSW01"
+const uint64_t SW_KG_MAGIC = 0x464c4b5753473031ull;  // "FLKWSG01"
+constexpr int SW_BLOB_WORDS = SW_WORDS + 1;
+}  // namespace
+
+int sw_snapshot(SessionOp* op, int64_t watermark, int32_t key_group, void* buf, int64_t capacity, int64_t* size) {
+    const KeySpace& ks = op->ks;
+    const int L = ks.sb_per_kg_log2;
+    int sb0 = 0, sb1 = ks.n_sb;
+    if (key_group >= 0) {
+        const int li = key_group - ks.kg_start;
+        if (li < 0 || li >= ks.n_kg) return set_error(FW_E_INVALID, "key group %d is not owned by this subtask", key_group);
+        sb0 = li << L;
+        sb1 = (li + 1) << L;
+    }
+    SW_TRY(hipStreamSynchronize(op->stream));
+    std::vector<int32_t> cnt(sb1 - sb0);
+    SW_TRY(hipMemcpy(cnt.data(), op->n_s + sb0, cnt.size() * 4, hipMemcpyDeviceToHost));
+    std::vector<uint64_t> ent, tmp;
+    int64_t n = 0;
+    for (int sb = sb0; sb < sb1; sb++) {
+        const int c = cnt[sb - sb0];
+        if (c <= 0) continue;
+        tmp.resize((size_t)c * SW_WORDS);
+        SW_TRY(hipMemcpy(tmp.data(), op->state + (size_t)sb * op->cap_s * SW_WORDS, tmp.size() * 8, hipMemcpyDeviceToHost));
+        for (int i = 0; i < c; i++) {
+            ent.insert(ent.end(), tmp.begin() + (size_t)i * SW_WORDS, tmp.begin() + (size_t)(i + 1) * SW_WORDS);
+            ent.push_back((uint64_t)(ks.kg_start + (sb >> L)) << 32 | (uint32_t)(sb & ((1 << L) - 1)));
+            n++;
+        }
+    }
+    const int64_t need = (int64_t)sizeof(SwHeader) + (int64_t)ent.size() * 8;
+    *size = need;
+    if (!buf) return FW_OK;
+    if (capacity < need) return set_error(FW_E_INVALID, "snapshot buffer too small (%lld < %lld)", (long long)capacity, (long long)need);
+    SwHeader hd{key_group >= 0 ? SW_KG_MAGIC : SW_MAGIC, op->push_seq, watermark, op->fingerprint, key_group, L, n};
+    memcpy(buf, &hd, sizeof hd);
+    if (!ent.empty()) memcpy((char*)buf + sizeof hd, ent.data(), ent.size() * 8);
+    return FW_OK;
+}
+
+int sw_restore(SessionOp* op, bool key_group, const void* buf, int64_t size, int64_t* watermark) {
+    SwHeader hd;
+    if (size < (int64_t)sizeof hd) return set_error(FW_E_INVALID, "session-window snapshot truncated");
+    memcpy(&hd, buf, sizeof hd);
+    const KeySpace& ks = op->ks;
+    const int L = ks.sb_per_kg_log2;
+    if (hd.magic != (key_group ? SW_KG_MAGIC : SW_MAGIC))
+        return set_error(FW_E_INVALID, "not a session-window %ssnapshot", key_group ? "key-group " : "");
+    if (hd.fingerprint != op->fingerprint) return set_error(FW_E_INVALID, "session-window snapshot of a different operator configuration");
+    if (hd.n < 0 || size < (int64_t)sizeof hd + hd.n * SW_BLOB_WORDS * 8) return set_error(FW_E_INVALID, "session-window snapshot truncated");
+    if (ks.hash_kind == KH_PRE && L > hd.sb_log2)
+        return set_error(FW_E_INVALID, "precomputed-hash keys cannot be split finer than the snapshot's sub-buckets");
+    int sb0 = 0, sb1 = ks.n_sb;
+    if (key_group) {
+        const int li = hd.key_group - ks.kg_start;
+        if (li < 0 || li >= ks.n_kg) return set_error(FW_E_INVALID, "key group %d is not owned by this subtask", hd.key_group);
+        sb0 = li << L;
+        sb1 = (li + 1) << L;
+    }
+    SW_TRY(hipStreamSynchronize(op->stream));
+    std::vector<int32_t> cnt(sb1 - sb0, 0);
+    if (key_group) {
+        SW_TRY(hipMemcpy(cnt.data(), op->n_s + sb0, cnt.size() * 4, hipMemcpyDeviceToHost));
+        for (int32_t c : cnt)
+            if (c != 0) return set_error(FW_E_STATE, "key group %d already holds state in this subtask", hd.key_group);
+    }
+    struct Ent {
+        uint64_t key;
+        int64_t start, end;
+        uint64_t acc;
+    };
+    std::vector<std::vector<Ent>> per(sb1 - sb0);
+    const uint64_t* src = (const uint64_t*)((const char*)buf + sizeof hd);
+    for (int64_t i = 0; i < hd.n; i++) {
+        uint64_t e[SW_BLOB_WORDS];
+        memcpy(e, src + (size_t)i * SW_BLOB_WORDS, sizeof e);
+        const int kg = (int)(e[4] >> 32);
+        int sb;
+        if (ks.hash_kind == KH_PRE) {
+            // the recorded sub-bucket holds the low hd.sb_log2 quotient bits; this handle uses the low L of them
+            sb = ((kg - ks.kg_start) << L) + (int)((uint32_t)e[4] & (uint32_t)((1 << L) - 1));
+        } else {
+            uint32_t m;
+            sb = route_key(ks, (int64_t)e[0], 0, &m);
+            if (sb >= 0 && sb < ks.n_sb && ks.kg_start + (sb >> L) != kg)
+                return set_error(FW_E_INVALID, "entry key does not belong to key group %d", kg);
+        }
+        if (sb < sb0 || sb >= sb1) return set_error(FW_E_INVALID, "snapshot entry of key group %d is not owned by this subtask", kg);
+        per[sb - sb0].push_back(Ent{e[0], (int64_t)e[1], (int64_t)e[2], e[3]});
+    }
+    std::vector<uint64_t> tmp;
+    std::vector<int64_t> mins(sb1 - sb0, INT64_MAX);
+    for (int sb = sb0; sb < sb1; sb++) {
+        std::vector<Ent>& v = per[sb - sb0];
+        if ((int64_t)v.size() > op->cap_s)
+            return set_error(FW_E_CAPACITY, "restored state exceeds the session list (%d sessions per superbucket)", op->cap_s);
+        std::sort(v.begin(), v.end(), [](const Ent& x, const Ent& y) { return x.key != y.key ? x.key < y.key : x.start < y.start; });
+        tmp.clear();
+        for (const Ent& x : v) {
+            tmp.push_back(x.key);
+            tmp.push_back((uint64_t)x.start);
+            tmp.push_back((uint64_t)x.end);
+            tmp.push_back(x.acc);
+            mins[sb - sb0] = std::min(mins[sb - sb0], x.end);
+        }
+        cnt[sb - sb0] = (int32_t)v.size();
+        if (!tmp.empty())
+            SW_TRY(hipMemcpy(op->state + (size_t)sb * op->cap_s * SW_WORDS, tmp.data(), tmp.size() * 8, hipMemcpyHostToDevice));
+    }
+    SW_TRY(hipMemcpy(op->n_s + sb0, cnt.data(), cnt.size() * 4, hipMemcpyHostToDevice));
+    SW_TRY(hipMemcpy(op->min_end + sb0, mins.data(), mins.size() * 8, hipMemcpyHostToDevice));
+    Ctrl c;
+    SW_TRY(hipMemcpy(&c, op->ctrl, sizeof c, hipMemcpyDeviceToHost));
+    if (key_group) {
+        c.live_entries += hd.n;
+        op->push_seq = std::max(op->push_seq, hd.push_seq);
+    } else {
+        c.live_entries = hd.n;
+        c.error = 0;
+        c.out_count[0] = 0;
+        c.n_side = 0;
+        op->push_seq = hd.push_seq;
+        *watermark = hd.watermark;
+        c.cur = hd.watermark;
+    }
+    SW_TRY(hipMemcpy(op->ctrl, &c, sizeof c, hipMemcpyHostToDevice));
+    return FW_OK;
+}
+
+}  // namespace fw

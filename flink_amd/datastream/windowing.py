@@ -107,3 +107,25 @@ class CountEvictor:
     @staticmethod
     def of(max_count, do_evict_after=False):
         return CountEvictor(max_count, do_evict_after)
+
+
+# ---- session windows: keyBy(...).window(EventTimeSessionWindows.withGap(gap))
+class EventTimeSessionWindows:
+    """EventTimeSessionWindows.withGap(size) (assigners/EventTimeSessionWindows.java): a merging
+    assigner; every element gets the window [ts, ts + gap), and MergingWindowSet merges the windows
+    of a key that intersect."""
+
+    def __init__(self, gap_ms):
+        if gap_ms <= 0:
+            raise ValueError("EventTimeSessionWindows parameters must satisfy 0 < size")
+        self.gap = int(gap_ms)
+
+    @staticmethod
+    def with_gap(gap_ms):
+        return EventTimeSessionWindows(gap_ms)
+
+    def assign_windows(self, ts):
+        return [(ts, ts + self.gap)]
+
+    def is_event_time(self):
+        return True

@@ -104,7 +104,27 @@ typedef enum {
        The async / device / segment result calls, the segment and key-row pushes, fw_late_records,
        fw_first_element_events, the heap-format and fw_ds_* key-group calls and the profiling calls
        return FW_E_INVALID on a count handle.  A full key table raises FW_ERRF_STATE. */
-    FW_WIN_COUNT = 3
+    FW_WIN_COUNT = 3,
+    /* v11 (additive), DataStream only: EventTimeSessionWindows.withGap(gap) with EventTimeTrigger, no
+       evictor, allowedLateness 0.  size_ms carries the gap (0 < gap <= 2^40); slide_ms, offset_ms and
+       allowed_lateness_ms must be 0.  An element's window [ts, ts + gap) and every session of its key
+       that it intersects (TimeWindow.intersects: inclusive, touching windows merge) become one
+       session; an element whose window is late (ts + gap - 1 <= watermark) and intersects no session
+       of its key when it arrives is dropped (num_late_records_dropped, or the late side output with
+       late_side_output = 1: fw_late_records, capacity 2 * max_batch_rows, FW_ERRF_LATE beyond it).
+       One aggregate (SUM / MIN / MAX / COUNT_STAR over I64 / I32 / F64), keys LONG / INT /
+       PRECOMPUTED; ds_first_ordinals, nullable columns, time zones and two-phase plans must be unset.
+       Timestamps outside [-2^62, 2^62) are unspecified.  Every push is folded into the state when it
+       is pushed, under the watermark of the last fw_advance (fw_stats.pending_rows stays 0; d_ts is
+       required); fw_advance(W') with W' above the current watermark fires every session with
+       end - 1 <= W' once and clears it, fw_flush does nothing.  Results come from fw_results /
+       fw_results_reset: key, window_start, window_end, values[0], a zero null mask, first_ord NULL.
+       fw_snapshot / fw_restore and the key-group forms use blobs of their own, which carry the
+       watermark and do not depend on the superbucket split.  The async / device / segment result
+       calls, the segment and key-row pushes, fw_advance_device, fw_first_element_events, the
+       heap-format and fw_ds_* key-group calls and the profiling calls return FW_E_INVALID on a
+       session handle.  A full session list raises FW_ERRF_STATE and drops the tile's rows. */
+    FW_WIN_SESSION = 4
 } fw_window_kind;
 
 typedef enum {
@@ -713,6 +733,16 @@ int fw_host_time_op(const fw_config* cfg, int32_t what, int64_t x, int64_t* out)
    first element arrives.  Returns FW_E_INVALID for a configuration fw_create would reject. */
 int fw_host_count_step(const fw_config* cfg, int64_t index, int64_t* slice, int32_t* ring_slot, int32_t* fires,
                        int64_t* window_start, int32_t* n_slices);
+/* v11 (additive): one element of one key against that key's sessions, as the kernels run it
+   (WindowOperator.processElement's merging branch, MergingWindowSet.addWindow, TimeWindow.intersects
+   / cover, the late test and the aggregate's fold -- the same routines the device code calls).
+   starts / ends / accs hold *n sessions sorted by start, pairwise non-touching, accs as result
+   values (DOUBLE as bits); capacity is the arrays' length.  The element (ts, value) under the
+   watermark either merges with every session it intersects or starts a session (*outcome = 1), or
+   is dropped as late and leaves the list untouched (*outcome = 0).  Returns FW_E_INVALID for a
+   configuration fw_create would reject, FW_E_CAPACITY when a new session does not fit. */
+int fw_host_session_add(const fw_config* cfg, int64_t watermark, int64_t ts, int64_t value, int64_t* starts, int64_t* ends,
+                        int64_t* accs, int32_t* n, int32_t capacity, int32_t* outcome);
 
 #ifdef __cplusplus
 }

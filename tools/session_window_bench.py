@@ -1,0 +1,90 @@
+#!/usr/bin/env python
+"""Session-window throughput on one GPU: EventTimeSessionWindows.withGap(3 s).sum(LONG),
+device-resident pushes, a watermark after every push.
+
+Three streams of --rows rows per push (default 2^22): 10^6 uniform keys, Zipf(1.1) over 10^6 keys,
+and one hot key (the path's known worst case: a key's rows are folded by one workgroup, tile after
+tile).  Push s carries event times in [10 s * s, 10 s * (s + 1)) and is followed by the watermark
+10 s * (s + 1) - 1, so no element is late and sessions of earlier pushes fire.  A step is the push,
+the advance and the (stream-ordered) result reset; it is timed on the host around a handle sync.
+Prints one JSON line per stream.
+
+    python tools/session_window_bench.py [--rows N] [--warmup 5] [--steps 20] [--streams uniform,zipf,hot]
+"""
+import argparse
+import json
+import os
+import sys
+import time
+
+import numpy as np
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+
+GAP_MS = 3000
+SPAN_MS = 10_000
+
+
+def _keys(kind, n_keys, rows, pushes, device):
+    import torch
+    g = torch.Generator(device=device)
+    g.manual_seed(1234)
+    if kind == "hot":
+        return [torch.full((rows,), 42, dtype=torch.int64, device=device)] * pushes
+    if kind == "uniform":
+        return [torch.randint(0, n_keys, (rows,), generator=g, device=device, dtype=torch.int64) for _ in range(pushes)]
+    w = torch.arange(1, n_keys + 1, device=device, dtype=torch.float64).pow(-1.1)
+    cdf = torch.cumsum(w / w.sum(), 0)
+    return [torch.searchsorted(cdf, torch.rand(rows, generator=g, device=device, dtype=torch.float64)).clamp_(max=n_keys - 1)
+            for _ in range(pushes)]
+
+
+def run(kind, rows, warmup, steps, n_keys=10**6):
+    import torch
+    from flink_amd.datastream import SessionWindowOperator
+    dev = torch.device("cuda", 0)
+    if kind == "hot":  # a step of the hot key takes far longer than the others: fewer of them
+        warmup, steps = min(warmup, 1), min(steps, 3)
+    op = SessionWindowOperator(GAP_MS, ("sum", "LONG"), state_capacity=1 << 21, max_batch_rows=rows,
+                               output_capacity=1 << 22).open()
+    try:
+        keys = _keys(kind, n_keys, rows, min(warmup + steps, 8), dev)
+        vals = torch.randint(1, 10**6, (rows,), device=dev, dtype=torch.int64)
+        offs = torch.randint(0, SPAN_MS, (rows,), device=dev, dtype=torch.int64)
+        torch.cuda.synchronize()
+        ms = []
+        for s in range(warmup + steps):
+            ts = offs + s * SPAN_MS
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            op.process_batch_device(keys[s % len(keys)], ts, vals)
+            op.handle.advance((s + 1) * SPAN_MS - 1)
+            op.handle.reset_results()  # the rows count as consumed (stream-ordered)
+            op.handle.sync()
+            if s >= warmup:
+                ms.append((time.perf_counter() - t0) * 1e3)
+        ms = np.array(ms)
+        st = op.handle.stats()
+        return {"tool": "session_window_bench", "stream": kind, "window": "EventTimeSessionWindows.withGap(3s).sum LONG",
+                "rows_per_push": rows, "keys": 1 if kind == "hot" else n_keys, "warmup": warmup, "steps": steps,
+                "ms_per_push_median": round(float(np.median(ms)), 4), "ms_per_push_min": round(float(ms.min()), 4),
+                "events_per_s": round(rows / (float(np.median(ms)) * 1e-3)), "fired_windows": st["num_fired_windows"],
+                "live_sessions": st["live_state_entries"], "late_dropped": st["num_late_records_dropped"],
+                "superbuckets": st["num_superbuckets"], "error_flags": st["error_flags"]}
+    finally:
+        op.close()
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--rows", type=int, default=1 << 22)
+    ap.add_argument("--warmup", type=int, default=5)
+    ap.add_argument("--steps", type=int, default=20)
+    ap.add_argument("--streams", default="uniform,zipf,hot")
+    a = ap.parse_args()
+    for kind in a.streams.split(","):
+        print(json.dumps(run(kind, a.rows, a.warmup, a.steps)), flush=True)
+
+
+if __name__ == "__main__":
+    main()
