@@ -9,6 +9,7 @@
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
+#include <atomic>
 #include <chrono>
 #include <cstdarg>
 #include <cstdio>
@@ -135,6 +136,9 @@ int fw::set_error(int code, const char* fmt, ...) {
     g_err = buf;
     return code;
 }
+
+// pushes k_ingest_pack took, over every handle of the process (fw_ingest_pack_launches(NULL))
+static std::atomic<int64_t> g_ig_pack_launches{0};
 
 struct fw_handle {
     fw_config cfg;
@@ -301,6 +305,15 @@ struct fw_handle {
     KTimer* timer = nullptr;  // non-null while fw_set_profiling is on
     int ablate = 0;           // FW_ABLATE (development timing builds only; results are wrong)
     int fold_always = 0;      // FW_FOLD=1 (development A/B): no adaptive fold skip
+    // k_ingest_pack (fw_ingest_pack.h): FW_IG_PACK 0 never, 1 (default) when the last completed push
+    // left the LDS fold skipped and valid PF_PACK fields, 2 on every push of an eligible handle (tests)
+    int ig_pack_mode = 1;
+    bool ig_pack_ok = false;  // planned: the handle's pushes are ones k_ingest_pack serves
+    // ingest mirror: host-mapped word written after each ingest launch (Tickets::ig_mirror)
+    volatile unsigned long long* ig_mirror = nullptr;
+    unsigned long long* d_ig_mirror = nullptr;
+    uint64_t ig_pushes = 0;          // ingest launches since the control block was initialised (Ctrl::push_count)
+    int64_t ig_pack_launches = 0;    // of all launches, the ones k_ingest_pack took
     int fill_pct = 75;        // superbucket LDS fill target (FW_FILL_PCT: development A/B)
     unsigned long long* stamps = nullptr;  // [N_STAMPS] merge phase cycles (FW_ABLATE & AB_STAMPS)
     unsigned long long* kt_dev = nullptr;  // [FW_KT_N][KT_WORDS] in-kernel launch timing
@@ -715,6 +728,12 @@ int validate_and_plan(fw_handle* h) {
         const bool ok = c.api == FW_API_SQL && !h->keyrow && c.agg_phase != FW_PHASE_GLOBAL && h->tz_utc.empty() &&
                         w.fast32 && ks.pass_log2 == 0 && (h->chunk_rows & (h->chunk_rows - 1)) == 0;
         h->pack = ok && int_word && h->run_rows > 0 && !(pe && atoi(pe) == 0);
+        // k_ingest_pack takes the PF_PACK pushes of SQL TUMBLE handles with one value column, NOT NULL
+        // columns and a key hash computed on the device, whose superbuckets fit its LDS plan (igp_serves).
+        // COUNT(*) alone stays with k_ingest: its pushes that cannot pack are PF_UNIT / PF_NARROW.
+        h->ig_pack_ok = h->pack && !h->narrow && c.window_kind == FW_WIN_TUMBLE && c.agg_phase != FW_PHASE_LOCAL &&
+                        c.nullable_cols == 0 && ks.hash_kind != FW_KEYHASH_PRECOMPUTED && h->nv == 1 && op != W_CNT &&
+                        ad.by_prev < 0 && ks.n_sb <= IGP_MAX_SB && h->chunk_rows == IGP_BLOCK * IGP_RPT;
     }
     h->treq_cap = std::max<int64_t>(c.max_batch_rows * 2, 1 << 16);
     if (c.api == FW_API_DATASTREAM) {
@@ -820,6 +839,7 @@ int allocate(fw_handle* h) {
             h->run_rows = 0;
             h->sub_cap = 0;
             h->pack = 0;
+            h->ig_pack_ok = false;
         } else {
             h->runs = (uint64_t*)r;
             h->run_ranks = (uint8_t*)rr;
@@ -882,7 +902,12 @@ int allocate(fw_handle* h) {
     HIP_TRY(hipHostMalloc((void**)&h->mirror, sizeof(unsigned long long), hipHostMallocMapped | hipHostMallocCoherent));
     *h->mirror = ~0ull;
     HIP_TRY(hipHostGetDevicePointer((void**)&h->d_mirror, (void*)h->mirror, 0));
+    HIP_TRY(hipHostMalloc((void**)&h->ig_mirror, sizeof(unsigned long long), hipHostMallocMapped | hipHostMallocCoherent));
+    *h->ig_mirror = ~0ull;
+    HIP_TRY(hipHostGetDevicePointer((void**)&h->d_ig_mirror, (void*)h->ig_mirror, 0));
     HIP_TRY(hipMemsetAsync(h->tickets, 0, sizeof(Tickets), h->stream));
+    if (h->ig_pack_ok)  // only handles that may choose k_ingest_pack have their ingest launches report
+        HIP_TRY(hipMemcpyAsync(&h->tickets->ig_mirror, &h->d_ig_mirror, sizeof(h->d_ig_mirror), hipMemcpyHostToDevice, h->stream));
     HIP_TRY(hipMemsetAsync(h->stamps, 0, sizeof(unsigned long long) * N_STAMPS, h->stream));
     HIP_TRY(hipMemsetAsync(h->kt_dev, 0, sizeof(unsigned long long) * FW_KT_N * KT_WORDS, h->stream));
     HIP_TRY(hipMemsetAsync(h->sb_out, 0, sizeof(int32_t) * (h->ks.n_sb + 1), h->stream));
@@ -1157,7 +1182,25 @@ int push(fw_handle* h, int64_t n, const int64_t* key, const int64_t* ts, const i
         a.run_rows = h->run_rows;
         a.sub_cap = h->sub_cap;
         a.pack = h->pack;
-        HIP_TRY(launch_ingest(a, h->stream, h->timer));
+        // k_ingest_pack or k_ingest.  The mirror may lag the device by the launches in flight: the
+        // packing kernel checks again on the device and falls back per launch or per chunk, so a stale
+        // word costs time only.  k_ingest keeps the pushes on which it folds again (every 8th by
+        // Ctrl::push_count), so a stream that turns skewed is noticed and fold_skip refreshed.
+        bool packing = false;
+        if (h->ig_pack_ok && h->ig_pack_mode && !kh && !seg_counts && stride == 1) {
+            const unsigned long long v = *h->ig_mirror;
+            packing = h->ig_pack_mode == 2 || (v != ~0ull && (v & IGM_FOLD_SKIP) && (v & IGM_PK_OK) &&
+                                               (h->ig_pushes & 7u) != 0 && !h->fold_always);
+        }
+        HIP_TRY(packing ? launch_ingest_pack(a, h->stream, h->timer) : launch_ingest(a, h->stream, h->timer));
+        // k_ingest does not write the mirror itself: a one-thread launch behind it does (in the steady
+        // state of a uniform stream that is every 8th push)
+        if (!packing && h->ig_pack_ok && h->ig_pack_mode == 1) HIP_TRY(launch_ig_report(h->tickets, h->ctrl, h->stream));
+        h->ig_pushes++;
+        if (packing) {
+            h->ig_pack_launches++;
+            g_ig_pack_launches.fetch_add(1, std::memory_order_relaxed);
+        }
         h->pushes_ub++;
         h->pushes_total++;
     }
@@ -1273,6 +1316,7 @@ int fw_create(const fw_config* cfg, fw_handle** out) {
     h->cfg = *cfg;
     if (const char* ab = getenv("FW_ABLATE")) h->ablate = atoi(ab);
     if (const char* fo = getenv("FW_FOLD")) h->fold_always = atoi(fo);
+    if (const char* ip = getenv("FW_IG_PACK")) h->ig_pack_mode = std::min(std::max(atoi(ip), 0), 2);
     if (const char* ak = getenv("FW_AR_KERNEL")) h->ar_kernel = atoi(ak);
     if (const char* fp = getenv("FW_FILL_PCT")) h->fill_pct = std::min(95, std::max(10, atoi(fp)));
     if (const char* si = getenv("FW_SKIP_IDLE")) h->skip_idle = atoi(si) != 0;
@@ -1308,6 +1352,7 @@ int fw_destroy(fw_handle* h) {
     hipFree(h->ranks);
     hipFree(h->treq);
     if (h->mirror) hipHostFree((void*)h->mirror);
+    if (h->ig_mirror) hipHostFree((void*)h->ig_mirror);
     hipFree(h->lfire);
     hipFree(h->side);
     hipFree(h->ordev);
@@ -2214,6 +2259,10 @@ int fw_set_profiling(fw_handle* h, int enable) {
     return FW_OK;
 }
 
+int64_t fw_ingest_pack_launches(fw_handle* h) {
+    return h ? h->ig_pack_launches : g_ig_pack_launches.load(std::memory_order_relaxed);
+}
+
 int fw_get_kernel_times(fw_handle* h, fw_kernel_times* out) {
     if (!h || !out) return fail(FW_E_INVALID, "null argument");
     CW_REFUSE(h, "fw_get_kernel_times");
@@ -2482,6 +2531,8 @@ int fw_restore(fw_handle* h, const void* buf, int64_t size) {
     HIP_TRY(hipMemcpy(&c, h->ctrl, sizeof c, hipMemcpyDeviceToHost));  // the key-row allocator survives
     const Ctrl keep = c;
     HIP_TRY(launch_init_ctrl(h->ctrl, h->stream));
+    h->ig_pushes = 0;  // Ctrl::push_count starts over: so does the host's copy, and the ingest mirror
+    if (h->ig_mirror) *h->ig_mirror = ~0ull;
     // the restore drops the pending pushes: with runs, their fill counters, overflow flags and formats
     // go too (as allocate() starts them), or the next push would add onto the dropped push's fills and
     // the next flush would fold its stale rows

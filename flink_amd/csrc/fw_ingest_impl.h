@@ -25,33 +25,6 @@ namespace fw {
 // (key, sliceEnd)) and the per-group fold of AggCombiner.combine (:76-99).
 // ======================================================================================
 
-// inclusive scan of one value per thread over an NT-thread block (wave shuffles + LDS)
-template <int NT>
-__device__ __forceinline__ uint32_t block_incl_scan(uint32_t v, uint32_t* wsum, uint32_t* total) {
-    const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
-    constexpr int NWV = NT / 64;
-#pragma unroll
-    for (int d = 1; d < 64; d <<= 1) {
-        const uint32_t t = __shfl_up(v, d, 64);
-        if (lane >= d) v += t;
-    }
-    if (lane == 63) wsum[w] = v;
-    __syncthreads();
-    if (tid < 64) {
-        uint32_t x = tid < NWV ? wsum[tid] : 0u;
-#pragma unroll
-        for (int d = 1; d < NWV; d <<= 1) {
-            const uint32_t t = __shfl_up(x, d, 64);
-            if (lane >= d) x += t;
-        }
-        if (tid < NWV) wsum[tid] = x;
-    }
-    __syncthreads();
-    if (w > 0) v += wsum[w - 1];
-    *total = wsum[NWV - 1];
-    return v;
-}
-
 // X: the configuration has nullable columns or words that read arrival ordinals (gates, ordinals)
 template <int NV, int NW, int RPT, bool X, int IG_BLOCK>
 // (launch bounds: 4 waves per SIMD, 128 VGPRs)

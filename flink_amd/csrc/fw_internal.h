@@ -105,6 +105,24 @@ constexpr bool ig_runs_fit(int n_isb, int block, int rpt, int nw) {
     return n_isb <= RUN_KMAX * block && lds - fixed >= 256 * 8 * (2 + nw);
 }
 
+// ---- k_ingest_pack (fw_ingest_pack.h): the early-packing ingest of PF_PACK pushes.  512 threads x 8
+// rows like k_ingest's narrow variant (same chunks, same cells), but a row is packed to its 8-B run
+// word as soon as it is routed, so a routed row holds 3 registers, and the LDS holds no fold table:
+// 64 VGPRs and 39 KiB, four workgroups per CU instead of two.
+constexpr int IGP_BLOCK = 512;
+constexpr int IGP_RPT = 8;
+constexpr int IGP_LDS = 39 * 1024;
+constexpr int IGP_AHEAD = 8;                       // rows per thread whose column loads are in flight at once
+constexpr int IGP_WAVES = 6;                       // waves per SIMD the registers are bounded for (6: 80 VGPRs, 3 workgroups per CU)
+constexpr int IGP_MAX_SB = 1024;                   // superbuckets its histogram / run bookkeeping holds
+constexpr int IGP_KMAX = IGP_MAX_SB / IGP_BLOCK;   // superbuckets per thread for the run claims
+// LDS bytes in front of the store stage: header, u16 histogram, u16 rbound, u32 roff (16-B multiples)
+constexpr int igp_fixed_bytes(int n_sb) { return 8 * (IG_HDR_WORDS + ig_hist_words(n_sb)) + 6 * ((n_sb + 7) & ~7); }
+// rows of a store window: an 8-B word and a 4-B destination per row
+constexpr int igp_stage_rows(int n_sb) { return ((IGP_LDS - igp_fixed_bytes(n_sb)) / 12) & ~15; }
+static_assert(igp_stage_rows(IGP_MAX_SB) >= 2048, "two store windows per chunk at most");
+static_assert(igp_stage_rows(IGP_MAX_SB) * 12 >= 2 * IGP_BLOCK * IGP_RPT, "the slow chunk's rank array fits the stage");
+
 // Partial-row formats, one per (push slot, chunk); a cell word is start | count << 16 | format << 30
 // (chunks hold <= 4096 rows).  A chunk whose rows all took the ingest kernel's common path (UTC SQL
 // slice ends on the slice grid, within PF_MAX_RANK slices of the push's rank base) leaves the slice
@@ -263,7 +281,12 @@ constexpr int TK_GROUPS = 16;
 struct Tickets {
     uint32_t c[2][TK_GROUPS + 1][32];
     uint32_t work[8][32];  // k_merge_fire: next superbucket of each XCD's share (reset by the last workgroup)
+    // host-mapped word (nullptr: none) written after an ingest launch for the host's choice of the next
+    // push's ingest kernel: push_count << 8 | IGM_PK_OK | IGM_FOLD_SKIP as the push leaves them
+    // (k_ingest_pack's last workgroup; k_ig_report behind a k_ingest launch)
+    unsigned long long* ig_mirror;
 };
+constexpr unsigned long long IGM_FOLD_SKIP = 1, IGM_PK_OK = 2;  // Tickets::ig_mirror bits
 
 struct Ctrl {
     int64_t cur;             // currentProgress == operator / timer-service watermark
@@ -730,6 +753,8 @@ inline void kt_mark(KTimer* t, int kind, bool end, hipStream_t s) {
 // launchers (fw_kernels.hip)
 hipError_t launch_compact(const CompactArgs& a, hipStream_t s, KTimer* t);
 hipError_t launch_ingest(const IngestArgs& a, hipStream_t s, KTimer* t);
+hipError_t launch_ingest_pack(const IngestArgs& a, hipStream_t s, KTimer* t);  // k_ingest_pack.hip
+hipError_t launch_ig_report(const Tickets* tk, const Ctrl* ctrl, hipStream_t s);   // k_ingest_pack.hip
 hipError_t launch_merge_fire(const MergeArgs& a, hipStream_t s, KTimer* t);
 hipError_t launch_init_ctrl(Ctrl* c, hipStream_t s);
 // key rows (fw_keyrows.hip)

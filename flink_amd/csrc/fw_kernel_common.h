@@ -322,6 +322,33 @@ __device__ __forceinline__ int64_t wred_sum_i64(int64_t v) {
     return wred<int64_t>(v, 0, [](int64_t a, int64_t b) { return a + b; });
 }
 
+// inclusive scan of one value per thread over an NT-thread block (wave shuffles + LDS)
+template <int NT>
+__device__ __forceinline__ uint32_t block_incl_scan(uint32_t v, uint32_t* wsum, uint32_t* total) {
+    const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
+    constexpr int NWV = NT / 64;
+#pragma unroll
+    for (int d = 1; d < 64; d <<= 1) {
+        const uint32_t t = __shfl_up(v, d, 64);
+        if (lane >= d) v += t;
+    }
+    if (lane == 63) wsum[w] = v;
+    __syncthreads();
+    if (tid < 64) {
+        uint32_t x = tid < NWV ? wsum[tid] : 0u;
+#pragma unroll
+        for (int d = 1; d < NWV; d <<= 1) {
+            const uint32_t t = __shfl_up(x, d, 64);
+            if (lane >= d) x += t;
+        }
+        if (tid < NWV) wsum[tid] = x;
+    }
+    __syncthreads();
+    if (w > 0) v += wsum[w - 1];
+    *total = wsum[NWV - 1];
+    return v;
+}
+
 // PF_PACK fields for the next flush epoch from a push's key and accumulator ranges (fw_internal.h):
 // each field twice the measured span (kb + rb + vb = 64, 2 <= rb <= 8, the spare bits widen the
 // accumulator field: sums drift), the bases centred on the ranges.  Returns the fields word (0: the
@@ -338,6 +365,23 @@ __device__ __forceinline__ uint32_t pack_fields(int64_t kmn, int64_t kmx, int64_
     *kbase = (int64_t)((uint64_t)kmn - ((((1ull << kb) - 1ull) - ks) >> 1));
     *vbase = (int64_t)((uint64_t)vmn - ((((1ull << vb) - 1ull) - vs) >> 1));
     return kb | (rb << 8) | (vb << 16) | PK_OK;
+}
+
+// a wave-uniform value a vector load or vector arithmetic produced, moved to scalar registers
+__device__ __forceinline__ uint32_t uni32(uint32_t v) { return (uint32_t)__builtin_amdgcn_readfirstlane((int)v); }
+__device__ __forceinline__ int64_t uni64(int64_t v) {
+    return (int64_t)(((uint64_t)uni32((uint32_t)((uint64_t)v >> 32)) << 32) | uni32((uint32_t)v));
+}
+
+// Tickets::ig_mirror: what the push just committed leaves for the next one (the thread that wrote
+// the control block; a vector store to host-mapped memory, system scope)
+__device__ __forceinline__ void ig_mirror_store(const Tickets* tk, const Ctrl* ctrl) {
+    unsigned long long* mirror = tk->ig_mirror;
+    if (!mirror) return;
+    __hip_atomic_store(mirror,
+                       ((unsigned long long)ctrl->push_count << 8) | (ctrl->fold_skip ? IGM_FOLD_SKIP : 0ull) |
+                           ((ctrl->pk_next_bits & PK_OK) ? IGM_PK_OK : 0ull),
+                       __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
 }
 
 // slot claim for the active lanes of a wave: one atomicAdd on *ctr, each lane gets base + rank

@@ -433,6 +433,10 @@ class WindowAggHandle:
         m = {"device": 1, "events": 2, "events_all": 3}[mode]
         check(lib().fw_set_profiling(self._h, m if enable else 0))
 
+    def ingest_pack_launches(self):
+        """Ingest launches of this handle the early-packing kernel (k_ingest_pack) took."""
+        return int(lib().fw_ingest_pack_launches(self._h))
+
     def kernel_times(self):
         """{kind: (ms, launches)} accumulated since set_profiling(True)."""
         t = abi.fw_kernel_times()

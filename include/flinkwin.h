@@ -516,6 +516,10 @@ typedef struct {
 int fw_set_profiling(fw_handle* h, int enable);
 /* synchronises the handle stream, then returns the accumulated times */
 int fw_get_kernel_times(fw_handle* h, fw_kernel_times* out);
+/* Ingest launches the early-packing kernel took (k_ingest_pack: PF_PACK pushes of SQL TUMBLE handles
+   with one NOT NULL integer aggregate; FW_IG_PACK=0 never, 1 by the last push's report, 2 on every push of
+   such a handle).  h == NULL: over every handle of the process.  No device call. */
+int64_t fw_ingest_pack_launches(fw_handle* h);
 
 /* ---- checkpoint -------------------------------------------------------------------- */
 /* Flushes, then serialises watermark + state + timers.  *size receives the byte count;

@@ -2,7 +2,7 @@
 # Register / spill report of the kernel translation units (host-side compile only):
 #   tools/regs.sh [k_ingest_nv1 k_merge_nw1 ...]
 cd "$(dirname "$0")/../flink_amd/csrc"
-units=${@:-"k_ingest_nv0 k_ingest_nv1 k_ingest_nv2 k_merge_nw1 k_merge_nw2 k_merge_nw4"}
+units=${@:-"k_ingest_nv0 k_ingest_nv1 k_ingest_nv2 k_ingest_pack k_merge_nw1 k_merge_nw2 k_merge_nw4"}
 for f in $units; do
   /opt/rocm/bin/hipcc -O3 -std=c++17 -fPIC --offload-arch=gfx950 -DFW_DIAG=0 -c -o /tmp/_regs_$f.o $f.hip \
       -Rpass-analysis=kernel-resource-usage 2>&1 |
