@@ -305,9 +305,12 @@ struct fw_handle {
     KTimer* timer = nullptr;  // non-null while fw_set_profiling is on
     int ablate = 0;           // FW_ABLATE (development timing builds only; results are wrong)
     int fold_always = 0;      // FW_FOLD=1 (development A/B): no adaptive fold skip
-    // k_ingest_pack (fw_ingest_pack.h): FW_IG_PACK 0 never, 1 (default) when the last completed push
-    // left the LDS fold skipped and valid PF_PACK fields, 2 on every push of an eligible handle (tests)
+    // k_ingest_pack (fw_ingest_pack.h): FW_IG_PACK 0 never, 1 (default) by fw_host_ig_pack_choice (the
+    // last completed push left the LDS fold skipped and valid PF_PACK fields, a flush epoch has been
+    // opened, no fold measurement is due), 2 on every push of an eligible handle (tests)
     int ig_pack_mode = 1;
+    uint64_t ig_since_fold = 0;      // pushes since the last one on which k_ingest folded (that one included)
+    uint64_t ig_merges = 0;          // merge launches since the control block was initialised
     bool ig_pack_ok = false;  // planned: the handle's pushes are ones k_ingest_pack serves
     // ingest mirror: host-mapped word written after each ingest launch (Tickets::ig_mirror)
     volatile unsigned long long* ig_mirror = nullptr;
@@ -1079,6 +1082,7 @@ int launch_merge(fw_handle* h, int64_t wm, int force) {
     HIP_TRY(launch_merge_fire(merge_args(h, wm, force), h->stream, h->timer));
     h->pushes_at_merge[h->merge_seq % 64] = h->pushes_total;
     h->merge_seq++;
+    h->ig_merges++;
     h->reset_pending = false;  // the launch started every output slab (and the overflow) afresh
     if (!force && wm > h->dev_cur) {  // merge_finalize's advanceProgress bookkeeping, mirrored
         h->dev_cur = wm;
@@ -1182,20 +1186,24 @@ int push(fw_handle* h, int64_t n, const int64_t* key, const int64_t* ts, const i
         a.run_rows = h->run_rows;
         a.sub_cap = h->sub_cap;
         a.pack = h->pack;
-        // k_ingest_pack or k_ingest.  The mirror may lag the device by the launches in flight: the
-        // packing kernel checks again on the device and falls back per launch or per chunk, so a stale
-        // word costs time only.  k_ingest keeps the pushes on which it folds again (every 8th by
-        // Ctrl::push_count), so a stream that turns skewed is noticed and fold_skip refreshed.
-        bool packing = false;
-        if (h->ig_pack_ok && h->ig_pack_mode && !kh && !seg_counts && stride == 1) {
-            const unsigned long long v = *h->ig_mirror;
-            packing = h->ig_pack_mode == 2 || (v != ~0ull && (v & IGM_FOLD_SKIP) && (v & IGM_PK_OK) &&
-                                               (h->ig_pushes & 7u) != 0 && !h->fold_always);
-        }
+        // k_ingest_pack or k_ingest (fw_host_ig_pack_choice).  The mirror may lag the device by the
+        // launches in flight: the packing kernel checks again on the device and falls back per launch
+        // or per chunk, so a stale word costs time only.
+        const unsigned long long igv = h->ig_mirror ? *h->ig_mirror : ~0ull;
+        const int32_t choice = fw_host_ig_pack_choice(
+            h->ig_pack_mode, igv, h->ig_since_fold, h->ig_merges,
+            (h->ig_pack_ok ? 0u : FW_IGX_PLAN) | (kh ? FW_IGX_KEY_HASH : 0u) | (seg_counts ? FW_IGX_SEGMENTS : 0u) |
+                (stride != 1 ? FW_IGX_STRIDE : 0u) | (h->fold_always ? FW_IGX_FOLD_ALWAYS : 0u));
+        const bool packing = choice == FW_IG_PACK;
+        if (choice == FW_IG_FOLD) a.fold_always = 1;  // the push on which k_ingest folds and measures again
         HIP_TRY(packing ? launch_ingest_pack(a, h->stream, h->timer) : launch_ingest(a, h->stream, h->timer));
         // k_ingest does not write the mirror itself: a one-thread launch behind it does (in the steady
-        // state of a uniform stream that is every 8th push)
+        // state of a uniform stream that is one push in 64)
         if (!packing && h->ig_pack_ok && h->ig_pack_mode == 1) HIP_TRY(launch_ig_report(h->tickets, h->ctrl, h->stream));
+        // a k_ingest launch folds when told to, when fold_skip is clear, and on every 8th push by
+        // Ctrl::push_count, which ig_pushes follows
+        if (!packing && (a.fold_always || (h->ig_pushes & 7u) == 0 || (igv != ~0ull && !(igv & IGM_FOLD_SKIP)))) h->ig_since_fold = 0;
+        h->ig_since_fold++;
         h->ig_pushes++;
         if (packing) {
             h->ig_pack_launches++;
@@ -1718,6 +1726,7 @@ int fw_advance_device(fw_handle* h, const int64_t* d_watermark) {
     // only ever skip launches, so a stale, lower value skips fewer)
     h->pushes_at_merge[h->merge_seq % 64] = h->pushes_total;
     h->merge_seq++;
+    h->ig_merges++;
     h->reset_pending = false;
     if (h->keyrow)
         HIP_TRY(launch_kr_collect(h->kr, h->ctrl, h->state, h->state_count, h->sb_nar, h->nw_t, h->ks.n_sb, h->cap_e, h->pwe,
@@ -2532,6 +2541,8 @@ int fw_restore(fw_handle* h, const void* buf, int64_t size) {
     const Ctrl keep = c;
     HIP_TRY(launch_init_ctrl(h->ctrl, h->stream));
     h->ig_pushes = 0;  // Ctrl::push_count starts over: so does the host's copy, and the ingest mirror
+    h->ig_since_fold = 0;
+    h->ig_merges = 0;  // (no PF_PACK fields until a push has measured them and a flush has opened an epoch)
     if (h->ig_mirror) *h->ig_mirror = ~0ull;
     // the restore drops the pending pushes: with runs, their fill counters, overflow flags and formats
     // go too (as allocate() starts them), or the next push would add onto the dropped push's fills and
@@ -3362,6 +3373,24 @@ int64_t fw_host_window_start(int64_t ts, int64_t offset, int64_t size) {
 }
 int64_t fw_host_next_trigger_watermark(int64_t wm, int64_t interval) {
     return next_trigger_watermark(wm, make_udiv((uint64_t)interval));
+}
+
+// Which ingest kernel takes a push (pure; push() above is its only caller beside the tests).
+// k_ingest_pack never folds, so k_ingest keeps every push on which something has to be folded or
+// measured: while fold_skip is clear or no PF_PACK fields are valid, while no flush has opened an
+// epoch that could carry such fields (the packing kernel would send every chunk the slow way), and
+// once in FW_IG_REFRESH pushes -- once in FW_IG_REFRESH_SKEW while the packing kernel's own sampled
+// estimate (IGM_SKEW) says the stream folds -- on which it is told to fold whatever
+// Ctrl::push_count is, so that fold_skip is measured again.
+int32_t fw_host_ig_pack_choice(int32_t mode, uint64_t mirror, uint64_t pushes_since_fold, uint64_t merge_launches,
+                               uint32_t ineligible) {
+    if (mode <= 0 || (ineligible & ~(uint32_t)FW_IGX_FOLD_ALWAYS)) return FW_IG_INGEST;
+    if (mode >= 2) return FW_IG_PACK;
+    if (ineligible & FW_IGX_FOLD_ALWAYS) return FW_IG_INGEST;  // (folds on every push as it is)
+    if (mirror == ~0ull || !(mirror & IGM_FOLD_SKIP) || !(mirror & IGM_PK_OK)) return FW_IG_INGEST;
+    if (merge_launches == 0) return FW_IG_INGEST;
+    if (pushes_since_fold >= (uint64_t)((mirror & IGM_SKEW) ? FW_IG_REFRESH_SKEW : FW_IG_REFRESH)) return FW_IG_FOLD;
+    return FW_IG_PACK;
 }
 
 int fw_host_time_op(const fw_config* cfg, int32_t what, int64_t x, int64_t* out) {

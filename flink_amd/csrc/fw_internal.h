@@ -108,7 +108,7 @@ constexpr bool ig_runs_fit(int n_isb, int block, int rpt, int nw) {
 // ---- k_ingest_pack (fw_ingest_pack.h): the early-packing ingest of PF_PACK pushes.  512 threads x 8
 // rows like k_ingest's narrow variant (same chunks, same cells), but a row is packed to its 8-B run
 // word as soon as it is routed, so a routed row holds 3 registers, and the LDS holds no fold table:
-// 64 VGPRs and 39 KiB, four workgroups per CU instead of two.
+// at most 80 VGPRs and 39 KiB, three workgroups per CU instead of two.
 constexpr int IGP_BLOCK = 512;
 constexpr int IGP_RPT = 8;
 constexpr int IGP_LDS = 39 * 1024;
@@ -282,11 +282,11 @@ struct Tickets {
     uint32_t c[2][TK_GROUPS + 1][32];
     uint32_t work[8][32];  // k_merge_fire: next superbucket of each XCD's share (reset by the last workgroup)
     // host-mapped word (nullptr: none) written after an ingest launch for the host's choice of the next
-    // push's ingest kernel: push_count << 8 | IGM_PK_OK | IGM_FOLD_SKIP as the push leaves them
+    // push's ingest kernel: push_count << 8 | IGM_SKEW | IGM_PK_OK | IGM_FOLD_SKIP as the push leaves them
     // (k_ingest_pack's last workgroup; k_ig_report behind a k_ingest launch)
     unsigned long long* ig_mirror;
 };
-constexpr unsigned long long IGM_FOLD_SKIP = 1, IGM_PK_OK = 2;  // Tickets::ig_mirror bits
+constexpr unsigned long long IGM_FOLD_SKIP = 1, IGM_PK_OK = 2, IGM_SKEW = 4;  // Tickets::ig_mirror bits
 
 struct Ctrl {
     int64_t cur;             // currentProgress == operator / timer-service watermark
@@ -305,9 +305,9 @@ struct Ctrl {
     int32_t push_slot;       // partial-buffer slot of the push being ingested
     uint64_t partials;       // partials written by the ingest kernels (cumulative)
     uint32_t fold_skip;      // k_ingest: the last pushes' LDS fold merged (almost) nothing -> skip it
-    uint32_t push_count;     // pushes ingested (every 8th one folds regardless, to re-measure)
+    uint32_t push_count;     // pushes ingested (k_ingest: every 8th one folds regardless, to re-measure)
     int32_t ovf_sel;         // live out_count
-    int32_t pad0;
+    int32_t ig_skew;         // k_ingest_pack's sampled fold estimate of its last push reached k_ingest's 2 % (IGM_SKEW)
     int64_t n_lfire;         // DataStream late-fire rows pending (EventTimeTrigger.onElement FIRE)
     int64_t n_side;          // DataStream late side-output rows since the last fw_late_records
     int64_t n_ordev;         // DataStream first-element retain / release events since the last read
@@ -543,7 +543,8 @@ struct IngestArgs {
     int32_t* slot_nch;     // [FW_MAX_PENDING] chunks of each pending push
     int64_t max_nch;       // cell_pad(chunks per slot): cells per superbucket per slot
     int64_t* chunk_stats;  // [n_chunks][CS_WORDS]: min target slice, dropped rows, accepted rows, partials,
-                           // partial bytes | compact << 40, -, -, -, key min / max, accumulator min / max
+                           // partial bytes | compact << 40, k_ingest_pack's sampled rows and the duplicates
+                           // among them, -, key min / max, accumulator min / max
     Tickets* tickets;
     int64_t n_chunks;
     int64_t* treq;         // timer requests: (key, window, sb) triples
@@ -561,7 +562,8 @@ struct IngestArgs {
     int32_t side_output;   // late side output instead of numLateRecordsDropped
     int32_t push_seq;      // fw_commit / fw_push_device call number (side-output rows)
     int64_t row0;          // row offset of this launch within its call
-    int32_t fold_always;   // development (FW_FOLD=1): fold every push (no adaptive skip)
+    int32_t fold_always;   // fold on this push whatever fold_skip says: FW_FOLD=1 (development: every push), and
+                           // the push on which a packing handle re-measures the fold (fw_api.hip)
     int32_t no_fold;       // minBy / maxBy: word pairs do not fold per word -- partials stay per element
     const int64_t* seg_counts;  // padded exchange buffer: valid rows per segment (nullptr: all valid)
     UDiv seg_div;          // divisor = segment length
@@ -583,6 +585,40 @@ struct IngestArgs {
     int32_t sub_cap;       // rows per sub-run
     int32_t pack;          // PF_PACK run rows allowed (runs, one integer word; fw_api.hip plans it)
 };
+// What k_ingest_pack reads of a push (launch_ingest_pack fills it from the IngestArgs the host builds,
+// which igp_serves checks): the kernel's scalar registers hold these and nothing of the window kinds,
+// word layouts and side outputs it does not serve.  The launch-uniform quotients and strides are
+// computed here once instead of per chunk.
+struct IngestPackArgs {
+    const int64_t* key;
+    const int64_t* ts;
+    const int64_t* val;
+    int64_t n;
+    Ctrl* ctrl;
+    Tickets* tickets;
+    int64_t* chunk_stats;
+    unsigned long long* kt;
+    uint64_t* parts;       // + slot * part_stride: the slot's chunk regions (PF_WIDE rows)
+    uint64_t* runs;        // + slot * run_stride: the slot's run rows
+    uint32_t* cells;       // + slot * cell_stride
+    uint32_t* run_fill;    // + slot * RUN_X * n_sb
+    uint32_t* run_ovf;     // + slot * n_sb
+    int64_t* slot_base;
+    int32_t* slot_nch;
+    int32_t* slot_fmt;
+    int64_t part_stride, run_stride, cell_stride;  // words per slot
+    int64_t interval, offset;  // TUMBLE, UTC: slice end = window_start(ts, offset, interval) + interval
+    int64_t back;          // (2^30 / interval) * interval: a chunk's 32-bit slice base lies this far below its first row
+    UDiv slice_div;
+    UDiv32 slice_div32;
+    UDiv32 maxp_div;       // routing (KeySpace)
+    int32_t max_p, kg_start, sb_log2, n_sb;
+    uint32_t rank_q;       // rank_lim / interval: ranks a row may have
+    uint32_t sub_cap;
+    int32_t can_pack;      // PF_PACK run rows are planned (pack, runs)
+    int32_t pad;
+};
+
 // Development ablations and phase stamps (FW_ABLATE) are compiled into the kernels only in a
 // diagnostic build (make DIAG=1): in the production build their checks fold away, so the hot loops
 // carry no scalar branches for them.

@@ -318,6 +318,12 @@ __device__ __forceinline__ int64_t wred_max_i64(int64_t v) {
 __device__ __forceinline__ uint32_t wred_sum_u32(uint32_t v) {
     return wred<uint32_t>(v, 0u, [](uint32_t a, uint32_t b) { return a + b; });
 }
+__device__ __forceinline__ uint32_t wred_min_u32(uint32_t v) {
+    return wred<uint32_t>(v, 0xFFFFFFFFu, [](uint32_t a, uint32_t b) { return a < b ? a : b; });
+}
+__device__ __forceinline__ uint32_t wred_max_u32(uint32_t v) {
+    return wred<uint32_t>(v, 0u, [](uint32_t a, uint32_t b) { return a > b ? a : b; });
+}
 __device__ __forceinline__ int64_t wred_sum_i64(int64_t v) {
     return wred<int64_t>(v, 0, [](int64_t a, int64_t b) { return a + b; });
 }
@@ -380,7 +386,7 @@ __device__ __forceinline__ void ig_mirror_store(const Tickets* tk, const Ctrl* c
     if (!mirror) return;
     __hip_atomic_store(mirror,
                        ((unsigned long long)ctrl->push_count << 8) | (ctrl->fold_skip ? IGM_FOLD_SKIP : 0ull) |
-                           ((ctrl->pk_next_bits & PK_OK) ? IGM_PK_OK : 0ull),
+                           ((ctrl->pk_next_bits & PK_OK) ? IGM_PK_OK : 0ull) | (ctrl->ig_skew ? IGM_SKEW : 0ull),
                        __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
 }
 

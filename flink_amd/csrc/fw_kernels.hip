@@ -108,6 +108,7 @@ __global__ void k_init_ctrl(Ctrl* c) {
         c->partials = 0;
         c->fold_skip = 0;
         c->push_count = 0;
+        c->ig_skew = 0;
         c->n_lfire = 0;
         c->n_side = 0;
         c->n_ordev = 0;

@@ -521,6 +521,27 @@ int fw_get_kernel_times(fw_handle* h, fw_kernel_times* out);
    such a handle).  h == NULL: over every handle of the process.  No device call. */
 int64_t fw_ingest_pack_launches(fw_handle* h);
 
+/* The host's choice of the ingest kernel for one push, as a pure function (no handle, no device call).
+   mode: FW_IG_PACK's value (0, 1, 2).  mirror: the word the last completed ingest launch reported
+   (push count << 8 | 4: the packing kernel's sampled fold estimate reached 2 % | 2: valid PF_PACK
+   fields | 1: the LDS fold is skipped; all ones: nothing reported yet).  pushes_since_fold: pushes
+   since the last one on which k_ingest folded, that one included.  merge_launches: merge launches since
+   the control block was initialised.  ineligible: FW_IGX_* bits of what keeps the push from
+   k_ingest_pack.  In mode 1 an eligible push goes to k_ingest while the mirror is invalid or lacks bit 1
+   or 2, while no merge has been launched, and (FW_IG_FOLD: told to fold and measure again) when
+   pushes_since_fold >= FW_IG_REFRESH, or >= FW_IG_REFRESH_SKEW with bit 4 set; every other push packs. */
+enum { FW_IG_INGEST = 0, FW_IG_PACK = 1, FW_IG_FOLD = 2 };
+enum { FW_IG_REFRESH = 64, FW_IG_REFRESH_SKEW = 8 };
+enum {
+    FW_IGX_PLAN = 1,        /* the handle's plan is not one k_ingest_pack serves */
+    FW_IGX_KEY_HASH = 2,    /* the push carries precomputed key hashes */
+    FW_IGX_SEGMENTS = 4,    /* padded exchange segments */
+    FW_IGX_STRIDE = 8,      /* packed rows (column stride != 1) */
+    FW_IGX_FOLD_ALWAYS = 16 /* FW_FOLD=1 (development): mode 1 keeps k_ingest, mode 2 packs */
+};
+int32_t fw_host_ig_pack_choice(int32_t mode, uint64_t mirror, uint64_t pushes_since_fold, uint64_t merge_launches,
+                               uint32_t ineligible);
+
 /* ---- checkpoint -------------------------------------------------------------------- */
 /* Flushes, then serialises watermark + state + timers.  *size receives the byte count;
    call with buf == NULL to query it. */
