@@ -139,6 +139,9 @@ int fw::set_error(int code, const char* fmt, ...) {
 
 // pushes k_ingest_pack took, over every handle of the process (fw_ingest_pack_launches(NULL))
 static std::atomic<int64_t> g_ig_pack_launches{0};
+// superbuckets the GF_TAG merge variants served on the old path [0] and on the tag path [1], over the
+// handles destroyed so far (fw_merge_path_superbuckets(NULL, .))
+static std::atomic<int64_t> g_mg_path[2];
 
 struct fw_handle {
     fw_config cfg;
@@ -311,6 +314,7 @@ struct fw_handle {
     int ig_pack_mode = 1;
     uint64_t ig_since_fold = 0;      // pushes since the last one on which k_ingest folded (that one included)
     uint64_t ig_merges = 0;          // merge launches since the control block was initialised
+    bool mg_tag = false;      // planned: the merge launches its GF_TAG variant (tag path for PF_PACK flushes)
     bool ig_pack_ok = false;  // planned: the handle's pushes are ones k_ingest_pack serves
     // ingest mirror: host-mapped word written after each ingest launch (Tickets::ig_mirror)
     volatile unsigned long long* ig_mirror = nullptr;
@@ -737,6 +741,10 @@ int validate_and_plan(fw_handle* h) {
         h->ig_pack_ok = h->pack && !h->narrow && c.window_kind == FW_WIN_TUMBLE && c.agg_phase != FW_PHASE_LOCAL &&
                         c.nullable_cols == 0 && ks.hash_kind != FW_KEYHASH_PRECOMPUTED && h->nv == 1 && op != W_CNT &&
                         ad.by_prev < 0 && ks.n_sb <= IGP_MAX_SB && h->chunk_rows == IGP_BLOCK * IGP_RPT;
+        // the merge's tag path serves the flushes of PF_PACK pushes of SQL TUMBLE handles that keep state
+        // (LOCAL emits partials instead); FW_MG_TAG=0 plans the plain variant (A/B)
+        const char* te = getenv("FW_MG_TAG");
+        h->mg_tag = h->pack && c.window_kind == FW_WIN_TUMBLE && c.agg_phase != FW_PHASE_LOCAL && !(te && atoi(te) == 0);
     }
     h->treq_cap = std::max<int64_t>(c.max_batch_rows * 2, 1 << 16);
     if (c.api == FW_API_DATASTREAM) {
@@ -842,6 +850,7 @@ int allocate(fw_handle* h) {
             h->run_rows = 0;
             h->sub_cap = 0;
             h->pack = 0;
+            h->mg_tag = false;
             h->ig_pack_ok = false;
         } else {
             h->runs = (uint64_t*)r;
@@ -1073,6 +1082,7 @@ MergeArgs merge_args(fw_handle* h, int64_t wm, int force) {
     a.slot_fmt = h->slot_fmt;
     a.run_rows = h->run_rows;
     a.sub_cap = h->sub_cap;
+    a.tag = h->mg_tag && h->pack && h->runs;
     a.ch_log2 = 0;
     while ((1ll << a.ch_log2) < h->chunk_rows) a.ch_log2++;
     return a;
@@ -1342,9 +1352,27 @@ int fw_create(const fw_config* cfg, fw_handle** out) {
     return FW_OK;
 }
 
+// the handle's superbuckets by merge path (Tickets::mg_path), after the launches queued so far
+static int read_mg_path(fw_handle* h, unsigned long long (&n)[2]) {
+    n[0] = n[1] = 0;
+    if (!h->tickets || !h->stream) return FW_OK;
+    HIP_TRY(hipMemcpyAsync(n, h->tickets->mg_path, sizeof n, hipMemcpyDeviceToHost, h->stream));
+    HIP_TRY(hipStreamSynchronize(h->stream));
+    return FW_OK;
+}
+
 int fw_destroy(fw_handle* h) {
     if (!h) return FW_OK;
     if (h->stream) hipStreamSynchronize(h->stream);
+    if (h->mg_tag) {
+        unsigned long long n[2];
+        if (read_mg_path(h, n) == FW_OK) {
+            g_mg_path[0].fetch_add((int64_t)n[0], std::memory_order_relaxed);
+            g_mg_path[1].fetch_add((int64_t)n[1], std::memory_order_relaxed);
+        } else {
+            (void)hipGetLastError();
+        }
+    }
     cw_free(&h->cw);
     sw_free(&h->sw);
     hipFree(h->ctrl);
@@ -2270,6 +2298,14 @@ int fw_set_profiling(fw_handle* h, int enable) {
 
 int64_t fw_ingest_pack_launches(fw_handle* h) {
     return h ? h->ig_pack_launches : g_ig_pack_launches.load(std::memory_order_relaxed);
+}
+
+int64_t fw_merge_path_superbuckets(fw_handle* h, int tag_path) {
+    const int i = tag_path ? 1 : 0;
+    if (!h) return g_mg_path[i].load(std::memory_order_relaxed);
+    unsigned long long n[2];
+    if (read_mg_path(h, n) != FW_OK) return -1;
+    return (int64_t)n[i];
 }
 
 int fw_get_kernel_times(fw_handle* h, fw_kernel_times* out) {

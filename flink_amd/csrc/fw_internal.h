@@ -55,6 +55,12 @@ constexpr int mg_entries(int nw, int kind) {
     if (kind == 4) return nw <= 1 ? 1536 : 768;  // KIND_HOPB: HB_R slots of nw words per entry
     return nw <= 1 ? (kind == FW_WIN_TUMBLE ? 3072 : 4096) : nw <= 4 ? 2048 : 1024;
 }
+// the tag-addressed table of the one-word TUMBLE merge's PF_PACK path (fw_merge_impl.h GF_TAG): slots
+// of a 4-B tag and an 8-B accumulator, 96 KB; at most mg_entries(1, TUMBLE) = 3072 of them hold a
+// group (37.5 %), and the tag (key offset << rb | rank) + 1 must fit 32 bits
+constexpr int MG_TAG_SLOTS = 8192;
+constexpr int MG_TAG_BITS = 31;
+constexpr int MG_TAG_RANKS = 256;               // 2^rb <= 256 ranks (pack_fields: rb <= 8)
 // LDS index slots of a table of E entries with NW accumulator words: a power of two, 4E when it
 // fits beside the entries in a workgroup's LDS, else the largest that does
 constexpr int mg_idx_slots(int nw, int e) {
@@ -285,6 +291,9 @@ struct Tickets {
     // push's ingest kernel: push_count << 8 | IGM_SKEW | IGM_PK_OK | IGM_FOLD_SKIP as the push leaves them
     // (k_ingest_pack's last workgroup; k_ig_report behind a k_ingest launch)
     unsigned long long* ig_mirror;
+    // k_merge_fire's GF_TAG variants: superbuckets with work served by the old path [0] and by the tag
+    // path [1] (cumulative; fw_merge_path_superbuckets)
+    unsigned long long mg_path[2];
 };
 constexpr unsigned long long IGM_FOLD_SKIP = 1, IGM_PK_OK = 2, IGM_SKEW = 4;  // Tickets::ig_mirror bits
 
@@ -704,6 +713,7 @@ struct MergeArgs {
     const int32_t* slot_fmt;
     int64_t run_rows;
     int32_t sub_cap;
+    int32_t tag;                // launch the GF_TAG variant (fw_api.hip plans it: PF_PACK handles, SQL TUMBLE, not LOCAL)
 };
 constexpr int64_t ORDEV_RELEASE = (int64_t)1 << 62;
 constexpr int LFW = 3 + MAX_WORDS;  // words per late-fire row

@@ -955,23 +955,20 @@ __device__ __forceinline__ RunSegs run_segs(const MergeArgs& a, int isb, int64_t
 // wave-uniform, so the segments a block touches are found with scalar reads of the lanes' segment
 // words (v_readlane): the block's first row by a scalar binary search, then the (few) segment
 // boundaries inside the block -- no per-row cross-lane shuffles.
-template <int NW, int GU, int GF>
-__device__ __forceinline__ uint32_t load_run_rows(const MergeArgs& a, const RunSegs& g, uint32_t r0_,
-                                                  uint64_t (&row)[GU][2 + NW]) {
-    constexpr int PW = 2 + NW;
-    constexpr bool CR = (GF & GF_COMPACT) != 0;
+// the segment search alone: ri[u] = the row's index in its push's run region, pf[u] = its segment's
+// push | format << 4
+template <int GU>
+__device__ __forceinline__ uint32_t locate_run_rows(const RunSegs& g, uint32_t r0_, uint32_t (&ri)[GU], uint32_t (&pf)[GU]) {
     const int lane = threadIdx.x & 63;
     const uint32_t r0 = (uint32_t)__builtin_amdgcn_readfirstlane((int)r0_);
     const uint32_t tot = (uint32_t)__builtin_amdgcn_readfirstlane((int)g.tot);
     const uint32_t last = min(r0 + (uint32_t)(64 * GU), tot) - 1u;  // the block's last row (tot > 0)
-    PackDec pk{};
-    if constexpr (CR && NW == 1) pk = pack_dec(a);
     const uint32_t first = min(r0, tot - 1u);  // a block past the end re-reads the last row
     int cur = 0;
 #pragma unroll
     for (int step = 32; step > 0; step >>= 1)
         if ((uint32_t)__builtin_amdgcn_readlane((int)g.excl, cur + step) <= first) cur += step;
-    uint32_t x[GU], adj[GU], pf[GU];
+    uint32_t x[GU], adj[GU];
     {
         const uint32_t a0 = (uint32_t)__builtin_amdgcn_readlane((int)g.adj, cur);
         const uint32_t p0 = (uint32_t)__builtin_amdgcn_readlane((int)g.pf, cur);
@@ -994,9 +991,26 @@ __device__ __forceinline__ uint32_t load_run_rows(const MergeArgs& a, const RunS
             pf[u] = x[u] >= b ? pn : pf[u];
         }
     }
+    uint32_t live = 0;
 #pragma unroll
     for (int u = 0; u < GU; u++) {
-        const uint32_t ri = adj[u] + x[u];  // row index in its push's run region
+        ri[u] = adj[u] + x[u];
+        live |= (uint32_t)(r0 + (uint32_t)(u * 64 + lane) < tot) << u;
+    }
+    return live;
+}
+template <int NW, int GU, int GF>
+__device__ __forceinline__ uint32_t load_run_rows(const MergeArgs& a, const RunSegs& g, uint32_t r0_,
+                                                  uint64_t (&row)[GU][2 + NW]) {
+    constexpr int PW = 2 + NW;
+    constexpr bool CR = (GF & GF_COMPACT) != 0;
+    PackDec pk{};
+    if constexpr (CR && NW == 1) pk = pack_dec(a);
+    uint32_t rix[GU], pf[GU];
+    const uint32_t live = locate_run_rows<GU>(g, r0_, rix, pf);
+#pragma unroll
+    for (int u = 0; u < GU; u++) {
+        const uint32_t ri = rix[u];  // row index in its push's run region
         const uint32_t p = pf[u] & 15u, fmt = (pf[u] >> 4) & 3u;
         const uint64_t* base = a.runs + (size_t)p * a.run_rows * PW;
         if (!CR || fmt == PF_WIDE) {
@@ -1023,9 +1037,6 @@ __device__ __forceinline__ uint32_t load_run_rows(const MergeArgs& a, const RunS
             }
         }
     }
-    uint32_t live = 0;
-#pragma unroll
-    for (int u = 0; u < GU; u++) live |= (uint32_t)(r0 + (uint32_t)(u * 64 + lane) < tot) << u;
     return live;
 }
 // every run row of superbucket sb's pending pushes through process(rows, live): waves take blocks of
@@ -1107,15 +1118,355 @@ __device__ __forceinline__ void gather_cells_push(const MergeArgs& a, int sb, in
     }
 }
 
-// GF: gather variant (GF_PASS: KeySpace.pass_log2 > 0, GF_COMPACT: compact partial rows)
+// ---- the tag path (GF_TAG): one-word SQL TUMBLE flushes whose pending pushes are all PF_PACK.
+// A PF_PACK row is (key - kbase) << (64 - kb) | rank << vb | (acc - vbase) with the epoch's bases and
+// widths, so word >> vb -- key offset and rank, kb + rb bits -- is the whole identity of its (key,
+// slice) group.  The LDS table is addressed by that tag: slot i holds tag[i] = (word >> vb) + 1
+// (0: empty) and acc[i], which starts at the word op's identity.  A row is one compare-and-swap on
+// the tag word (0 -> tag, returning what was there) and, when that was 0 or the tag itself, one
+// non-returning 64-bit atomic on acc[i]; else the next slot.  The fold is commutative and the slot
+// starts at the identity, so a fresh claim and a hit are the same two instructions: no entry
+// numbers, no "claiming" state, no publication order, no decode of the row and no 128-bit hash, and
+// a row in flight holds two registers instead of six.
+// Without timer requests, an entry's flags are a function of its slice alone (flags_of below: F_ACC,
+// plus F_TIMER unless the slice was fired when its rows were buffered), so the table keeps none:
+// ranks -- at most 2^rb slice ends -- have their slice end, flags and "due at W" computed once per
+// superbucket (rk_end / rk_flag).  The path runs only when every live state entry converts to a tag
+// with those flags (tag_superbucket returns false otherwise, before it has changed anything but LDS).
+constexpr int GF_TAG = 4;
+constexpr int MG_TAG_LOG2 = 13;
+static_assert((1 << MG_TAG_LOG2) == MG_TAG_SLOTS, "tag_slot's shift");
+constexpr uint32_t TG_DUE = 1u << 31;  // rk_flag: the rank's timer is due at this watermark
+// rows per lane per block and blocks in flight of the tag path's gather (the defaults are the
+// measured best; -DFW_TAG_G / -DFW_TAG_D build the other points of the sweep)
+#ifndef FW_TAG_G
+#define FW_TAG_G 4
+#endif
+#ifndef FW_TAG_D
+#define FW_TAG_D 1
+#endif
+struct TagLds {
+    uint32_t tag[MG_TAG_SLOTS];
+    uint64_t acc[MG_TAG_SLOTS];
+    int64_t rk_end[MG_TAG_RANKS];
+    uint32_t rk_flag[MG_TAG_RANKS];
+    uint16_t due[MG_TAG_SLOTS];   // slots of the groups whose timer is due at this watermark
+    uint16_t live[MG_TAG_SLOTS];  // slots of the groups written back, in state order
+    uint32_t ndue, nlive;
+    uint32_t nfresh;    // groups the gather created
+    uint32_t overflow;
+};
+// what a launch's tag-path superbuckets share (uniform; read once per workgroup): the flush epoch's
+// PF_PACK fields and bases, and whether the launch's flush can take the path at all
+struct TagEpoch {
+    uint32_t bits;
+    bool ok;
+    int64_t kbase, vbase, rbase;
+};
+// the merge kernel's LDS: the entry table, and for the GF_TAG variants the tag table in the same bytes
+template <int NW, int E, bool TAG>
+struct MergeLds {
+    StateLds<NW, E> S;
+};
+template <int NW, int E>
+struct MergeLds<NW, E, true> {
+    union {
+        StateLds<NW, E> S;
+        TagLds T;
+    };
+};
+// home slot of a tag: 32-bit multiplicative hash, the top bits
+__device__ __forceinline__ uint32_t tag_slot(uint32_t tg) { return (tg * 0x9E3779B1u) >> (32 - MG_TAG_LOG2); }
+
+// (uniform) may this launch's flush take the tag path: every pending push wrote PF_PACK run rows under
+// valid fields whose key and rank bits fit a tag.  (Per superbucket: no chunk kept rows of it in its own
+// region -- PF_WIDE rows, or rows past sub_cap -- see the kernel.)
+__device__ __forceinline__ TagEpoch tag_epoch(const MergeArgs& a, int64_t pend, bool flush) {
+    TagEpoch ep;
+    ep.bits = __hip_atomic_load(&a.ctrl->pk_cur_bits, __ATOMIC_RELAXED, DEV_SCOPE);
+    ep.kbase = __hip_atomic_load(&a.ctrl->pk_cur_k, __ATOMIC_RELAXED, DEV_SCOPE);
+    ep.vbase = __hip_atomic_load(&a.ctrl->pk_cur_v, __ATOMIC_RELAXED, DEV_SCOPE);
+    ep.rbase = a.slot_base[0];
+    bool pack = flush && (ep.bits & PK_OK) && (ep.bits & 255u) + ((ep.bits >> 8) & 255u) <= (uint32_t)MG_TAG_BITS;
+    for (int p = 0; p < FW_MAX_PENDING; p++)
+        if (p < pend) pack &= (uint32_t)a.slot_fmt[p] == PF_PACK;
+    ep.ok = pack;
+    return ep;
+}
+
+// the 8-byte words of rows r0 + u * 64 + lane of the segments (load_run_rows' rows, PF_PACK runs)
+template <int G>
+__device__ __forceinline__ uint32_t load_run_words(const MergeArgs& a, const RunSegs& g, uint32_t r0, uint64_t (&w)[G]) {
+    uint32_t ri[G], pf[G];
+    const uint32_t live = locate_run_rows<G>(g, r0, ri, pf);
+#pragma unroll
+    for (int u = 0; u < G; u++) w[u] = a.runs[(size_t)(pf[u] & 15u) * a.run_rows * 3 + ri[u]];  // (a slot holds run_rows PF_WIDE rows)
+    return live;
+}
+
+// One superbucket's flush and fire on the tag path; every thread of the workgroup calls it.  False:
+// a live state entry does not convert (its key or slice lies outside the epoch's fields, or its flags
+// are not the ones its slice implies) -- nothing but LDS has changed, the caller takes the old path.
+template <uint32_t OPS, int G, int D>
+__device__ __forceinline__ bool tag_superbucket(const MergeArgs& a, TagLds& T, int sb, int32_t n0, int64_t pend, int64_t W,
+                                                int64_t w_old, bool do_fire, const TagEpoch& ep, Stamps& stm, int32_t* s_emit,
+                                                int64_t* s_newmin) {
+    constexpr int E = mg_entries(1, FW_WIN_TUMBLE);
+    constexpr uint32_t MASK = MG_TAG_SLOTS - 1;
+    constexpr int32_t OP = (int32_t)(OPS & 15u);
+    const int tid = threadIdx.x;
+    const uint32_t kb = ep.bits & 255u, rb = (ep.bits >> 8) & 255u, vb = (ep.bits >> 16) & 255u;
+    const int64_t kbase = ep.kbase, vbase = ep.vbase, rbase = ep.rbase;
+    const int64_t interval = a.win.interval;
+    // this thread's first state entry, in flight while the table is cleared
+    const uint64_t* st = a.state + (size_t)sb * a.cap_e * 4;
+    uint64_t p[4] = {0, 0, 0, 0};
+    if (tid < n0) load_words<4>(st + (size_t)tid * 4, p);
+    auto claim = [&](uint32_t s, uint32_t tg) -> uint32_t {  // what slot s held: 0 (now tg), tg, or another tag
+        uint32_t was = 0;
+        __hip_atomic_compare_exchange_strong(&T.tag[s], &was, tg, __ATOMIC_RELAXED, __ATOMIC_RELAXED, LDS_SCOPE);
+        return was;
+    };
+    // ---- clear the table (16-byte LDS stores), the ranks' slice ends and flags
+    for (int i = tid; i < MG_TAG_SLOTS / 4; i += MG_BLOCK) ((uint4*)T.tag)[i] = make_uint4(0u, 0u, 0u, 0u);
+    for (int i = tid; i < MG_TAG_SLOTS / 2; i += MG_BLOCK)
+        ((ulonglong2*)T.acc)[i] = make_ulonglong2(word_identity(OP), word_identity(OP));
+    if (tid < MG_TAG_RANKS) {
+        // the gather's flags_of (UTC, not LOCAL): the window timer unless already fired (AggCombiner.java:103-110)
+        const int64_t end = wadd(rbase, (int64_t)tid * interval);
+        const uint32_t fl = is_fired(end, w_old) ? F_ACC : (F_ACC | F_TIMER);
+        T.rk_end[tid] = end;
+        T.rk_flag[tid] = fl | ((do_fire && (fl & F_TIMER) && is_fired(end, W)) ? TG_DUE : 0u);
+    }
+    if (tid == 0) {
+        T.nfresh = 0;
+        T.overflow = 0;
+        T.ndue = 0;
+        T.nlive = 0;
+        *s_newmin = INT64_MAX;
+    }
+    __syncthreads();
+    // ---- state load: each live entry to its tag; entries are distinct, so a claim only loops on collisions
+    {
+        const uint64_t span = (uint64_t)interval << rb;
+        bool bad = false;
+        for (int e = tid; e < n0; e += MG_BLOCK) {
+            if (e != tid) load_words<4>(st + (size_t)e * 4, p);
+            const uint64_t ko = p[0] - (uint64_t)kbase, d = p[1] - (uint64_t)rbase;
+            const uint64_t r = udiv(d, a.win.slice_div);
+            if (!(ko < (1ull << kb) && d < span && r * (uint64_t)interval == d && p[2] == (uint64_t)(F_ACC | F_TIMER) &&
+                  !is_fired((int64_t)p[1], w_old))) {
+                bad = true;
+                continue;
+            }
+            const uint32_t tg = (((uint32_t)ko << rb) | (uint32_t)r) + 1u;
+            uint32_t s = tag_slot(tg);
+            while (claim(s, tg) != 0) s = (s + 1) & MASK;  // (n0 <= E < MG_TAG_SLOTS: an empty slot exists)
+            T.acc[s] = p[3];
+        }
+        if (__syncthreads_or(bad)) return false;
+    }
+    stm.mark(0);
+    // ---- gather: the run rows' words, G per lane per block (run_segs / locate_run_rows as the old path)
+    {
+        const bool gst = (FW_ABL(a) & AB_GSTAMPS) && stm.on && tid == 0;  // diagnostic: [2] rows ready, [4] claims, [7] folds + probing, [13] the loop
+        uint64_t g0 = gst ? __builtin_amdgcn_s_memtime() : 0;
+        const uint64_t gl0 = g0;
+        auto gstamp = [&](int i, bool vm) {
+            if (!gst) return;
+            if (vm) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+            else asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+            const uint64_t g1 = __builtin_amdgcn_s_memtime();
+            stm.acc[i] += g1 - g0;
+            g0 = g1;
+        };
+        const uint64_t vmask = (1ull << vb) - 1ull;
+        uint32_t nfr = 0;  // groups this lane created
+        auto fold_words = [&](uint64_t (&w)[G], uint32_t live) __attribute__((always_inline)) {
+            gstamp(2, true);
+            uint32_t tg[G], sl[G], was[G];
+#pragma unroll
+            for (int u = 0; u < G; u++) {
+                tg[u] = (uint32_t)(w[u] >> vb) + 1u;
+                sl[u] = tag_slot(tg[u]);
+            }
+#pragma unroll
+            for (int u = 0; u < G; u++) was[u] = ((live >> u) & 1u) ? claim(sl[u], tg[u]) : tg[u];
+            gstamp(4, false);
+            uint32_t rest = 0;
+#pragma unroll
+            for (int u = 0; u < G; u++) {
+                if (!((live >> u) & 1u)) continue;
+                if (was[u] == 0 || was[u] == tg[u]) {
+                    lds_fold(OP, &T.acc[sl[u]], (uint64_t)vbase + (w[u] & vmask));
+                    nfr += was[u] == 0;
+                } else {
+                    rest |= 1u << u;
+                }
+            }
+            while (rest) {  // home slot taken by another group: linear probing, a lane's rows one at a time
+                const int um = __ffs(rest) - 1;
+                rest &= rest - 1;
+                uint64_t ww = 0;
+                uint32_t t = 0, s = 0;
+                static_for<G>([&](auto UU) {
+                    constexpr int u = decltype(UU)::value;
+                    if (u == um) {
+                        ww = w[u];
+                        t = tg[u];
+                        s = sl[u];
+                    }
+                });
+                for (int probes = 1;; probes++) {
+                    s = (s + 1) & MASK;
+                    const uint32_t o = claim(s, t);
+                    if (o == 0 || o == t) {
+                        lds_fold(OP, &T.acc[s], (uint64_t)vbase + (ww & vmask));
+                        nfr += o == 0;
+                        break;
+                    }
+                    if (probes >= MG_TAG_SLOTS) {  // the table is full of other groups: the row is dropped (ERR_STATE)
+                        T.overflow = 1;
+                        break;
+                    }
+                }
+            }
+            gstamp(7, false);
+        };
+        constexpr uint32_t STEP = (uint32_t)MG_BLOCK * G;
+        const RunSegs g = run_segs(a, sb, pend);
+        uint32_t r0 = (uint32_t)(tid >> 6) * 64u * G;
+        if (r0 < g.tot) {  // (wave-uniform)
+            if constexpr (D > 1) {  // a ring of D blocks, as gather_runs
+                uint64_t buf[D][G];
+                uint32_t live[D];
+                static_for<D - 1>([&](auto K) {
+                    constexpr int k = decltype(K)::value;
+                    live[k] = load_run_words<G>(a, g, r0 + (uint32_t)k * STEP, buf[k]);
+                });
+                bool done = false;
+                while (!done) {
+                    static_for<D>([&](auto K) {
+                        constexpr int k = decltype(K)::value;
+                        constexpr int kn = (k + D - 1) % D;
+                        if (done) return;
+                        live[kn] = load_run_words<G>(a, g, r0 + (uint32_t)(D - 1) * STEP, buf[kn]);
+                        fold_words(buf[k], live[k]);
+                        r0 += STEP;
+                        done = r0 >= g.tot;
+                    });
+                }
+            } else {
+                for (; r0 < g.tot; r0 += STEP) {
+                    uint64_t w[G];
+                    const uint32_t live = load_run_words<G>(a, g, r0, w);
+                    fold_words(w, live);
+                }
+            }
+            // the groups created: one LDS add per wave (no row needs an entry number)
+            nfr = wred_sum_u32(nfr);
+            if ((tid & 63) == 0 && nfr) __hip_atomic_fetch_add(&T.nfresh, nfr, __ATOMIC_RELAXED, LDS_SCOPE);
+        }
+        if (gst) stm.acc[13] += __builtin_amdgcn_s_memtime() - gl0;
+    }
+    __syncthreads();
+    stm.mark(1);
+    run_release(a, sb, pend);
+    // ---- the groups by what becomes of them.  One pass over the slots, MG_TAG_SLOTS / MG_BLOCK per
+    // thread (a wave's lanes read consecutive slots), lists the due groups and the others (two LDS adds
+    // per wave); the fire and the write-back then run over dense lists, every lane busy.  (A single
+    // pass that emitted or wrote back each slot as it met it claimed a row per slot and branch with the
+    // waves a quarter full: measured 138 M cycles against 82 M for the old path's fire and write-back.)
+    const uint32_t n_ent = (uint32_t)n0 + T.nfresh;
+    const uint32_t rmask = (1u << rb) - 1u;
+    {
+        constexpr int PER = MG_TAG_SLOTS / MG_BLOCK;
+        uint32_t tgs[PER];
+#pragma unroll
+        for (int j = 0; j < PER; j++) tgs[j] = T.tag[j * MG_BLOCK + tid];
+        uint32_t isdue = 0, islive = 0, nd = 0, nl = 0;
+        uint64_t bd[PER], bl[PER];
+#pragma unroll
+        for (int j = 0; j < PER; j++) {
+            const uint32_t fl = tgs[j] ? T.rk_flag[(tgs[j] - 1u) & rmask] : 0u;
+            isdue |= (uint32_t)((fl & TG_DUE) != 0) << j;
+            islive |= (uint32_t)(fl != 0 && !(fl & TG_DUE)) << j;
+            bd[j] = __ballot((isdue >> j) & 1u);
+            bl[j] = __ballot((islive >> j) & 1u);
+            nd += (uint32_t)__popcll(bd[j]);
+            nl += (uint32_t)__popcll(bl[j]);
+        }
+        uint32_t d0 = 0, l0 = 0;
+        if ((tid & 63) == 0) {
+            if (nd) d0 = __hip_atomic_fetch_add(&T.ndue, nd, __ATOMIC_RELAXED, LDS_SCOPE);
+            if (nl) l0 = __hip_atomic_fetch_add(&T.nlive, nl, __ATOMIC_RELAXED, LDS_SCOPE);
+        }
+        d0 = uni32(d0);
+        l0 = uni32(l0);
+#pragma unroll
+        for (int j = 0; j < PER; j++) {
+            const uint32_t rd = __builtin_amdgcn_mbcnt_hi((uint32_t)(bd[j] >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)bd[j], 0u));
+            const uint32_t rl = __builtin_amdgcn_mbcnt_hi((uint32_t)(bl[j] >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)bl[j], 0u));
+            if ((isdue >> j) & 1u) T.due[d0 + rd] = (uint16_t)(j * MG_BLOCK + tid);
+            if ((islive >> j) & 1u) T.live[l0 + rl] = (uint16_t)(j * MG_BLOCK + tid);
+            d0 += (uint32_t)__popcll(bd[j]);
+            l0 += (uint32_t)__popcll(bl[j]);
+        }
+    }
+    __syncthreads();
+    stm.mark(6);
+    // ---- fire (fire_tumble: fireWindow + clearWindow of every due group), then the write-back of the
+    // others in the state's entry format
+    const uint32_t ndue = T.ndue, nlive = min(T.nlive, (uint32_t)a.cap_e);  // (beyond cap_e: ERR_STATE below)
+    for (uint32_t q = tid; q < ndue; q += MG_BLOCK) {
+        const uint32_t sl = T.due[q], x = T.tag[sl] - 1u;
+        uint64_t acc[1] = {T.acc[sl]};
+        if (a.ad.count_star_word < 0 || acc[0] != 0)
+            emit_row<1, false>(a, sb, s_emit, wadd(kbase, (int64_t)(x >> rb)), T.rk_end[x & rmask], acc);
+    }
+    stm.mark(5);  // (no barrier: thread 0's wave)
+    {
+        uint64_t* so = a.state + (size_t)sb * a.cap_e * 4;
+        int64_t lnm = INT64_MAX;
+        for (uint32_t q = tid; q < nlive; q += MG_BLOCK) {
+            const uint32_t sl = T.live[q], x = T.tag[sl] - 1u, fl = T.rk_flag[x & rmask];
+            const int64_t end = T.rk_end[x & rmask];
+            st16(so + (size_t)q * 4, (uint64_t)wadd(kbase, (int64_t)(x >> rb)), (uint64_t)end);
+            st16(so + (size_t)q * 4 + 2, (uint64_t)(fl & (F_ACC | F_TIMER)), T.acc[sl]);
+            if (fl & F_TIMER) lnm = min(lnm, end);
+        }
+        lnm = wred_min_i64(lnm);
+        if ((tid & 63) == 0 && lnm != INT64_MAX) __hip_atomic_fetch_min(s_newmin, lnm, __ATOMIC_RELAXED, LDS_SCOPE);
+    }
+    __syncthreads();
+    if (tid == 0) {
+        a.state_count[sb] = (int32_t)nlive;
+        a.sb_min_timer[sb] = *s_newmin;
+        a.sb_out[sb] = (int32_t)min((int64_t)*s_emit, a.slab_cap);
+        if (ndue) a.sb_fired[sb] += ndue;
+        __hip_atomic_fetch_add(&a.ctrl->state_moved, (uint64_t)(n0 + (int32_t)nlive), __ATOMIC_RELAXED, DEV_SCOPE);
+        __hip_atomic_fetch_max(&a.ctrl->peak_entries, (uint64_t)n_ent, __ATOMIC_RELAXED, DEV_SCOPE);
+        if (T.overflow || n_ent > (uint32_t)E) __hip_atomic_fetch_or(&a.ctrl->error, ERR_STATE, __ATOMIC_RELAXED, DEV_SCOPE);
+    }
+    __syncthreads();
+    stm.mark(3);
+    return true;
+}
+
+// GF: gather variant (GF_PASS: KeySpace.pass_log2 > 0, GF_COMPACT: compact partial rows, GF_TAG: the
+// tag path for PF_PACK flushes beside the old one)
 template <int NW, int E, bool Q, int KIND, uint32_t OPS, int GF>
 __global__ __launch_bounds__(MG_BLOCK, 4) void k_merge_fire(MergeArgs a) {
     constexpr bool PS = (GF & GF_PASS) != 0;
+    constexpr bool TAG = (GF & GF_TAG) != 0;
+    static_assert(!TAG || (NW == 1 && KIND == FW_WIN_TUMBLE && !Q && !PS && OPS != OPS_ANY && E == mg_entries(1, FW_WIN_TUMBLE)),
+                  "the tag path serves the one-word SQL TUMBLE layouts");
     constexpr int PW = 2 + NW;
     constexpr int PWE = 3 + NW;
     const int64_t CH = a.chunk_rows;  // chunk rows of the ingest kernel that wrote the cells
     constexpr int GU = mg_rows_in_flight(NW);
-    __shared__ StateLds<NW, E> S;
+    __shared__ MergeLds<NW, E, TAG> lds;
+    StateLds<NW, E>& S = lds.S;
     __shared__ int32_t s_work;
     __shared__ int32_t s_nlive;
     __shared__ int64_t s_newmin;
@@ -1141,6 +1492,11 @@ __global__ __launch_bounds__(MG_BLOCK, 4) void k_merge_fire(MergeArgs a) {
 
     Stamps stm;
     stm.init((FW_ABL(a) & AB_STAMPS) != 0);
+    // GF_TAG: the flush epoch's PF_PACK fields and bases, and this workgroup's superbuckets by path
+    // (no timer requests: their entries carry F_TIMER without F_ACC; no ablation but the stamps)
+    TagEpoch tep{};
+    uint32_t n_by_path[2] = {0, 0};
+    if constexpr (TAG) tep = tag_epoch(a, pend, do_flush && ntreq == 0 && !(FW_ABL(a) & ~(AB_STAMPS | AB_GSTAMPS)));
     // Persistent workgroups (one per CU: the LDS table fills it) pull superbuckets from a work
     // counter per XCD (the dispatcher deals blocks to XCDs round robin, block b to XCD b % 8), each
     // XCD owning a contiguous eighth of the superbuckets so their cells share its L2.  A launch
@@ -1169,6 +1525,11 @@ __global__ __launch_bounds__(MG_BLOCK, 4) void k_merge_fire(MergeArgs a) {
     for (int tk = s_tk; tk < nq; tk = s_tk) {
     const int sb = qbase + tk;
     const int32_t n0 = a.state_count[sb];
+    // GF_TAG: the pushes in which a chunk kept rows of sb in its own region (run_overflow), loaded here
+    // so that the path is known when the barriers below have passed
+    uint32_t ovf_w = 0;
+    if constexpr (TAG)
+        if (tep.ok && (tid & 63) < pend) ovf_w = a.run_ovf[(size_t)(tid & 63) * a.n_sb + sb];
     __syncthreads();  // every thread has read s_tk; the previous superbucket is done with the LDS
     if (tid == 0) {
         s_tk = (int32_t)__hip_atomic_fetch_add(wq, 1u, __ATOMIC_RELAXED, DEV_SCOPE);  // the next one
@@ -1179,6 +1540,15 @@ __global__ __launch_bounds__(MG_BLOCK, 4) void k_merge_fire(MergeArgs a) {
     }
     __syncthreads();
     if (!s_work) continue;
+    if constexpr (TAG) {
+        // the tag path, chosen per superbucket (every wave read the same flags): a flush of PF_PACK runs
+        // alone; a state entry that does not convert sends the superbucket back here, to the old path
+        const bool tagp = tep.ok && __ballot(ovf_w != 0) == 0;
+        const bool served = tagp && tag_superbucket<OPS, FW_TAG_G, FW_TAG_D>(a, lds.T, sb, n0, pend, W, w_old, do_fire, tep, stm,
+                                                                              &s_emit, &s_newmin);
+        n_by_path[served]++;
+        if (served) continue;
+    }
     const bool gather = do_flush && !(FW_ABL(a) & AB_M_NO_GATHER);
     // this thread's first cell word, loaded while the state loads (the gather below walks the
     // cells of every pending push, one cell per thread per pass, in flat tile order f:
@@ -1831,6 +2201,10 @@ __global__ __launch_bounds__(MG_BLOCK, 4) void k_merge_fire(MergeArgs a) {
     __syncthreads();
     stm.mark(3);
     }  // superbuckets of this workgroup (s_tk was published before the last barrier)
+    if constexpr (TAG) {
+        if (tid == 0 && n_by_path[0]) atomicAdd(&a.tickets->mg_path[0], (unsigned long long)n_by_path[0]);
+        if (tid == 0 && n_by_path[1]) atomicAdd(&a.tickets->mg_path[1], (unsigned long long)n_by_path[1]);
+    }
     stm.flush(a.stamps);
     merge_ticket(a, W);
 }
@@ -1884,6 +2258,14 @@ static bool merge_layout_launch(const MergeArgs& a, uint32_t lay, hipStream_t s)
         if (L != OPS_ANY && lay == L) {
             // compact rows come with the one-word layouts (fw_api.hip plans narrow for them alone)
             if constexpr (NW == 1) {
+                // the PF_PACK layouts (integer words) of SQL TUMBLE also carry the tag path (fw_api.hip plans a.tag)
+                if constexpr (L != ops_pack({W_SUM_F})) {
+                    if (a.compact && a.tag && a.win.kind == FW_WIN_TUMBLE) {
+                        hipLaunchKernelGGL((k_merge_fire<NW, mg_entries(NW, FW_WIN_TUMBLE), false, FW_WIN_TUMBLE, L, GF_COMPACT | GF_TAG>),
+                                           dim3(merge_grid(a.n_sb)), dim3(MG_BLOCK), 0, s, a);
+                        return true;
+                    }
+                }
                 if (a.compact) {
                     merge_launch<NW, false, L, GF_COMPACT>(a, s);
                     return true;

@@ -437,6 +437,10 @@ class WindowAggHandle:
         """Ingest launches of this handle the early-packing kernel (k_ingest_pack) took."""
         return int(lib().fw_ingest_pack_launches(self._h))
 
+    def merge_path_superbuckets(self):
+        """(entry-table path, tag path): superbuckets this handle's merge launches served on each."""
+        return tuple(int(lib().fw_merge_path_superbuckets(self._h, t)) for t in (0, 1))
+
     def kernel_times(self):
         """{kind: (ms, launches)} accumulated since set_profiling(True)."""
         t = abi.fw_kernel_times()

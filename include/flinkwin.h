@@ -520,6 +520,12 @@ int fw_get_kernel_times(fw_handle* h, fw_kernel_times* out);
    with one NOT NULL integer aggregate; FW_IG_PACK=0 never, 1 by the last push's report, 2 on every push of
    such a handle).  h == NULL: over every handle of the process.  No device call. */
 int64_t fw_ingest_pack_launches(fw_handle* h);
+/* Superbuckets with work that the merge launches of a PF_PACK handle (SQL TUMBLE, one integer aggregate,
+   not the LOCAL phase) served on the tag path (tag_path != 0: flushes whose pending pushes are all
+   PF_PACK and whose state converts) or on the entry-table path (tag_path == 0), cumulative.  Other
+   handles, and every handle under FW_MG_TAG=0, count nothing.  Synchronises the handle stream; -1 on a
+   device error.  h == NULL: over the handles destroyed so far, no device call. */
+int64_t fw_merge_path_superbuckets(fw_handle* h, int tag_path);
 
 /* The host's choice of the ingest kernel for one push, as a pure function (no handle, no device call).
    mode: FW_IG_PACK's value (0, 1, 2).  mirror: the word the last completed ingest launch reported
