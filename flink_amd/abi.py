@@ -307,3 +307,39 @@ def result_is_double(kind, typ):
     if kind in (AGG_COUNT_STAR, AGG_COUNT):
         return False
     return typ == T_F64
+
+
+# ---- host entry points of a SQL session configuration (FW_WIN_SESSION with API_SQL): the arithmetic
+# the session kernels run, without a device
+def host_sql_session_words(cfg):
+    """fw_host_sql_session_words: the accumulator words per session the plan of ``cfg`` uses."""
+    from . import _native
+    nw = C.c_int32()
+    _native.check(_native.lib().fw_host_sql_session_words(C.byref(cfg), C.byref(nw)))
+    return nw.value
+
+
+def host_sql_session_add(cfg, watermark, ts, values, nulls, starts, ends, acc_words, n, capacity):
+    """fw_host_sql_session_add: one row (``values`` / ``nulls`` per value column, int64 bit patterns
+    and 0 / 1 flags) of one key against that key's ``n`` sorted sessions held in the ctypes arrays
+    ``starts`` / ``ends`` (int64 * capacity) and ``acc_words`` (int64 * (capacity * words)).
+    Returns (outcome, n): outcome 1 kept, 0 dropped as late.  Raises FlinkWinError (FW_E_CAPACITY)
+    when a new session does not fit."""
+    from . import _native
+    nv = max(cfg.n_value_cols, 1)
+    v = (C.c_int64 * nv)(*[int(x) for x in values])
+    f = (C.c_uint8 * nv)(*[1 if x else 0 for x in nulls])
+    cnt, out = C.c_int32(n), C.c_int32()
+    _native.check(_native.lib().fw_host_sql_session_add(C.byref(cfg), int(watermark), int(ts), v, f, starts, ends, acc_words,
+                                                        C.byref(cnt), capacity, C.byref(out)))
+    return out.value, cnt.value
+
+
+def host_sql_session_result(cfg, acc_words):
+    """fw_host_sql_session_result: (values per aggregate as int64 bit patterns, null mask) of one
+    session's accumulator words."""
+    from . import _native
+    w = (C.c_int64 * len(acc_words))(*[int(x) for x in acc_words])
+    vals, nm = (C.c_int64 * FW_MAX_AGGS)(), C.c_uint32()
+    _native.check(_native.lib().fw_host_sql_session_result(C.byref(cfg), w, vals, C.byref(nm)))
+    return list(vals)[:cfg.n_aggs], nm.value

@@ -327,133 +327,28 @@ struct fw_handle {
     int kt_device = 0;                     // fw_set_profiling(FW_PROF_DEVICE) is on
 };
 
-namespace {
-
-int validate_and_plan(fw_handle* h) {
-    const fw_config& c = h->cfg;
-    if (c.abi_version != FW_ABI_VERSION) return fail(FW_E_INVALID, "abi_version %d != %d", c.abi_version, FW_ABI_VERSION);
-    if (c.api != FW_API_SQL && c.api != FW_API_DATASTREAM) return fail(FW_E_INVALID, "bad api %d", c.api);
-    if (c.n_aggs < 1 || c.n_aggs > FW_MAX_AGGS) return fail(FW_E_INVALID, "n_aggs %d out of range", c.n_aggs);
-    if (c.n_value_cols < 0 || c.n_value_cols > FW_MAX_COLS) return fail(FW_E_INVALID, "n_value_cols out of range");
-    if (c.max_parallelism < 1 || c.max_parallelism > 32768) return fail(FW_E_INVALID, "max_parallelism out of range");
-    if (c.parallelism < 1 || c.parallelism > c.max_parallelism) return fail(FW_E_INVALID, "parallelism out of range");
-    if (c.subtask_index < 0 || c.subtask_index >= c.parallelism) return fail(FW_E_INVALID, "subtask_index out of range");
-    if (c.key_hash < FW_KEYHASH_LONG || c.key_hash > FW_KEYHASH_KEYROW) return fail(FW_E_INVALID, "bad key_hash");
-    if (c.window_kind == FW_WIN_COUNT) {  // count windows: a plan of their own (fw_count.hip)
-        int rc = cw_plan(c, &h->cw);
-        if (rc) return rc;
-        h->ks = h->cw.ks;
-        h->nv = h->cw.is_count ? 0 : 1;
-        h->slot_col[0] = h->cw.val_col;
-        h->n_out = 1;
-        h->out_cap = c.output_capacity;
-        h->stage_cap = c.max_batch_rows;
-        return FW_OK;
-    }
-    if (c.window_kind == FW_WIN_SESSION) {  // session windows: a plan of their own (fw_session.hip)
-        int rc = sw_plan(c, &h->sw);
-        if (rc) return rc;
-        h->ks = h->sw.ks;
-        h->nv = h->sw.d.is_count ? 0 : 1;
-        h->slot_col[0] = h->sw.val_col;
-        h->n_out = 1;
-        h->out_cap = c.output_capacity;
-        h->stage_cap = c.max_batch_rows;
-        return FW_OK;
-    }
-    h->keyrow = c.key_hash == FW_KEYHASH_KEYROW;
-    if (h->keyrow) {
-        if (c.api != FW_API_SQL) return fail(FW_E_INVALID, "key rows (FW_KEYHASH_KEYROW) are SQL keys");
-        const int32_t mb = c.key_row_max_bytes ? c.key_row_max_bytes : 120;  // 120: one 128-B line per id
-        if (mb < 16 || mb > 4096 || (mb & 7)) return fail(FW_E_INVALID, "key_row_max_bytes must be a multiple of 8 in [16, 4096]");
-        h->kr.stride_words = (int32_t)(((8 + mb) + 127) / 128 * 16);  // meta word + image, whole 128-B lines
-        h->kr.max_len = mb;
-    }
-    if (c.size_ms <= 0) return fail(FW_E_INVALID, "window size must be > 0");
-    // ---- window (SliceAssigners constructors' argument checks)
-    WinDesc& w = h->win;
-    w.kind = c.window_kind;
-    w.size = c.size_ms;
-    w.offset = c.offset_ms;
-    switch (c.window_kind) {
-        case FW_WIN_TUMBLE:
-            if (!(c.offset_ms > -c.size_ms && c.offset_ms < c.size_ms))
-                return fail(FW_E_INVALID, "Tumbling Window parameters must satisfy abs(offset) < size");
-            w.interval = c.size_ms;
-            w.n_slices = 1;
-            if (c.api == FW_API_DATASTREAM) w.offset = c.offset_ms % c.size_ms;
-            break;
-        case FW_WIN_HOP:
-            if (c.slide_ms <= 0) return fail(FW_E_INVALID, "Hopping Window must satisfy slide > 0 and size > 0");
-            // SQL slices need slide | size (SliceAssigners.HoppingSliceAssigner); DataStream sliding
-            // windows do not (SlidingEventTimeWindows.java:77-90): panes of gcd(size, slide) ms, each in
-            // floor or ceil(size / slide) windows
-            if (c.api != FW_API_DATASTREAM && c.size_ms % c.slide_ms != 0)
-                return fail(FW_E_INVALID, "Slicing Hopping Window requires size must be an integral multiple of slide");
-            if (c.api == FW_API_DATASTREAM && c.size_ms < c.slide_ms)  // gaps: panes in no window (not eligible)
-                return fail(FW_E_INVALID, "sliding windows with size < slide run on the reference operator");
-            if (c.api == FW_API_DATASTREAM && !(c.offset_ms > -c.slide_ms && c.offset_ms < c.slide_ms))
-                return fail(FW_E_INVALID, "SlidingEventTimeWindows parameters must satisfy abs(offset) < slide and size > 0");
-            w.interval = gcd64(c.size_ms, c.slide_ms);
-            w.n_slices = (int32_t)(c.size_ms / w.interval);
-            break;
-        case FW_WIN_CUMULATE:
-            if (c.api != FW_API_SQL) return fail(FW_E_INVALID, "CUMULATE is a SQL window");
-            if (c.slide_ms <= 0 || c.size_ms % c.slide_ms != 0)
-                return fail(FW_E_INVALID, "Cumulative Window requires maxSize must be an integral multiple of step");
-            w.interval = c.slide_ms;
-            w.n_slices = (int32_t)(c.size_ms / c.slide_ms);
-            break;
-        default: return fail(FW_E_INVALID, "bad window kind %d", c.window_kind);
-    }
-    w.ds = c.api == FW_API_DATASTREAM;
-    w.slide = c.window_kind == FW_WIN_HOP ? c.slide_ms : c.size_ms;
-    w.n_win = (w.ds && c.window_kind == FW_WIN_HOP) ? (int32_t)((c.size_ms + c.slide_ms - 1) / c.slide_ms) : 1;
-    w.slide_div = make_udiv((uint64_t)w.slide);
-    // ---- lateness (DataStream) and shift time zone (SQL TIMESTAMP_LTZ)
-    if (c.allowed_lateness_ms < 0) return fail(FW_E_INVALID, "The allowed lateness cannot be negative.");
-    if (c.api == FW_API_SQL && (c.allowed_lateness_ms != 0 || c.late_side_output))
-        return fail(FW_E_INVALID, "allowed lateness and late side outputs are DataStream WindowOperator features");
-    w.lateness = c.allowed_lateness_ms;
-    if (c.tz_n < 0) return fail(FW_E_INVALID, "tz_n must be >= 0");
-    if (c.tz_n > 0) {
-        if (c.api != FW_API_SQL) return fail(FW_E_INVALID, "shift time zones belong to SQL TIMESTAMP_LTZ windows");
-        if (!c.tz_utc || !c.tz_offset_ms) return fail(FW_E_INVALID, "tz_utc / tz_offset_ms required when tz_n > 0");
-        if (c.tz_utc[0] != INT64_MIN) return fail(FW_E_INVALID, "tz_utc[0] must be Long.MIN_VALUE");
-        h->tz_utc.assign(c.tz_utc, c.tz_utc + c.tz_n);
-        h->tz_off.assign(c.tz_offset_ms, c.tz_offset_ms + c.tz_n);
-        h->tz_bound.assign(c.tz_n, INT64_MIN);
-        for (int i = 1; i < c.tz_n; i++) {
-            if (h->tz_utc[i] <= h->tz_utc[i - 1]) return fail(FW_E_INVALID, "tz_utc must be strictly ascending");
-            if (h->tz_off[i] < -18 * 3600000ll || h->tz_off[i] > 18 * 3600000ll) return fail(FW_E_INVALID, "offset out of range");
-            h->tz_bound[i] = h->tz_utc[i] + std::max(h->tz_off[i - 1], h->tz_off[i]);
-            if (h->tz_bound[i] <= h->tz_bound[i - 1]) return fail(FW_E_INVALID, "tz transitions too close together");
-        }
-    }
-    w.tz = TzTable{h->tz_utc.data(), h->tz_off.data(), h->tz_bound.data(), c.tz_n, c.tz_use_dst ? 1 : 0};
-    w.slice_div = make_udiv((uint64_t)w.interval);
-    w.size_div = make_udiv((uint64_t)w.size);
-    w.fast32 = w.interval < (1ll << 30) && w.offset < (1ll << 61) && w.offset > -(1ll << 61);
-    w.slice_div32 = make_udiv32(w.fast32 ? (uint32_t)w.interval : 1u);
-    h->always_flush = c.api == FW_API_DATASTREAM;
-
+// The aggregate planner: fw_config.aggs -> accumulator words (WordDesc: op, value slot and NULL gate
+// per word, shared words deduplicated) and the aggregates over them (AggDesc: w0, w1, nn, ...).
+// slot_col[0 .. *n_slots) receives the value columns the words read.  The time windows and the SQL
+// session plan (fw_session.hip) share it.
+int fw::plan_aggs(const fw_config& c, WordDesc* wd_out, AggDesc* ad_out, int32_t* slot_col, int32_t* n_slots) {
+    WordDesc& wd = *wd_out;
+    AggDesc& ad = *ad_out;
     // ---- aggregates -> accumulator words
     if (c.api == FW_API_DATASTREAM && c.nullable_cols)
         return fail(FW_E_INVALID, "DataStream field aggregations have no NULL inputs");
     if (c.agg_phase != FW_PHASE_ONE && c.agg_phase != FW_PHASE_LOCAL && c.agg_phase != FW_PHASE_GLOBAL)
         return fail(FW_E_INVALID, "bad agg_phase %d", c.agg_phase);
     if (c.agg_phase != FW_PHASE_ONE && c.api != FW_API_SQL) return fail(FW_E_INVALID, "two-phase aggregation is SQL only");
-    WordDesc& wd = h->wd;
-    AggDesc& ad = h->ad;
     wd.nw = 0;
     wd.has_q = 0;
     int nslot = 0;
     auto nullable = [&](int col) { return ((c.nullable_cols >> col) & 1u) != 0; };
     auto slot_of = [&](int col) -> int {
         for (int s = 0; s < nslot; s++)
-            if (h->slot_col[s] == col) return s;
+            if (slot_col[s] == col) return s;
         if (nslot >= MAX_KCOLS) return -1;
-        h->slot_col[nslot] = col;
+        slot_col[nslot] = col;
         return nslot++;
     };
     // one word per (op, slot, gate); COUNT words are identified by their gate alone
@@ -615,6 +510,131 @@ int validate_and_plan(fw_handle* h) {
         if (wd.op[i] == W_CNT && wd.gate[i] < 0) star = i;
     for (int g = 0; g < c.n_aggs; g++)
         if (nn_star[g]) ad.nn[g] = star;
+    *n_slots = nslot;
+    return FW_OK;
+}
+
+namespace {
+
+int validate_and_plan(fw_handle* h) {
+    const fw_config& c = h->cfg;
+    if (c.abi_version != FW_ABI_VERSION) return fail(FW_E_INVALID, "abi_version %d != %d", c.abi_version, FW_ABI_VERSION);
+    if (c.api != FW_API_SQL && c.api != FW_API_DATASTREAM) return fail(FW_E_INVALID, "bad api %d", c.api);
+    if (c.n_aggs < 1 || c.n_aggs > FW_MAX_AGGS) return fail(FW_E_INVALID, "n_aggs %d out of range", c.n_aggs);
+    if (c.n_value_cols < 0 || c.n_value_cols > FW_MAX_COLS) return fail(FW_E_INVALID, "n_value_cols out of range");
+    if (c.max_parallelism < 1 || c.max_parallelism > 32768) return fail(FW_E_INVALID, "max_parallelism out of range");
+    if (c.parallelism < 1 || c.parallelism > c.max_parallelism) return fail(FW_E_INVALID, "parallelism out of range");
+    if (c.subtask_index < 0 || c.subtask_index >= c.parallelism) return fail(FW_E_INVALID, "subtask_index out of range");
+    if (c.key_hash < FW_KEYHASH_LONG || c.key_hash > FW_KEYHASH_KEYROW) return fail(FW_E_INVALID, "bad key_hash");
+    if (c.window_kind == FW_WIN_COUNT) {  // count windows: a plan of their own (fw_count.hip)
+        int rc = cw_plan(c, &h->cw);
+        if (rc) return rc;
+        h->ks = h->cw.ks;
+        h->nv = h->cw.is_count ? 0 : 1;
+        h->slot_col[0] = h->cw.val_col;
+        h->n_out = 1;
+        h->out_cap = c.output_capacity;
+        h->stage_cap = c.max_batch_rows;
+        return FW_OK;
+    }
+    if (c.window_kind == FW_WIN_SESSION) {  // session windows: a plan of their own (fw_session.hip)
+        int rc = sw_plan(c, &h->sw);
+        if (rc) return rc;
+        h->ks = h->sw.ks;
+        if (h->sw.d.sql) {  // the value columns the plan's words read (staged and checked per push)
+            h->nv = h->sw.n_slots;
+            for (int s = 0; s < h->nv; s++) h->slot_col[s] = h->sw.slot_col[s];
+            h->ad = h->sw.ad;
+        } else {
+            h->nv = h->sw.d.is_count ? 0 : 1;
+            h->slot_col[0] = h->sw.val_col;
+        }
+        h->n_out = h->sw.n_out;
+        h->out_cap = c.output_capacity;
+        h->stage_cap = c.max_batch_rows;
+        return FW_OK;
+    }
+    h->keyrow = c.key_hash == FW_KEYHASH_KEYROW;
+    if (h->keyrow) {
+        if (c.api != FW_API_SQL) return fail(FW_E_INVALID, "key rows (FW_KEYHASH_KEYROW) are SQL keys");
+        const int32_t mb = c.key_row_max_bytes ? c.key_row_max_bytes : 120;  // 120: one 128-B line per id
+        if (mb < 16 || mb > 4096 || (mb & 7)) return fail(FW_E_INVALID, "key_row_max_bytes must be a multiple of 8 in [16, 4096]");
+        h->kr.stride_words = (int32_t)(((8 + mb) + 127) / 128 * 16);  // meta word + image, whole 128-B lines
+        h->kr.max_len = mb;
+    }
+    if (c.size_ms <= 0) return fail(FW_E_INVALID, "window size must be > 0");
+    // ---- window (SliceAssigners constructors' argument checks)
+    WinDesc& w = h->win;
+    w.kind = c.window_kind;
+    w.size = c.size_ms;
+    w.offset = c.offset_ms;
+    switch (c.window_kind) {
+        case FW_WIN_TUMBLE:
+            if (!(c.offset_ms > -c.size_ms && c.offset_ms < c.size_ms))
+                return fail(FW_E_INVALID, "Tumbling Window parameters must satisfy abs(offset) < size");
+            w.interval = c.size_ms;
+            w.n_slices = 1;
+            if (c.api == FW_API_DATASTREAM) w.offset = c.offset_ms % c.size_ms;
+            break;
+        case FW_WIN_HOP:
+            if (c.slide_ms <= 0) return fail(FW_E_INVALID, "Hopping Window must satisfy slide > 0 and size > 0");
+            // SQL slices need slide | size (SliceAssigners.HoppingSliceAssigner); DataStream sliding
+            // windows do not (SlidingEventTimeWindows.java:77-90): panes of gcd(size, slide) ms, each in
+            // floor or ceil(size / slide) windows
+            if (c.api != FW_API_DATASTREAM && c.size_ms % c.slide_ms != 0)
+                return fail(FW_E_INVALID, "Slicing Hopping Window requires size must be an integral multiple of slide");
+            if (c.api == FW_API_DATASTREAM && c.size_ms < c.slide_ms)  // gaps: panes in no window (not eligible)
+                return fail(FW_E_INVALID, "sliding windows with size < slide run on the reference operator");
+            if (c.api == FW_API_DATASTREAM && !(c.offset_ms > -c.slide_ms && c.offset_ms < c.slide_ms))
+                return fail(FW_E_INVALID, "SlidingEventTimeWindows parameters must satisfy abs(offset) < slide and size > 0");
+            w.interval = gcd64(c.size_ms, c.slide_ms);
+            w.n_slices = (int32_t)(c.size_ms / w.interval);
+            break;
+        case FW_WIN_CUMULATE:
+            if (c.api != FW_API_SQL) return fail(FW_E_INVALID, "CUMULATE is a SQL window");
+            if (c.slide_ms <= 0 || c.size_ms % c.slide_ms != 0)
+                return fail(FW_E_INVALID, "Cumulative Window requires maxSize must be an integral multiple of step");
+            w.interval = c.slide_ms;
+            w.n_slices = (int32_t)(c.size_ms / c.slide_ms);
+            break;
+        default: return fail(FW_E_INVALID, "bad window kind %d", c.window_kind);
+    }
+    w.ds = c.api == FW_API_DATASTREAM;
+    w.slide = c.window_kind == FW_WIN_HOP ? c.slide_ms : c.size_ms;
+    w.n_win = (w.ds && c.window_kind == FW_WIN_HOP) ? (int32_t)((c.size_ms + c.slide_ms - 1) / c.slide_ms) : 1;
+    w.slide_div = make_udiv((uint64_t)w.slide);
+    // ---- lateness (DataStream) and shift time zone (SQL TIMESTAMP_LTZ)
+    if (c.allowed_lateness_ms < 0) return fail(FW_E_INVALID, "The allowed lateness cannot be negative.");
+    if (c.api == FW_API_SQL && (c.allowed_lateness_ms != 0 || c.late_side_output))
+        return fail(FW_E_INVALID, "allowed lateness and late side outputs are DataStream WindowOperator features");
+    w.lateness = c.allowed_lateness_ms;
+    if (c.tz_n < 0) return fail(FW_E_INVALID, "tz_n must be >= 0");
+    if (c.tz_n > 0) {
+        if (c.api != FW_API_SQL) return fail(FW_E_INVALID, "shift time zones belong to SQL TIMESTAMP_LTZ windows");
+        if (!c.tz_utc || !c.tz_offset_ms) return fail(FW_E_INVALID, "tz_utc / tz_offset_ms required when tz_n > 0");
+        if (c.tz_utc[0] != INT64_MIN) return fail(FW_E_INVALID, "tz_utc[0] must be Long.MIN_VALUE");
+        h->tz_utc.assign(c.tz_utc, c.tz_utc + c.tz_n);
+        h->tz_off.assign(c.tz_offset_ms, c.tz_offset_ms + c.tz_n);
+        h->tz_bound.assign(c.tz_n, INT64_MIN);
+        for (int i = 1; i < c.tz_n; i++) {
+            if (h->tz_utc[i] <= h->tz_utc[i - 1]) return fail(FW_E_INVALID, "tz_utc must be strictly ascending");
+            if (h->tz_off[i] < -18 * 3600000ll || h->tz_off[i] > 18 * 3600000ll) return fail(FW_E_INVALID, "offset out of range");
+            h->tz_bound[i] = h->tz_utc[i] + std::max(h->tz_off[i - 1], h->tz_off[i]);
+            if (h->tz_bound[i] <= h->tz_bound[i - 1]) return fail(FW_E_INVALID, "tz transitions too close together");
+        }
+    }
+    w.tz = TzTable{h->tz_utc.data(), h->tz_off.data(), h->tz_bound.data(), c.tz_n, c.tz_use_dst ? 1 : 0};
+    w.slice_div = make_udiv((uint64_t)w.interval);
+    w.size_div = make_udiv((uint64_t)w.size);
+    w.fast32 = w.interval < (1ll << 30) && w.offset < (1ll << 61) && w.offset > -(1ll << 61);
+    w.slice_div32 = make_udiv32(w.fast32 ? (uint32_t)w.interval : 1u);
+    h->always_flush = c.api == FW_API_DATASTREAM;
+
+    // ---- aggregates -> accumulator words
+    WordDesc& wd = h->wd;
+    AggDesc& ad = h->ad;
+    int32_t nslot = 0;
+    if (int rc = plan_aggs(c, &wd, &ad, h->slot_col, &nslot)) return rc;
     h->nv = nslot;
     h->nw_t = round_nw(wd.nw);
     h->n_out = c.n_aggs + (ad.first_word >= 0 ? 1 : 0);  // + value1's ordinal (fw_result.first_ord)
@@ -1606,8 +1626,7 @@ static int commit_impl(fw_handle* h, int64_t n, uint32_t packed, const int64_t* 
     const int rc = h->cw.on  ? cw_push(&h->cw, n, h->d_key[b], h->cfg.key_hash == FW_KEYHASH_PRECOMPUTED ? h->d_kh[b] : nullptr,
                                        (const uint64_t*)vals[h->slot_col[0]])
                    : h->sw.on ? sw_push(&h->sw, h->host_cur, n, h->d_key[b], h->d_ts[b],
-                                        h->cfg.key_hash == FW_KEYHASH_PRECOMPUTED ? h->d_kh[b] : nullptr,
-                                        (const uint64_t*)vals[h->slot_col[0]])
+                                        h->cfg.key_hash == FW_KEYHASH_PRECOMPUTED ? h->d_kh[b] : nullptr, vals, nuls)
                    : h->keyrow ? push_key_rows(h, n, h->d_kro[b], h->d_krb[b], h->d_ts[b], vals, nuls)
                              : push(h, n, h->d_key[b], h->d_ts[b],
                                     h->cfg.key_hash == FW_KEYHASH_PRECOMPUTED ? h->d_kh[b] : nullptr, vals, nuls);
@@ -1648,8 +1667,14 @@ int fw_push_device(fw_handle* h, int64_t n, const int64_t* d_key, const int64_t*
     if (!d_key || !d_ts) return fail(FW_E_INVALID, "null key/ts column");
     if (h->sw.on) {  // session windows: folded into the state now, under the current watermark
         if (h->cfg.key_hash == FW_KEYHASH_PRECOMPUTED && !d_key_hash) return fail(FW_E_INVALID, "key_hash column required");
-        if (h->nv > 0 && (!d_values || !d_values[h->slot_col[0]])) return fail(FW_E_INVALID, "value column %d is NULL", h->slot_col[0]);
-        return sw_push(&h->sw, h->host_cur, n, d_key, d_ts, d_key_hash, h->nv > 0 ? (const uint64_t*)d_values[h->slot_col[0]] : nullptr);
+        if (h->nv > 0 && !d_values) return fail(FW_E_INVALID, "value columns required");
+        for (int s = 0; s < h->nv; s++) {
+            const int v = h->slot_col[s];
+            if (!d_values[v]) return fail(FW_E_INVALID, "value column %d is NULL", v);
+            if (((h->cfg.nullable_cols >> v) & 1u) && (!d_nulls || !d_nulls[v]))
+                return fail(FW_E_INVALID, "nullable value column %d needs its null-flag column", v);
+        }
+        return sw_push(&h->sw, h->host_cur, n, d_key, d_ts, d_key_hash, d_values, d_nulls);
     }
     if (h->keyrow) return fail(FW_E_INVALID, "a FW_KEYHASH_KEYROW operator takes key rows (fw_push_device_key_rows)");
     if (h->cfg.key_hash == FW_KEYHASH_PRECOMPUTED && !d_key_hash) return fail(FW_E_INVALID, "key_hash column required");
@@ -1772,14 +1797,18 @@ int fw_flush(fw_handle* h) {
 // a count handle's rows: one per fire, in the device's order; first_ord orders them as the reference emits
 struct FoldedOut {
     int64_t *key, *ws, *we;
-    uint64_t* val;
+    uint64_t* val[FW_MAX_AGGS];  // [n_val] value columns (a SQL session handle: one per aggregate)
+    int32_t n_val;
     int64_t* ord;  // NULL: a session handle's rows carry no ordinal
     uint32_t* null_mask;
+    bool nulls;    // the null mask is written by the device (a SQL session handle); else zeros
     int64_t out_cap;
 };
 static FoldedOut folded_out(fw_handle* h) {
-    if (h->cw.on) return {h->cw.out_key, h->cw.out_ws, h->cw.out_we, h->cw.out_val, h->cw.out_ord, h->cw.out_null, h->cw.out_cap};
-    return {h->sw.out_key, h->sw.out_ws, h->sw.out_we, h->sw.out_val, nullptr, h->sw.out_null, h->sw.out_cap};
+    if (h->cw.on) return {h->cw.out_key, h->cw.out_ws, h->cw.out_we, {h->cw.out_val}, 1, h->cw.out_ord, h->cw.out_null, false, h->cw.out_cap};
+    FoldedOut w{h->sw.out_key, h->sw.out_ws, h->sw.out_we, {}, h->sw.n_out, nullptr, h->sw.out_null, h->sw.d.sql != 0, h->sw.out_cap};
+    for (int g = 0; g < w.n_val; g++) w.val[g] = h->sw.out_val[g];
+    return w;
 }
 static int cw_results(fw_handle* h, fw_result* out, int copy_to_host) {
     const FoldedOut w = folded_out(h);
@@ -1796,7 +1825,7 @@ static int cw_results(fw_handle* h, fw_result* out, int copy_to_host) {
         out->key = w.key;
         out->window_start = w.ws;
         out->window_end = w.we;
-        out->values[0] = (int64_t*)w.val;
+        for (int g = 0; g < w.n_val; g++) out->values[g] = (int64_t*)w.val[g];
         out->first_ord = w.ord;
         out->null_mask = w.null_mask;
         return FW_OK;
@@ -1804,22 +1833,25 @@ static int cw_results(fw_handle* h, fw_result* out, int copy_to_host) {
     h->r_key.resize(n);
     h->r_ws.resize(n);
     h->r_we.resize(n);
-    h->r_val[0].resize(n);
-    h->r_val[1].resize(n);
+    const int ord_at = w.n_val;  // r_val[n_val] holds a count handle's ordinals
+    for (int g = 0; g < w.n_val; g++) h->r_val[g].resize(n);
+    if (w.ord) h->r_val[ord_at].resize(n);
     h->r_null.assign(n, 0u);
     if (n) {
         HIP_TRY(hipMemcpyAsync(h->r_key.data(), w.key, n * 8, hipMemcpyDeviceToHost, h->stream));
         HIP_TRY(hipMemcpyAsync(h->r_ws.data(), w.ws, n * 8, hipMemcpyDeviceToHost, h->stream));
         HIP_TRY(hipMemcpyAsync(h->r_we.data(), w.we, n * 8, hipMemcpyDeviceToHost, h->stream));
-        HIP_TRY(hipMemcpyAsync(h->r_val[0].data(), w.val, n * 8, hipMemcpyDeviceToHost, h->stream));
-        if (w.ord) HIP_TRY(hipMemcpyAsync(h->r_val[1].data(), w.ord, n * 8, hipMemcpyDeviceToHost, h->stream));
+        for (int g = 0; g < w.n_val; g++)
+            HIP_TRY(hipMemcpyAsync(h->r_val[g].data(), w.val[g], n * 8, hipMemcpyDeviceToHost, h->stream));
+        if (w.nulls) HIP_TRY(hipMemcpyAsync(h->r_null.data(), w.null_mask, n * 4, hipMemcpyDeviceToHost, h->stream));
+        if (w.ord) HIP_TRY(hipMemcpyAsync(h->r_val[ord_at].data(), w.ord, n * 8, hipMemcpyDeviceToHost, h->stream));
         HIP_TRY(hipStreamSynchronize(h->stream));
     }
     out->key = h->r_key.data();
     out->window_start = h->r_ws.data();
     out->window_end = h->r_we.data();
-    out->values[0] = (int64_t*)h->r_val[0].data();
-    out->first_ord = w.ord ? (int64_t*)h->r_val[1].data() : nullptr;
+    for (int g = 0; g < w.n_val; g++) out->values[g] = (int64_t*)h->r_val[g].data();
+    out->first_ord = w.ord ? (int64_t*)h->r_val[ord_at].data() : nullptr;
     out->null_mask = h->r_null.data();
     return FW_OK;
 }
@@ -3470,13 +3502,80 @@ int fw_host_session_add(const fw_config* cfg, int64_t watermark, int64_t ts, int
     h.cfg = *cfg;
     const int rc = validate_and_plan(&h);
     if (rc) return rc;
+    if (h.sw.d.sql) return fail(FW_E_INVALID, "fw_host_session_add needs a DataStream session configuration (SQL: fw_host_sql_session_add)");
     if (*n < 0 || *n > capacity) return fail(FW_E_INVALID, "bad session count %d (capacity %d)", *n, capacity);
     const SessionDesc& d = h.sw.d;
     for (int32_t i = 0; i < *n; i++) accs[i] = (int64_t)session_word_of_result(d, (uint64_t)accs[i]);
-    const int r = session_add(d, watermark, ts, session_word(d, (uint64_t)value), starts, ends, (uint64_t*)accs, 1, n, capacity);
+    const uint64_t word = session_word(d, (uint64_t)value);
+    const int r = session_add<1>(d.gap, d.ops, watermark, ts, &word, 1, starts, ends, (uint64_t*)accs, 1, 1, n, capacity);
     for (int32_t i = 0; i < *n; i++) accs[i] = (int64_t)session_result(d, (uint64_t)accs[i]);
     if (r < 0) return fail(FW_E_CAPACITY, "the session list is full (%d sessions)", capacity);
     *outcome = r;
+    return FW_OK;
+}
+
+// the plan of a SQL session configuration, as fw_create makes it
+static int sql_session_plan(const fw_config* cfg, const char* name, fw_handle* h) {
+    if (cfg->window_kind != FW_WIN_SESSION || cfg->api != FW_API_SQL)
+        return fail(FW_E_INVALID, "%s needs a FW_WIN_SESSION configuration with api FW_API_SQL", name);
+    h->cfg = *cfg;
+    return validate_and_plan(h);
+}
+
+int fw_host_sql_session_words(const fw_config* cfg, int32_t* nw) {
+    if (!cfg || !nw) return fail(FW_E_INVALID, "null argument");
+    fw_handle h;
+    const int rc = sql_session_plan(cfg, "fw_host_sql_session_words", &h);
+    if (rc) return rc;
+    *nw = h.sw.d.nw;
+    return FW_OK;
+}
+
+int fw_host_sql_session_add(const fw_config* cfg, int64_t watermark, int64_t ts, const int64_t* values, const uint8_t* nulls,
+                            int64_t* starts, int64_t* ends, int64_t* acc_words, int32_t* n, int32_t capacity, int32_t* outcome) {
+    if (!cfg || !n || !outcome || (capacity > 0 && (!starts || !ends || !acc_words))) return fail(FW_E_INVALID, "null argument");
+    fw_handle h;
+    const int rc = sql_session_plan(cfg, "fw_host_sql_session_add", &h);
+    if (rc) return rc;
+    if (cfg->n_value_cols > 0 && !values) return fail(FW_E_INVALID, "null argument");
+    if (cfg->nullable_cols && !nulls) return fail(FW_E_INVALID, "null flags required (nullable_cols != 0)");
+    if (*n < 0 || *n > capacity) return fail(FW_E_INVALID, "bad session count %d (capacity %d)", *n, capacity);
+    const SessionDesc& d = h.sw.d;
+    uint64_t words[SW_MAX_NW];
+    for (int w = 0; w < d.nw; w++) {  // a row's words, as sw_row_words computes them on the device
+        const int32_t col = d.col[w], gate = d.gate[w];
+        if (gate >= 0 && nulls[gate]) words[w] = session_identity(d.ops[w]);
+        else words[w] = col == SW_COL_ONE ? 1ull : (uint64_t)values[col];
+    }
+    uint64_t* acc = (uint64_t*)acc_words;
+    int r;
+    switch (d.nw) {
+        case 1: r = session_add<1>(d.gap, d.ops, watermark, ts, words, 1, starts, ends, acc, 1, 1, n, capacity); break;
+        case 2: r = session_add<2>(d.gap, d.ops, watermark, ts, words, 1, starts, ends, acc, 1, 2, n, capacity); break;
+        case 3: r = session_add<3>(d.gap, d.ops, watermark, ts, words, 1, starts, ends, acc, 1, 3, n, capacity); break;
+        case 4: r = session_add<4>(d.gap, d.ops, watermark, ts, words, 1, starts, ends, acc, 1, 4, n, capacity); break;
+        case 5: r = session_add<5>(d.gap, d.ops, watermark, ts, words, 1, starts, ends, acc, 1, 5, n, capacity); break;
+        case 6: r = session_add<6>(d.gap, d.ops, watermark, ts, words, 1, starts, ends, acc, 1, 6, n, capacity); break;
+        case 7: r = session_add<7>(d.gap, d.ops, watermark, ts, words, 1, starts, ends, acc, 1, 7, n, capacity); break;
+        default: r = session_add<8>(d.gap, d.ops, watermark, ts, words, 1, starts, ends, acc, 1, 8, n, capacity); break;
+    }
+    if (r < 0) return fail(FW_E_CAPACITY, "the session list is full (%d sessions)", capacity);
+    *outcome = r;
+    return FW_OK;
+}
+
+int fw_host_sql_session_result(const fw_config* cfg, const int64_t* acc_words, int64_t* values, uint32_t* null_mask) {
+    if (!cfg || !acc_words || !values || !null_mask) return fail(FW_E_INVALID, "null argument");
+    fw_handle h;
+    const int rc = sql_session_plan(cfg, "fw_host_sql_session_result", &h);
+    if (rc) return rc;
+    uint32_t nm = 0;
+    for (int g = 0; g < h.sw.ad.n; g++) {
+        bool isnull;
+        values[g] = (int64_t)sql_agg_result(h.sw.ad, g, (const uint64_t*)acc_words, &isnull);
+        if (isnull) nm |= 1u << g;
+    }
+    *null_mask = nm;
     return FW_OK;
 }
 

@@ -531,6 +531,48 @@ struct AggDesc {
     int32_t by_prev;          // minBy / maxBy: the W_BYPREV word (-1: not a minBy / maxBy layout)
 };
 
+// The SQL result of aggregate g over the accumulator words acc, for a plan whose words are all of
+// the four merge classes (no W_Q* / W_DN* / W_BY* word, integer MIN / MAX): the per-aggregate rule of
+// emit_row (fw_merge_impl.h).  COUNTs are never NULL; SUM / MIN / MAX are NULL without a non-NULL
+// input (SumAggFunction.java:66-69); SUM(INT) wraps at 32 bits; AVG is NULL on a zero count, Java's
+// truncating division for BIGINT / INT (an INT result for INT), IEEE division for DOUBLE.  A NULL's
+// value word is 0.  The session advance kernel and fw_host_sql_session_result share it.
+FW_HD uint64_t sql_agg_result(const AggDesc& ad, int g, const uint64_t* acc, bool* isnull) {
+    const int32_t kind = ad.kind[g], type = ad.type[g];
+    const uint64_t w0 = acc[ad.w0[g]];
+    const bool no_rows = ad.nn[g] >= 0 && acc[ad.nn[g]] == 0;
+    *isnull = false;
+    switch (kind) {
+        case FW_AGG_COUNT_STAR:
+        case FW_AGG_COUNT: return w0;
+        case FW_AGG_SUM:
+            if (no_rows) break;
+            return type == FW_T_I32 ? (uint64_t)(int64_t)(int32_t)(uint32_t)w0 : w0;
+        case FW_AGG_MIN:
+        case FW_AGG_MAX:
+            if (no_rows) break;
+            return w0;
+        case FW_AGG_AVG: {
+            const uint64_t cnt = acc[ad.w1[g]];
+            if (cnt == 0) break;
+            if (type == FW_T_F64) {
+                double s, q;
+                __builtin_memcpy(&s, &w0, 8);
+                q = s / (double)(int64_t)cnt;
+                uint64_t r;
+                __builtin_memcpy(&r, &q, 8);
+                return r;
+            }
+            int64_t q = (int64_t)w0 / (int64_t)cnt;
+            if (type == FW_T_I32) q = (int32_t)q;
+            return (uint64_t)q;
+        }
+        default: break;
+    }
+    *isnull = true;
+    return 0;
+}
+
 constexpr int CS_WORDS = 12;  // IngestArgs::chunk_stats words per chunk
 struct IngestArgs {
     const int64_t* key;

@@ -1,5 +1,5 @@
-// fw_session.h -- DataStream event-time session windows (EventTimeSessionWindows.withGap) as a
-// sorted, dense list of sessions per superbucket.
+// fw_session.h -- event-time session windows as a sorted, dense list of sessions per superbucket:
+// DataStream EventTimeSessionWindows.withGap and the SQL SESSION window TVF aggregate.
 //
 // keyBy(...).window(EventTimeSessionWindows.withGap(gap)) runs WindowOperator.processElement's
 // merging branch: the element's window [ts, ts + gap) goes through MergingWindowSet.addWindow, which
@@ -9,6 +9,14 @@
 // key is a union of intervals, independent of arrival order except for elements that are already
 // late when they arrive (DESIGN.md "Session windows").
 //
+// The SQL form, SESSION(TABLE t PARTITION BY k, DESCRIPTOR(rowtime), gap) aggregated per (k,
+// window_start, window_end), runs the same interval rules on the Table side (recalled, parity
+// unpinned: UnsliceWindowAggProcessor, UnsliceAssigners.SessionUnsliceAssigner, the table runtime's
+// MergingWindowProcessFunction.assignActualWindows / MergingFunctionImpl.merge and
+// WindowAggOperator.processWatermark).  It differs in what a session carries: the accumulator words
+// of a list of aggregates over NULL-able columns (the planner's WordDesc / AggDesc), 1 to 8 words
+// rounded up to 1, 2, 4 or 8; a late row is dropped and counted, there is no side output.
+//
 // This header holds the interval arithmetic the kernels and fw_host_session_add share (FW_HD), the
 // per-handle state of a session operator (SessionOp) and the entry points fw_api.hip dispatches to.
 #pragma once
@@ -16,16 +24,27 @@
 
 namespace fw {
 
+constexpr int SW_MAX_NW = MAX_WORDS;      // accumulator words of a session
+constexpr int32_t SW_COL_ONE = -1;        // SessionDesc::col of a count word: every row counts 1
+constexpr int32_t SW_COL_PAD = -2;        // ... of a padding word: an integer add of 0
+
 struct SessionDesc {
-    int64_t gap;       // EventTimeSessionWindows.withGap(gap)
-    int32_t op;        // CountWordOp of the one accumulator word
-    int32_t vtype;     // fw_value_type of the aggregated field
-    int32_t is_count;  // COUNT_STAR: every element counts 1
-    int32_t dbl_cmp;   // DOUBLE min / max: the accumulator holds dkey(value) (Double.compare order)
+    int64_t gap;       // EventTimeSessionWindows.withGap(gap) / the SESSION TVF's gap
+    int32_t op;        // DataStream: CountWordOp of the one accumulator word (= ops[0])
+    int32_t vtype;     // DataStream: fw_value_type of the aggregated field
+    int32_t is_count;  // DataStream: COUNT_STAR, every element counts 1
+    int32_t dbl_cmp;   // DataStream DOUBLE min / max: the accumulator holds dkey(value) (Double.compare order)
+    int32_t sql;       // the SQL form: words from the planner's WordDesc, results through sql_agg_result
+    int32_t nw;        // words the plan uses; the kernels carry sw_round_nw(nw)
+    int32_t ops[SW_MAX_NW];   // CountWordOp per word (the word's merge class)
+    int32_t col[SW_MAX_NW];   // value column the word reads, SW_COL_ONE or SW_COL_PAD
+    int32_t gate[SW_MAX_NW];  // value column whose NULL rows the word skips, -1: none
 };
 
 constexpr int64_t SW_MAX_GAP = (int64_t)1 << 40;
-constexpr int SW_WORDS = 4;               // words per session: key, start, end, acc
+constexpr int SW_WORDS = 4;               // words per one-word session: key, start, end, acc
+FW_HD constexpr int sw_stride(int nw) { return 3 + nw; }  // words per session: key, start, end, acc[nw]
+FW_HD constexpr int sw_round_nw(int nw) { return nw <= 1 ? 1 : nw <= 2 ? 2 : nw <= 4 ? 4 : 8; }
 constexpr int64_t SW_DEAD = INT64_MIN;    // end word of a scratch slot that holds no session
 
 // TimeWindow.intersects: inclusive on both sides, so windows that merely touch merge
@@ -65,15 +84,30 @@ FW_HD uint64_t session_identity(int32_t op) {
 }
 FW_HD uint64_t session_fold(int32_t op, uint64_t older, uint64_t newer) { return count_fold(op, older, newer); }
 
-// One element (ts, word) of one key against the key's sessions: n sessions sorted by start, pairwise
-// non-touching, session i at start[i * stride], end[i * stride], acc[i * stride].  The element's
-// window and every session it intersects become one session (MergingWindowSet.addWindow); an
-// element that intersects nothing and is late is dropped and leaves the list untouched.
+// the merge class of a planner word as the CountWordOp that folds it, -1 outside the four classes
+FW_HD int32_t session_op_of_word(int32_t wop) {
+    switch (wop) {
+        case W_CNT:
+        case W_SUM_I: return CW_ADD_I;
+        case W_SUM_F: return CW_ADD_F;
+        case W_MIN_I: return CW_MIN;
+        case W_MAX_I: return CW_MAX;
+        default: return -1;
+    }
+}
+
+// One element (ts, its NW words at words[w * wstride]) of one key against the key's sessions: n
+// sessions sorted by start, pairwise non-touching, session i at start[i * stride], end[i * stride]
+// and its NW accumulator words at acc[i * astride ..], word w folded under ops[w] (the word count is
+// a template parameter so the device's copies unroll).  The element's window and every session
+// it intersects become one session (MergingWindowSet.addWindow); an element that intersects nothing
+// and is late is dropped and leaves the list untouched.
 // Returns 1 merged or added, 0 dropped as late, -1 the list is full (capacity sessions).
-FW_HD int session_add(const SessionDesc& d, int64_t watermark, int64_t ts, uint64_t word, int64_t* start, int64_t* end,
-                      uint64_t* acc, int stride, int32_t* n, int32_t capacity) {
+template <int NW>
+FW_HD int session_add(int64_t gap, const int32_t* ops, int64_t watermark, int64_t ts, const uint64_t* words, int wstride,
+                      int64_t* start, int64_t* end, uint64_t* acc, int stride, int astride, int32_t* n, int32_t capacity) {
     const int32_t m = *n;
-    const int64_t we = ts + d.gap;
+    const int64_t we = ts + gap;
     int32_t i = 0;
     while (i < m && !session_intersects(ts, we, start[(size_t)i * stride], end[(size_t)i * stride]) &&
            end[(size_t)i * stride] < ts)
@@ -81,34 +115,35 @@ FW_HD int session_add(const SessionDesc& d, int64_t watermark, int64_t ts, uint6
     int32_t j = i;
     while (j < m && session_intersects(ts, we, start[(size_t)j * stride], end[(size_t)j * stride])) j++;
     if (i == j) {
-        if (session_late(ts, d.gap, watermark)) return 0;
+        if (session_late(ts, gap, watermark)) return 0;
         if (m >= capacity) return -1;
         for (int32_t k = m; k > i; k--) {
             start[(size_t)k * stride] = start[(size_t)(k - 1) * stride];
             end[(size_t)k * stride] = end[(size_t)(k - 1) * stride];
-            acc[(size_t)k * stride] = acc[(size_t)(k - 1) * stride];
+            for (int w = 0; w < NW; w++) acc[(size_t)k * astride + w] = acc[(size_t)(k - 1) * astride + w];
         }
         start[(size_t)i * stride] = ts;
         end[(size_t)i * stride] = we;
-        acc[(size_t)i * stride] = word;
+        for (int w = 0; w < NW; w++) acc[(size_t)i * astride + w] = words[(size_t)w * wstride];
         *n = m + 1;
         return 1;
     }
     int64_t s = ts, e = we;
-    uint64_t a = acc[(size_t)i * stride];
     for (int32_t k = i; k < j; k++) {
         session_cover(&s, &e, start[(size_t)k * stride], end[(size_t)k * stride]);
-        if (k > i) a = session_fold(d.op, a, acc[(size_t)k * stride]);
+        if (k > i)
+            for (int w = 0; w < NW; w++)
+                acc[(size_t)i * astride + w] = session_fold(ops[w], acc[(size_t)i * astride + w], acc[(size_t)k * astride + w]);
     }
     start[(size_t)i * stride] = s;
     end[(size_t)i * stride] = e;
-    acc[(size_t)i * stride] = session_fold(d.op, a, word);
+    for (int w = 0; w < NW; w++) acc[(size_t)i * astride + w] = session_fold(ops[w], acc[(size_t)i * astride + w], words[(size_t)w * wstride]);
     const int32_t gone = j - i - 1;
     if (gone > 0) {
         for (int32_t k = j; k < m; k++) {
             start[(size_t)(k - gone) * stride] = start[(size_t)k * stride];
             end[(size_t)(k - gone) * stride] = end[(size_t)k * stride];
-            acc[(size_t)(k - gone) * stride] = acc[(size_t)k * stride];
+            for (int w = 0; w < NW; w++) acc[(size_t)(k - gone) * astride + w] = acc[(size_t)k * astride + w];
         }
         *n = m - gone;
     }
@@ -120,12 +155,17 @@ constexpr int64_t SW_MAX_HIST = CW_MAX_HIST;       // [superbucket][chunk] parti
 constexpr int64_t SW_SIDE_WORDS = 4;               // late side-output row: key, ts, push_seq << 32 | row, value
 
 // Per-handle state of a session operator.  Superbucket sb's sessions are the first n_s[sb] entries of
-// state[(sb * cap_s + i) * SW_WORDS ..]: key, start, end, acc, sorted by (key as uint64, start) and
-// dense -- no tombstones: a fold rewrites the list, a fire compacts it.
+// state[(sb * cap_s + i) * sw_stride(nw_t) ..]: key, start, end, acc[nw_t], sorted by (key as uint64,
+// start) and dense -- no tombstones: a fold rewrites the list, a fire compacts it.
 struct SessionOp {
     bool on = false;
     SessionDesc d{};
+    AggDesc ad{};             // SQL: the aggregates over the words (sql_agg_result)
     KeySpace ks{};
+    int32_t nw_t = 1;         // sw_round_nw(d.nw): the kernels' instance
+    int32_t n_out = 1;        // result value columns (SQL: one per aggregate)
+    int32_t n_slots = 0;      // SQL: value columns the plan loads, slot_col[0 .. n_slots)
+    int32_t slot_col[MAX_KCOLS] = {};
     int32_t val_col = 0;
     int32_t cap_s = 0;        // sessions per superbucket
     int32_t late_side = 0;    // late_side_output
@@ -151,19 +191,23 @@ struct SessionOp {
     int64_t* out_key = nullptr;
     int64_t* out_ws = nullptr;
     int64_t* out_we = nullptr;
-    uint64_t* out_val = nullptr;
-    uint32_t* out_null = nullptr;  // zeros
+    uint64_t* out_val[FW_MAX_AGGS] = {};  // [n_out] columns
+    uint32_t* out_null = nullptr;  // DataStream: zeros
     int64_t* side = nullptr;       // [side_cap][SW_SIDE_WORDS]
     int64_t push_seq = 0;
 };
 
+// fw_api.hip: the aggregate planner of the time windows (fw_config.aggs -> WordDesc / AggDesc, the
+// value slots the words read); the SQL session plan calls it too
+int plan_aggs(const fw_config& c, WordDesc* wd, AggDesc* ad, int32_t* slot_col, int32_t* n_slots);
 // validation + plan of a FW_WIN_SESSION configuration; no device call
 int sw_plan(const fw_config& c, SessionOp* op);
 int sw_allocate(SessionOp* op, hipStream_t stream, Ctrl* ctrl);
 void sw_free(SessionOp* op);
 // folds n rows into the state under the watermark `watermark` (stream-ordered, asynchronous)
+// (DataStream: d_vals[val_col] is the one value column, d_nulls is not read)
 int sw_push(SessionOp* op, int64_t watermark, int64_t n, const int64_t* d_key, const int64_t* d_ts, const int32_t* d_khash,
-            const uint64_t* d_val);
+            const void* const* d_vals, const uint8_t* const* d_nulls);
 // fires every session with end - 1 <= watermark and compacts the rest (stream-ordered, asynchronous)
 int sw_advance(SessionOp* op, int64_t watermark);
 int sw_snapshot(SessionOp* op, int64_t watermark, int32_t key_group, void* buf, int64_t capacity, int64_t* size);

@@ -7,6 +7,9 @@
 //                 sorted state into a scratch list, coalesce by a segmented running max of `end`
 // and one launch per watermark:
 //   k_sw_advance  one workgroup per superbucket: emit the due sessions, compact the rest
+// k_sw_fold and k_sw_advance are templates on the accumulator words a session carries (NW = 1, 2, 4
+// or 8; 3 + NW words per session): the DataStream handle is the NW = 1 instance, a SQL session handle
+// takes the instance of its plan's word count and a merge class per word.
 // No workgroup waits on another: the only cross-workgroup traffic is counters (atomic adds).
 #include <hip/hip_runtime.h>
 
@@ -215,10 +218,12 @@ __global__ __launch_bounds__(256) void k_sw_scatter(int64_t n, int32_t n_chunks,
 struct SwFoldArgs {
     const int64_t* key;
     const int64_t* ts;
-    const uint64_t* val;
+    const uint64_t* vals[FW_MAX_COLS];   // value columns by column index (the ones SessionDesc::col names)
+    const uint8_t* nulls[FW_MAX_COLS];   // null-flag columns (the ones SessionDesc::gate names)
     const uint32_t* perm;
     const int32_t* seg;
     SessionDesc d;
+    uint32_t opsp;  // d.ops, two bits per word
     int64_t watermark;
     int32_t cap_s;
     int32_t late_side;
@@ -233,21 +238,43 @@ struct SwFoldArgs {
 };
 
 // first index in [lo, hi) of the sorted session list whose (key, start) is not below (k, s)
+template <int SWS>
 __device__ __forceinline__ int sw_lower(const uint64_t* st, int lo, int hi, uint64_t k, int64_t s) {
     while (lo < hi) {  // <= 32 steps
         const int mid = (lo + hi) >> 1;
-        const uint64_t mk = st[(size_t)mid * SW_WORDS];
-        const int64_t ms = (int64_t)st[(size_t)mid * SW_WORDS + 1];
+        const uint64_t mk = st[(size_t)mid * SWS];
+        const int64_t ms = (int64_t)st[(size_t)mid * SWS + 1];
         if (mk < k || (mk == k && ms < s)) lo = mid + 1;
         else hi = mid;
     }
     return lo;
 }
 
+// a row's NW accumulator words: the identity where the word's gate column is NULL, 1 for a count
+// word, 0 for a padding word, else the value of the word's column
+template <int NW>
+__device__ __forceinline__ void sw_row_words(const SwFoldArgs& a, uint32_t row, uint64_t* out) {
+#pragma unroll
+    for (int w = 0; w < NW; w++) {
+        const int32_t col = a.d.col[w], gate = a.d.gate[w];
+        uint64_t v;
+        if (gate >= 0 && a.nulls[gate][row]) v = session_identity((int32_t)((a.opsp >> (2 * w)) & 3u));
+        else if (col == SW_COL_ONE) v = 1ull;
+        else if (col == SW_COL_PAD) v = 0ull;
+        else {
+            v = a.vals[col][row];
+            if (NW == 1 && a.d.dbl_cmp) v = (uint64_t)dkey(v);
+        }
+        out[w] = v;
+    }
+}
+
+template <int NW>
 __global__ __launch_bounds__(SW_TILE) void k_sw_fold(SwFoldArgs a) {
+    constexpr int SWS = sw_stride(NW);   // words per session
     __shared__ uint64_t sk[SW_TILE];     // sorted keys; then the coalesce chunk's keys
     __shared__ int64_t sts[SW_TILE];     // their timestamps; then the chunk's ends
-    __shared__ uint64_t sa[SW_TILE];     // scan: accumulators
+    __shared__ uint64_t sa[NW][SW_TILE]; // scan: accumulators, word by word
     __shared__ int64_t se[SW_TILE];      // scan: ends
     __shared__ uint32_t sp[SW_TILE];     // positions in the tile (arrival order)
     __shared__ uint32_t sf[SW_TILE];     // scan: segment flags
@@ -257,18 +284,21 @@ __global__ __launch_bounds__(SW_TILE) void k_sw_fold(SwFoldArgs a) {
     __shared__ int32_t hhi[SW_TILE];
     __shared__ int32_t hlen[SW_TILE];    // by head: run length | late-candidate flag << 30
     __shared__ int64_t c_max, c_end;     // coalesce carries: running max end of the last key, open group's end
-    __shared__ uint64_t c_key, c_acc;
+    __shared__ uint64_t c_key, c_acc[NW];
     __shared__ int32_t c_groups, c_valid;
     __shared__ uint32_t n_drop;
 
     const int t = threadIdx.x;
-    const SessionDesc d = a.d;
-    const int64_t gap = d.gap, W = a.watermark;
-    const int op = d.op;
+    const int64_t gap = a.d.gap, W = a.watermark;
+    // the words' merge classes, two bits each, and their identities, derived where they are used:
+    // one scalar register instead of three per word across the scan loops
+    const uint32_t opsp = a.opsp;
+#define SW_OP(w) ((int32_t)((opsp >> (2 * (w))) & 3u))
+#define SW_IDN(w) session_identity(SW_OP(w))
     const int64_t seg0 = a.seg[blockIdx.x], seg1 = a.seg[blockIdx.x + 1];
     if (seg0 >= seg1) return;
-    uint64_t* st = a.state + (size_t)blockIdx.x * a.cap_s * SW_WORDS;
-    uint64_t* M = a.scratch + (size_t)blockIdx.x * ((size_t)a.cap_s + SW_TILE) * SW_WORDS;
+    uint64_t* st = a.state + (size_t)blockIdx.x * a.cap_s * SWS;
+    uint64_t* M = a.scratch + (size_t)blockIdx.x * ((size_t)a.cap_s + SW_TILE) * SWS;
     int ns = a.n_s[blockIdx.x];
     const int ns_at_entry = ns;
     int64_t tile_min_end = INT64_MAX;
@@ -305,8 +335,8 @@ __global__ __launch_bounds__(SW_TILE) void k_sw_fold(SwFoldArgs a) {
         const bool runtail = valid && (t == nt - 1 || sk[t + 1] != mykey);
         if (runtail) atomicOr((uint32_t*)&hlen[hi_], (uint32_t)(rank + 1));
         if (head) {
-            hlo[t] = sw_lower(st, 0, ns, mykey, INT64_MIN);
-            hhi[t] = mykey == ~0ull ? ns : sw_lower(st, 0, ns, mykey + 1, INT64_MIN);
+            hlo[t] = sw_lower<SWS>(st, 0, ns, mykey, INT64_MIN);
+            hhi[t] = mykey == ~0ull ? ns : sw_lower<SWS>(st, 0, ns, mykey + 1, INT64_MIN);
         }
         __syncthreads();
         const bool slow = valid && (hlen[hi_] >> 30) != 0;
@@ -323,27 +353,34 @@ __global__ __launch_bounds__(SW_TILE) void k_sw_fold(SwFoldArgs a) {
         // the run's rows in arrival order, for the late-candidate runs
         ord[t] = valid ? ((uint32_t)hi_ << 20 | (slow ? sp[t] : (uint32_t)rank) << 10 | (uint32_t)rank) : (0x7FF00000u | (uint32_t)t);
         // reverse segmented scan: a tile session's first row gets the reduce of its rows and its end
-        uint64_t myword = session_identity(op);
-        if (valid) myword = session_word(d, d.is_count ? 1ull : a.val[a.perm[base + sp[t]]]);
-        if (t < n2) {
-            sa[t] = myword;
-            se[t] = myts + gap;
-            sf[t] = (!valid || slow || stail) ? 1u : 0u;
+        {
+            uint64_t myword[NW];
+#pragma unroll
+            for (int w = 0; w < NW; w++) myword[w] = SW_IDN(w);
+            if (valid) sw_row_words<NW>(a, a.perm[base + sp[t]], myword);
+            if (t < n2) {
+#pragma unroll
+                for (int w = 0; w < NW; w++) sa[w][t] = myword[w];
+                se[t] = myts + gap;
+                sf[t] = (!valid || slow || stail) ? 1u : 0u;
+            }
         }
         __syncthreads();
-        for (int dd = 1; dd < n2; dd <<= 1) {
+        for (int dd = 1; dd < n2; dd <<= 1) {  // all NW words per step
             const bool take = t + dd < n2 && !sf[t];
-            uint64_t ov = 0;
+            uint64_t ov[NW];
             int64_t oe = 0;
             uint32_t of = 0;
             if (take) {
-                ov = sa[t + dd];
+#pragma unroll
+                for (int w = 0; w < NW; w++) ov[w] = sa[w][t + dd];
                 oe = se[t + dd];
                 of = sf[t + dd];
             }
             __syncthreads();
             if (take) {
-                sa[t] = session_fold(op, sa[t], ov);
+#pragma unroll
+                for (int w = 0; w < NW; w++) sa[w][t] = session_fold(SW_OP(w), sa[w][t], ov[w]);
                 if (oe > se[t]) se[t] = oe;
                 sf[t] = of;
             }
@@ -355,8 +392,8 @@ __global__ __launch_bounds__(SW_TILE) void k_sw_fold(SwFoldArgs a) {
         // starts no tile session is a dead slot.  A late-candidate key's sessions and rows share the
         // region M[lo + head, hi + head + len), which the run's head lane fills below.
         for (int i = t; i < ns; i += SW_TILE) {
-            const uint64_t k = st[(size_t)i * SW_WORDS];
-            const int64_t s = (int64_t)st[(size_t)i * SW_WORDS + 1];
+            const uint64_t k = st[(size_t)i * SWS];
+            const int64_t s = (int64_t)st[(size_t)i * SWS + 1];
             int l = 0, h = nt;  // rows with key < k
             while (l < h) {
                 const int mid = (l + h) >> 1;
@@ -373,37 +410,44 @@ __global__ __launch_bounds__(SW_TILE) void k_sw_fold(SwFoldArgs a) {
                 }
                 before = l;
             }
-            uint64_t* dst = M + (size_t)(i + before) * SW_WORDS;
+            uint64_t* dst = M + (size_t)(i + before) * SWS;
             dst[0] = k;
             dst[1] = (uint64_t)s;
-            dst[2] = st[(size_t)i * SW_WORDS + 2];
-            dst[3] = st[(size_t)i * SW_WORDS + 3];
+            dst[2] = st[(size_t)i * SWS + 2];
+#pragma unroll
+            for (int w = 0; w < NW; w++) dst[3 + w] = st[(size_t)i * SWS + 3 + w];
         }
         if (valid && !slow) {
             // state sessions of the key with start <= ts sort before the row
-            const int c = sw_lower(st, lo, hi, mykey, myts + 1);
-            uint64_t* dst = M + (size_t)(t + c) * SW_WORDS;
+            const int c = sw_lower<SWS>(st, lo, hi, mykey, myts + 1);
+            uint64_t* dst = M + (size_t)(t + c) * SWS;
             dst[0] = mykey;
             dst[1] = (uint64_t)myts;
             dst[2] = shead ? (uint64_t)se[t] : (uint64_t)SW_DEAD;
-            dst[3] = shead ? sa[t] : session_identity(op);
+#pragma unroll
+            for (int w = 0; w < NW; w++) dst[3 + w] = shead ? sa[w][t] : SW_IDN(w);
         }
         __threadfence_block();
         __syncthreads();
         if (head && slow) {
-            uint64_t* reg = M + (size_t)(lo + t) * SW_WORDS;
+            uint64_t* reg = M + (size_t)(lo + t) * SWS;
             int32_t n = hi - lo;
             const int32_t room = n + len;
             for (int r = 0; r < len; r++) {  // arrival order
                 const int u = hi_ + (int)(ord[t + r] & 0x3FFu);
                 const int64_t ts = sts[u];
                 const uint32_t row = a.perm[base + sp[u]];
-                const uint64_t raw = d.is_count ? 1ull : a.val[row];
-                const int rc = session_add(d, W, ts, session_word(d, raw), (int64_t*)reg + 1, (int64_t*)reg + 2, reg + 3, SW_WORDS,
-                                           &n, room);
-                if (rc == 0) {
+                int32_t ops[NW];
+#pragma unroll
+                for (int w = 0; w < NW; w++) ops[w] = SW_OP(w);
+                // the row's words: a late-candidate run's rows are segments of their own in the scan
+                // above, so sa[.][u] still holds the words of the row at sorted index u
+                const int rc = session_add<NW>(gap, ops, W, ts, &sa[0][u], SW_TILE, (int64_t*)reg + 1, (int64_t*)reg + 2, reg + 3, SWS,
+                                               SWS, &n, room);
+                if (rc == 0) {  // dropped: counted (SQL has no side output: late_side is 0)
                     atomicAdd(&n_drop, 1u);
-                    if (a.late_side) {
+                    if (NW == 1 && a.late_side) {
+                        const uint64_t raw = a.d.is_count ? 1ull : a.vals[a.d.col[0]][row];
                         const unsigned long long o = atomicAdd((unsigned long long*)&a.ctrl->n_side, 1ull);
                         if (o < (unsigned long long)a.side_cap) {
                             int64_t* sd = a.side + (size_t)o * SW_SIDE_WORDS;
@@ -418,11 +462,12 @@ __global__ __launch_bounds__(SW_TILE) void k_sw_fold(SwFoldArgs a) {
                 }
             }
             for (int32_t q = 0; q < room; q++) {
-                reg[(size_t)q * SW_WORDS] = mykey;
+                reg[(size_t)q * SWS] = mykey;
                 if (q >= n) {
-                    reg[(size_t)q * SW_WORDS + 1] = (uint64_t)INT64_MAX;
-                    reg[(size_t)q * SW_WORDS + 2] = (uint64_t)SW_DEAD;
-                    reg[(size_t)q * SW_WORDS + 3] = session_identity(op);
+                    reg[(size_t)q * SWS + 1] = (uint64_t)INT64_MAX;
+                    reg[(size_t)q * SWS + 2] = (uint64_t)SW_DEAD;
+#pragma unroll
+                    for (int w = 0; w < NW; w++) reg[(size_t)q * SWS + 3 + w] = SW_IDN(w);
                 }
             }
         }
@@ -441,25 +486,28 @@ __global__ __launch_bounds__(SW_TILE) void k_sw_fold(SwFoldArgs a) {
                 c_max = INT64_MIN;
                 c_end = INT64_MIN;
                 c_key = 0;
-                c_acc = session_identity(op);
+#pragma unroll
+                for (int w = 0; w < NW; w++) c_acc[w] = SW_IDN(w);
             }
             __syncthreads();
             for (int c0 = 0; c0 < L; c0 += SW_TILE) {
                 const int j = c0 + t;
                 const bool in = j < L;
-                uint64_t k = ~0ull, acc = session_identity(op);
+                uint64_t k = ~0ull;
                 int64_t s = INT64_MAX, e = SW_DEAD;
+#pragma unroll
+                for (int w = 0; w < NW; w++) sa[w][t] = SW_IDN(w);  // (free since the previous chunk's last barrier)
                 if (in) {
-                    const uint64_t* src = M + (size_t)j * SW_WORDS;
+                    const uint64_t* src = M + (size_t)j * SWS;
                     k = src[0];
                     s = (int64_t)src[1];
                     e = (int64_t)src[2];
-                    acc = src[3];
+#pragma unroll
+                    for (int w = 0; w < NW; w++) sa[w][t] = src[3 + w];
                 }
                 const bool live = e != SW_DEAD;
                 const uint64_t pk = c_key;
                 const int64_t pmax = c_max, pend = c_end;
-                const uint64_t pacc = c_acc;
                 const int32_t pgroups = c_groups, pvalid = c_valid;
                 sk[t] = k;
                 sts[t] = e;
@@ -484,45 +532,50 @@ __global__ __launch_bounds__(SW_TILE) void k_sw_fold(SwFoldArgs a) {
                 // group index and the reduce of each group
                 int32_t total_heads;
                 const int32_t hcount = sw_block_scan<SW_TILE>(is_head ? 1 : 0, hx, &total_heads);
-                sa[t] = acc;
                 se[t] = e;
                 sf[t] = is_head ? 1u : 0u;
                 __syncthreads();
-                for (int dd = 1; dd < SW_TILE; dd <<= 1) {
+                for (int dd = 1; dd < SW_TILE; dd <<= 1) {  // all NW words per step
                     const bool take = t >= dd && !sf[t];
-                    uint64_t ov = 0;
+                    uint64_t ov[NW];
                     int64_t oe = 0;
                     uint32_t of = 0;
                     if (take) {
-                        ov = sa[t - dd];
+#pragma unroll
+                        for (int w = 0; w < NW; w++) ov[w] = sa[w][t - dd];
                         oe = se[t - dd];
                         of = sf[t - dd];
                     }
                     __syncthreads();
                     if (take) {
-                        sa[t] = session_fold(op, ov, sa[t]);
+#pragma unroll
+                        for (int w = 0; w < NW; w++) sa[w][t] = session_fold(SW_OP(w), ov[w], sa[w][t]);
                         if (oe > se[t]) se[t] = oe;
                         sf[t] = of;
                     }
                     __syncthreads();
                 }
-                uint64_t gacc = sa[t];
+                uint64_t gacc[NW];
+#pragma unroll
+                for (int w = 0; w < NW; w++) gacc[w] = sa[w][t];
                 int64_t gend = se[t];
-                if (hcount == 0) {  // still the group the previous chunk left open
-                    gacc = session_fold(op, pacc, gacc);
+                if (hcount == 0) {  // still the group the previous chunk left open (c_acc: rewritten behind the next barrier)
+#pragma unroll
+                    for (int w = 0; w < NW; w++) gacc[w] = session_fold(SW_OP(w), c_acc[w], gacc[w]);
                     if (pend > gend) gend = pend;
                 }
                 const int32_t g = pgroups + hcount - 1;
                 const bool glast = t == SW_TILE - 1 || j + 1 >= L || hx[t + 1] != hcount;
                 if (pass == 1 && in && g >= 0 && g < a.cap_s) {
-                    uint64_t* dst = st + (size_t)g * SW_WORDS;
+                    uint64_t* dst = st + (size_t)g * SWS;
                     if (is_head) {
                         dst[0] = k;
                         dst[1] = (uint64_t)s;
                     }
                     if (glast) {
                         dst[2] = (uint64_t)gend;
-                        dst[3] = gacc;
+#pragma unroll
+                        for (int w = 0; w < NW; w++) dst[3 + w] = gacc[w];
                     }
                 }
                 __syncthreads();
@@ -531,7 +584,8 @@ __global__ __launch_bounds__(SW_TILE) void k_sw_fold(SwFoldArgs a) {
                     c_key = last_key;
                     c_max = (from_carry && last_key == pk && pmax > incl_last) ? pmax : incl_last;
                     c_groups = pgroups + total_heads;
-                    c_acc = gacc;
+#pragma unroll
+                    for (int w = 0; w < NW; w++) c_acc[w] = gacc[w];
                     c_end = gend;
                 }
                 __threadfence_block();
@@ -560,11 +614,14 @@ __global__ __launch_bounds__(SW_TILE) void k_sw_fold(SwFoldArgs a) {
         __syncthreads();
     }
     if (t == 0 && sts[0] < a.min_end[blockIdx.x]) a.min_end[blockIdx.x] = sts[0];
+#undef SW_OP
+#undef SW_IDN
 }
 
 // ---- the watermark -----------------------------------------------------------------------------
 struct SwAdvArgs {
     SessionDesc d;
+    AggDesc ad;   // SQL: the aggregates over the session's words
     int64_t watermark;
     int32_t cap_s;
     uint64_t* state;
@@ -574,21 +631,24 @@ struct SwAdvArgs {
     int64_t* out_key;
     int64_t* out_ws;
     int64_t* out_we;
-    uint64_t* out_val;
+    uint64_t* out_val[FW_MAX_AGGS];
+    uint32_t* out_null;
     int64_t out_cap;
 };
 
+template <int NW>
 __global__ __launch_bounds__(SW_TILE) void k_sw_advance(SwAdvArgs a) {
+    constexpr int SWS = sw_stride(NW);
     __shared__ int32_t buf[SW_TILE];
     __shared__ int64_t mn[SW_TILE];
     __shared__ unsigned long long out_base;
     const int t = threadIdx.x;
     const int ns = a.n_s[blockIdx.x];
     if (ns == 0 || !session_due(a.min_end[blockIdx.x], a.watermark)) return;  // nothing is due (uniform)
-    uint64_t* st = a.state + (size_t)blockIdx.x * a.cap_s * SW_WORDS;
+    uint64_t* st = a.state + (size_t)blockIdx.x * a.cap_s * SWS;
     // the due sessions, counted first: one device atomic per workgroup claims their output rows
     int32_t mine = 0;
-    for (int i = t; i < ns; i += SW_TILE) mine += session_due((int64_t)st[(size_t)i * SW_WORDS + 2], a.watermark) ? 1 : 0;
+    for (int i = t; i < ns; i += SW_TILE) mine += session_due((int64_t)st[(size_t)i * SWS + 2], a.watermark) ? 1 : 0;
     int32_t n_due;
     sw_block_scan<SW_TILE>(mine, buf, &n_due);
     if (t == 0) {
@@ -601,18 +661,22 @@ __global__ __launch_bounds__(SW_TILE) void k_sw_advance(SwAdvArgs a) {
         }
     }
     __syncthreads();
+    const bool sql = a.d.sql != 0;  // (uniform)
     int32_t fired = 0, kept = 0;
     int64_t min_end = INT64_MAX;
     for (int c0 = 0; c0 < ns; c0 += SW_TILE) {
         const int i = c0 + t;
         const bool in = i < ns;
-        uint64_t k = 0, acc = 0;
+        uint64_t k = 0, acc[NW];
         int64_t s = 0, e = 0;
+#pragma unroll
+        for (int w = 0; w < NW; w++) acc[w] = 0;
         if (in) {
-            k = st[(size_t)i * SW_WORDS];
-            s = (int64_t)st[(size_t)i * SW_WORDS + 1];
-            e = (int64_t)st[(size_t)i * SW_WORDS + 2];
-            acc = st[(size_t)i * SW_WORDS + 3];
+            k = st[(size_t)i * SWS];
+            s = (int64_t)st[(size_t)i * SWS + 1];
+            e = (int64_t)st[(size_t)i * SWS + 2];
+#pragma unroll
+            for (int w = 0; w < NW; w++) acc[w] = st[(size_t)i * SWS + 3 + w];
         }
         const bool due = in && session_due(e, a.watermark);
         int32_t n_f;
@@ -624,14 +688,30 @@ __global__ __launch_bounds__(SW_TILE) void k_sw_advance(SwAdvArgs a) {
                 a.out_key[o] = (int64_t)k;
                 a.out_ws[o] = s;
                 a.out_we[o] = e;
-                a.out_val[o] = session_result(a.d, acc);
+                if (!sql) {
+                    a.out_val[0][o] = session_result(a.d, acc[0]);
+                } else {
+                    // the aggregates index the words at run time: read from the session's own slot,
+                    // which no kept session of this chunk is moved into before the barrier below
+                    uint32_t nm = 0;
+                    for (int g = 0; g < a.ad.n; g++) {
+                        bool isnull;
+                        const uint64_t v = sql_agg_result(a.ad, g, st + (size_t)i * SWS + 3, &isnull);
+                        a.out_val[g][o] = v;
+                        if (isnull) nm |= 1u << g;
+                    }
+                    a.out_null[o] = nm;
+                }
             }
-        } else if (in) {  // stable compaction: the slot is at or before the session's own
-            uint64_t* dst = st + (size_t)(kept + (t + 1 - fi) - 1) * SW_WORDS;
+        }
+        if (sql) __syncthreads();
+        if (in && !due) {  // stable compaction: the slot is at or before the session's own
+            uint64_t* dst = st + (size_t)(kept + (t + 1 - fi) - 1) * SWS;
             dst[0] = k;
             dst[1] = (uint64_t)s;
             dst[2] = (uint64_t)e;
-            dst[3] = acc;
+#pragma unroll
+            for (int w = 0; w < NW; w++) dst[3 + w] = acc[w];
             if (e < min_end) min_end = e;
         }
         fired += n_f;
@@ -672,7 +752,67 @@ int sw_dalloc(T** p, size_t count) {
 
 }  // namespace
 
-int sw_plan(const fw_config& c, SessionOp* op) {
+// the SQL form: SESSION(TABLE t PARTITION BY k, DESCRIPTOR(rowtime), gap) aggregated per session
+static int sw_plan_sql(const fw_config& c, SessionOp* op) {
+    if (c.key_hash == FW_KEYHASH_LONG || c.key_hash == FW_KEYHASH_INT)
+        return set_error(FW_E_INVALID, "FW_KEYHASH_LONG / FW_KEYHASH_INT are DataStream key hashes; a SQL session takes BINROW_BIGINT / "
+                                       "BINROW_INT / PRECOMPUTED keys");
+    if (c.key_hash == FW_KEYHASH_KEYROW)
+        return set_error(FW_E_INVALID, "SQL session windows: key rows (FW_KEYHASH_KEYROW) run on the reference operator");
+    if (c.size_ms < 1) return set_error(FW_E_INVALID, "session gap (size_ms) must be > 0");
+    if (c.size_ms > SW_MAX_GAP) return set_error(FW_E_INVALID, "session gap (size_ms) must be <= 2^40");
+    if (c.slide_ms != 0) return set_error(FW_E_INVALID, "session windows have no slide (slide_ms must be 0)");
+    if (c.offset_ms != 0) return set_error(FW_E_INVALID, "session windows have no offset (offset_ms must be 0)");
+    if (c.allowed_lateness_ms != 0)
+        return set_error(FW_E_INVALID, "SQL session windows have no allowed lateness (allowed_lateness_ms must be 0)");
+    if (c.late_side_output != 0)
+        return set_error(FW_E_INVALID, "SQL session windows have no late side output (late_side_output must be 0)");
+    if (c.ds_first_ordinals) return set_error(FW_E_INVALID, "ds_first_ordinals is a DataStream option (ds_first_ordinals must be 0)");
+    if (c.tz_n != 0)
+        return set_error(FW_E_INVALID, "SQL session windows over TIMESTAMP_LTZ (shift time zones) run on the reference operator (tz_n must be 0)");
+    if (c.agg_phase != FW_PHASE_ONE)
+        return set_error(FW_E_INVALID, "SQL session windows are one-phase (agg_phase must be FW_PHASE_ONE)");
+    if (c.max_batch_rows <= 0 || c.max_batch_rows >= (1ll << 31)) return set_error(FW_E_INVALID, "max_batch_rows must be in (0, 2^31)");
+    if (c.output_capacity <= 0) return set_error(FW_E_INVALID, "output_capacity must be > 0");
+    for (int g = 0; g < c.n_aggs; g++) {
+        const fw_agg_desc& a = c.aggs[g];
+        if (a.kind < FW_AGG_COUNT_STAR || a.kind > FW_AGG_AVG)
+            return set_error(FW_E_INVALID, "SQL session windows: agg %d: kind %d is not COUNT(*) / COUNT / SUM / MIN / MAX / AVG", g, a.kind);
+        if (a.type != FW_T_I64 && a.type != FW_T_I32 && a.type != FW_T_F64)
+            return set_error(FW_E_INVALID, "SQL session windows: agg %d: bad type %d", g, a.type);
+        if ((a.kind == FW_AGG_MIN || a.kind == FW_AGG_MAX) && a.type == FW_T_F64)
+            return set_error(FW_E_INVALID, "SQL session windows: agg %d: MIN / MAX over DOUBLE run on the reference operator (strict "
+                                           "comparison in arrival order)", g);
+    }
+    WordDesc wd{};
+    int rc = plan_aggs(c, &wd, &op->ad, op->slot_col, &op->n_slots);
+    if (rc) return rc;
+    SessionDesc& d = op->d;
+    d = SessionDesc{};
+    d.gap = c.size_ms;
+    d.sql = 1;
+    d.nw = wd.nw;
+    for (int w = 0; w < SW_MAX_NW; w++) {
+        d.ops[w] = CW_ADD_I;
+        d.col[w] = SW_COL_PAD;
+        d.gate[w] = -1;
+        if (w >= wd.nw) continue;
+        d.ops[w] = session_op_of_word(wd.op[w]);
+        if (d.ops[w] < 0)  // W_Q*, W_DN*, W_BY*, W_FIRST, W_CNTV: the sorted fold has no arrival ordinals
+            return set_error(FW_E_INVALID, "SQL session windows: accumulator word op %d is outside the four merge classes", wd.op[w]);
+        d.col[w] = wd.op[w] == W_CNT ? SW_COL_ONE : op->slot_col[wd.col[w]];
+        d.gate[w] = wd.gate[w] >= 0 ? op->slot_col[wd.gate[w]] : -1;
+    }
+    d.op = d.ops[0];
+    op->nw_t = sw_round_nw(d.nw);
+    op->n_out = c.n_aggs;
+    op->val_col = 0;
+    op->late_side = 0;
+    return FW_OK;
+}
+
+// the DataStream form: EventTimeSessionWindows.withGap with one built-in aggregation
+static int sw_plan_ds(const fw_config& c, SessionOp* op) {
     if (c.api != FW_API_DATASTREAM)
         return set_error(FW_E_INVALID, "FW_WIN_SESSION (EventTimeSessionWindows) is a DataStream window: api must be FW_API_DATASTREAM");
     if (c.n_aggs != 1) return set_error(FW_E_INVALID, "session windows take one aggregation (n_aggs == 1), got %d", c.n_aggs);
@@ -708,14 +848,32 @@ int sw_plan(const fw_config& c, SessionOp* op) {
     if (c.output_capacity <= 0) return set_error(FW_E_INVALID, "output_capacity must be > 0");
 
     SessionDesc& d = op->d;
+    d = SessionDesc{};
     d.gap = c.size_ms;
     const bool f = g.type == FW_T_F64;
     d.op = is_count ? CW_ADD_I : g.kind == FW_AGG_SUM ? (f ? CW_ADD_F : CW_ADD_I) : g.kind == FW_AGG_MIN ? CW_MIN : CW_MAX;
     d.vtype = g.type;
     d.is_count = is_count;
     d.dbl_cmp = f && !is_count && (d.op == CW_MIN || d.op == CW_MAX);
+    d.nw = 1;
+    for (int w = 0; w < SW_MAX_NW; w++) {
+        d.ops[w] = CW_ADD_I;
+        d.col[w] = SW_COL_PAD;
+        d.gate[w] = -1;
+    }
+    d.ops[0] = d.op;
+    d.col[0] = is_count ? SW_COL_ONE : g.input_col;
+    op->nw_t = 1;
+    op->n_out = 1;
     op->val_col = is_count ? 0 : g.input_col;
     op->late_side = c.late_side_output;
+    return FW_OK;
+}
+
+int sw_plan(const fw_config& c, SessionOp* op) {
+    const int prc = c.api == FW_API_SQL ? sw_plan_sql(c, op) : sw_plan_ds(c, op);
+    if (prc) return prc;
+    const SessionDesc& d = op->d;
 
     KeySpace& ks = op->ks;
     ks.hash_kind = c.key_hash;
@@ -743,12 +901,23 @@ int sw_plan(const fw_config& c, SessionOp* op) {
     op->out_cap = c.output_capacity;
     op->side_cap = c.late_side_output ? 2 * c.max_batch_rows : 0;
     uint64_t x = 0xcbf29ce484222325ull;  // the semantics fingerprint of the blobs (FNV-1a, as the time windows')
-    for (int64_t v : {(int64_t)c.api, (int64_t)FW_WIN_SESSION, d.gap, (int64_t)d.op, (int64_t)d.vtype, (int64_t)d.is_count,
-                      (int64_t)ks.hash_kind, (int64_t)ks.max_p})
+    auto mix = [&x](int64_t v) {
         for (int b = 0; b < 8; b++) {
             x ^= (uint64_t)((v >> (8 * b)) & 0xff);
             x *= 0x100000001b3ull;
         }
+    };
+    if (!d.sql) {  // (the DataStream blobs' fingerprint since their first build)
+        for (int64_t v : {(int64_t)c.api, (int64_t)FW_WIN_SESSION, d.gap, (int64_t)d.op, (int64_t)d.vtype, (int64_t)d.is_count,
+                          (int64_t)ks.hash_kind, (int64_t)ks.max_p})
+            mix(v);
+    } else {  // the API, every aggregate, the NULL-able columns, key hash, gap, max parallelism
+        for (int64_t v : {(int64_t)c.api, (int64_t)FW_WIN_SESSION, d.gap, (int64_t)c.n_aggs, (int64_t)c.nullable_cols,
+                          (int64_t)ks.hash_kind, (int64_t)ks.max_p})
+            mix(v);
+        for (int g = 0; g < c.n_aggs; g++)
+            for (int64_t v : {(int64_t)c.aggs[g].kind, (int64_t)c.aggs[g].type, (int64_t)c.aggs[g].input_col}) mix(v);
+    }
     op->fingerprint = x;
     op->on = true;
     return FW_OK;
@@ -759,8 +928,9 @@ int sw_allocate(SessionOp* op, hipStream_t stream, Ctrl* ctrl) {
     op->ctrl = ctrl;
     int rc;
     const int n_sb = op->ks.n_sb;
-    if ((rc = sw_dalloc(&op->state, (size_t)n_sb * op->cap_s * SW_WORDS))) return rc;
-    if ((rc = sw_dalloc(&op->scratch, (size_t)n_sb * ((size_t)op->cap_s + SW_TILE) * SW_WORDS))) return rc;
+    const size_t sws = (size_t)sw_stride(op->nw_t);
+    if ((rc = sw_dalloc(&op->state, (size_t)n_sb * op->cap_s * sws))) return rc;
+    if ((rc = sw_dalloc(&op->scratch, (size_t)n_sb * ((size_t)op->cap_s + SW_TILE) * sws))) return rc;
     if ((rc = sw_dalloc(&op->n_s, (size_t)n_sb))) return rc;
     SW_TRY(hipMemsetAsync(op->n_s, 0, (size_t)n_sb * 4, stream));
     if ((rc = sw_dalloc(&op->min_end, (size_t)n_sb))) return rc;
@@ -775,7 +945,8 @@ int sw_allocate(SessionOp* op, hipStream_t stream, Ctrl* ctrl) {
     if ((rc = sw_dalloc(&op->out_key, oc))) return rc;
     if ((rc = sw_dalloc(&op->out_ws, oc))) return rc;
     if ((rc = sw_dalloc(&op->out_we, oc))) return rc;
-    if ((rc = sw_dalloc(&op->out_val, oc))) return rc;
+    for (int g = 0; g < op->n_out; g++)
+        if ((rc = sw_dalloc(&op->out_val[g], oc))) return rc;
     if ((rc = sw_dalloc(&op->out_null, oc))) return rc;
     SW_TRY(hipMemsetAsync(op->out_null, 0, oc * 4, stream));
     if (op->side_cap && (rc = sw_dalloc(&op->side, (size_t)op->side_cap * SW_SIDE_WORDS))) return rc;
@@ -797,13 +968,22 @@ void sw_free(SessionOp* op) {
     hipFree(op->out_key);
     hipFree(op->out_ws);
     hipFree(op->out_we);
-    hipFree(op->out_val);
+    for (int g = 0; g < FW_MAX_AGGS; g++) hipFree(op->out_val[g]);
     hipFree(op->out_null);
     hipFree(op->side);
 }
 
+// the kernels' instance of a handle: NW = sw_round_nw(words of the plan)
+#define SW_LAUNCH_NW(kernel, nw_t, ...)                                            \
+    switch (nw_t) {                                                                \
+        case 1: hipLaunchKernelGGL(kernel<1>, __VA_ARGS__); break;                 \
+        case 2: hipLaunchKernelGGL(kernel<2>, __VA_ARGS__); break;                 \
+        case 4: hipLaunchKernelGGL(kernel<4>, __VA_ARGS__); break;                 \
+        default: hipLaunchKernelGGL(kernel<8>, __VA_ARGS__); break;                \
+    }
+
 int sw_push(SessionOp* op, int64_t watermark, int64_t n, const int64_t* d_key, const int64_t* d_ts, const int32_t* d_khash,
-            const uint64_t* d_val) {
+            const void* const* d_vals, const uint8_t* const* d_nulls) {
     if (n >= (1ll << 32) || op->push_seq >= (1ll << 30))
         return set_error(FW_E_INVALID, "arrival ordinals need < 2^32 rows per call and < 2^30 calls");
     hipStream_t s = op->stream;
@@ -831,10 +1011,15 @@ int sw_push(SessionOp* op, int64_t watermark, int64_t n, const int64_t* d_key, c
         SwFoldArgs fa{};
         fa.key = d_key + o;
         fa.ts = d_ts + o;
-        fa.val = op->d.is_count ? nullptr : d_val + o;
+        for (int w = 0; w < op->d.nw; w++) {  // the columns the words name
+            const int32_t col = op->d.col[w], gate = op->d.gate[w];
+            if (col >= 0) fa.vals[col] = (const uint64_t*)d_vals[col] + o;
+            if (gate >= 0) fa.nulls[gate] = d_nulls[gate] + o;
+        }
         fa.perm = op->perm;
         fa.seg = op->seg;
         fa.d = op->d;
+        for (int w = 0; w < SW_MAX_NW; w++) fa.opsp |= (uint32_t)op->d.ops[w] << (2 * w);
         fa.watermark = watermark;
         fa.cap_s = op->cap_s;
         fa.late_side = op->late_side;
@@ -846,7 +1031,7 @@ int sw_push(SessionOp* op, int64_t watermark, int64_t n, const int64_t* d_key, c
         fa.side = op->side;
         fa.side_cap = op->side_cap;
         fa.ord_base = (op->push_seq << 32) + o;
-        hipLaunchKernelGGL(k_sw_fold, dim3(n_sb), dim3(SW_TILE), 0, s, fa);
+        SW_LAUNCH_NW(k_sw_fold, op->nw_t, dim3(n_sb), dim3(SW_TILE), 0, s, fa);
         SW_TRY(hipGetLastError());
     }
     op->push_seq++;
@@ -865,17 +1050,20 @@ int sw_advance(SessionOp* op, int64_t watermark) {
     a.out_key = op->out_key;
     a.out_ws = op->out_ws;
     a.out_we = op->out_we;
-    a.out_val = op->out_val;
+    a.ad = op->ad;
+    for (int g = 0; g < op->n_out; g++) a.out_val[g] = op->out_val[g];
+    a.out_null = op->out_null;
     a.out_cap = op->out_cap;
-    hipLaunchKernelGGL(k_sw_advance, dim3(op->ks.n_sb), dim3(SW_TILE), 0, op->stream, a);
+    SW_LAUNCH_NW(k_sw_advance, op->nw_t, dim3(op->ks.n_sb), dim3(SW_TILE), 0, op->stream, a);
     SW_TRY(hipGetLastError());
     return FW_OK;
 }
 
-// ---- checkpoint: the library's own blob.  Entries are (key, start, end, acc, key group << 32 |
-// sub-bucket) in no particular order: a restore routes every key again (precomputed-hash keys carry
-// no hash in the state, so they are placed by the recorded sub-bucket and may not be split finer
-// than the snapshot's) and sorts each superbucket's list.
+// ---- checkpoint: the library's own blob.  Entries are (key, start, end, acc[nw_t], key group << 32 |
+// sub-bucket) in no particular order (nw_t = 1 for a DataStream handle: five words, as ever): a
+// restore routes every key again (precomputed-hash keys carry no hash in the state, so they are
+// placed by the recorded sub-bucket and may not be split finer than the snapshot's) and sorts each
+// superbucket's list.
 namespace {
 struct SwHeader {
     uint64_t magic;
@@ -887,7 +1075,7 @@ struct SwHeader {
 };
 const uint64_t SW_MAGIC = 0x464c4b5753573031ull;     // "FLKWSW01"
 const uint64_t SW_KG_MAGIC = 0x464c4b5753473031ull;  // "FLKWSG01"
-constexpr int SW_BLOB_WORDS = SW_WORDS + 1;
+constexpr int SW_MAX_BLOB_WORDS = 3 + SW_MAX_NW + 1;
 }  // namespace
 
 int sw_snapshot(SessionOp* op, int64_t watermark, int32_t key_group, void* buf, int64_t capacity, int64_t* size) {
@@ -904,14 +1092,15 @@ int sw_snapshot(SessionOp* op, int64_t watermark, int32_t key_group, void* buf, 
     std::vector<int32_t> cnt(sb1 - sb0);
     SW_TRY(hipMemcpy(cnt.data(), op->n_s + sb0, cnt.size() * 4, hipMemcpyDeviceToHost));
     std::vector<uint64_t> ent, tmp;
+    const int SWS = sw_stride(op->nw_t);
     int64_t n = 0;
     for (int sb = sb0; sb < sb1; sb++) {
         const int c = cnt[sb - sb0];
         if (c <= 0) continue;
-        tmp.resize((size_t)c * SW_WORDS);
-        SW_TRY(hipMemcpy(tmp.data(), op->state + (size_t)sb * op->cap_s * SW_WORDS, tmp.size() * 8, hipMemcpyDeviceToHost));
+        tmp.resize((size_t)c * SWS);
+        SW_TRY(hipMemcpy(tmp.data(), op->state + (size_t)sb * op->cap_s * SWS, tmp.size() * 8, hipMemcpyDeviceToHost));
         for (int i = 0; i < c; i++) {
-            ent.insert(ent.end(), tmp.begin() + (size_t)i * SW_WORDS, tmp.begin() + (size_t)(i + 1) * SW_WORDS);
+            ent.insert(ent.end(), tmp.begin() + (size_t)i * SWS, tmp.begin() + (size_t)(i + 1) * SWS);
             ent.push_back((uint64_t)(ks.kg_start + (sb >> L)) << 32 | (uint32_t)(sb & ((1 << L) - 1)));
             n++;
         }
@@ -932,6 +1121,7 @@ int sw_restore(SessionOp* op, bool key_group, const void* buf, int64_t size, int
     memcpy(&hd, buf, sizeof hd);
     const KeySpace& ks = op->ks;
     const int L = ks.sb_per_kg_log2;
+    const int NW = op->nw_t, SWS = sw_stride(NW), SW_BLOB_WORDS = SWS + 1;
     if (hd.magic != (key_group ? SW_KG_MAGIC : SW_MAGIC))
         return set_error(FW_E_INVALID, "not a session-window %ssnapshot", key_group ? "key-group " : "");
     if (hd.fingerprint != op->fingerprint) return set_error(FW_E_INVALID, "session-window snapshot of a different operator configuration");
@@ -955,18 +1145,19 @@ int sw_restore(SessionOp* op, bool key_group, const void* buf, int64_t size, int
     struct Ent {
         uint64_t key;
         int64_t start, end;
-        uint64_t acc;
+        uint64_t acc[SW_MAX_NW];
     };
     std::vector<std::vector<Ent>> per(sb1 - sb0);
     const uint64_t* src = (const uint64_t*)((const char*)buf + sizeof hd);
     for (int64_t i = 0; i < hd.n; i++) {
-        uint64_t e[SW_BLOB_WORDS];
-        memcpy(e, src + (size_t)i * SW_BLOB_WORDS, sizeof e);
-        const int kg = (int)(e[4] >> 32);
+        uint64_t e[SW_MAX_BLOB_WORDS];
+        memcpy(e, src + (size_t)i * SW_BLOB_WORDS, (size_t)SW_BLOB_WORDS * 8);
+        const uint64_t where = e[SWS];
+        const int kg = (int)(where >> 32);
         int sb;
         if (ks.hash_kind == KH_PRE) {
             // the recorded sub-bucket holds the low hd.sb_log2 quotient bits; this handle uses the low L of them
-            sb = ((kg - ks.kg_start) << L) + (int)((uint32_t)e[4] & (uint32_t)((1 << L) - 1));
+            sb = ((kg - ks.kg_start) << L) + (int)((uint32_t)where & (uint32_t)((1 << L) - 1));
         } else {
             uint32_t m;
             sb = route_key(ks, (int64_t)e[0], 0, &m);
@@ -974,7 +1165,9 @@ int sw_restore(SessionOp* op, bool key_group, const void* buf, int64_t size, int
                 return set_error(FW_E_INVALID, "entry key does not belong to key group %d", kg);
         }
         if (sb < sb0 || sb >= sb1) return set_error(FW_E_INVALID, "snapshot entry of key group %d is not owned by this subtask", kg);
-        per[sb - sb0].push_back(Ent{e[0], (int64_t)e[1], (int64_t)e[2], e[3]});
+        Ent en{e[0], (int64_t)e[1], (int64_t)e[2], {}};
+        for (int w = 0; w < NW; w++) en.acc[w] = e[3 + w];
+        per[sb - sb0].push_back(en);
     }
     std::vector<uint64_t> tmp;
     std::vector<int64_t> mins(sb1 - sb0, INT64_MAX);
@@ -988,12 +1181,12 @@ int sw_restore(SessionOp* op, bool key_group, const void* buf, int64_t size, int
             tmp.push_back(x.key);
             tmp.push_back((uint64_t)x.start);
             tmp.push_back((uint64_t)x.end);
-            tmp.push_back(x.acc);
+            for (int w = 0; w < NW; w++) tmp.push_back(x.acc[w]);
             mins[sb - sb0] = std::min(mins[sb - sb0], x.end);
         }
         cnt[sb - sb0] = (int32_t)v.size();
         if (!tmp.empty())
-            SW_TRY(hipMemcpy(op->state + (size_t)sb * op->cap_s * SW_WORDS, tmp.data(), tmp.size() * 8, hipMemcpyHostToDevice));
+            SW_TRY(hipMemcpy(op->state + (size_t)sb * op->cap_s * SWS, tmp.data(), tmp.size() * 8, hipMemcpyHostToDevice));
     }
     SW_TRY(hipMemcpy(op->n_s + sb0, cnt.data(), cnt.size() * 4, hipMemcpyHostToDevice));
     SW_TRY(hipMemcpy(op->min_end + sb0, mins.data(), mins.size() * 8, hipMemcpyHostToDevice));

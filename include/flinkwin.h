@@ -123,7 +123,28 @@ typedef enum {
        watermark and do not depend on the superbucket split.  The async / device / segment result
        calls, the segment and key-row pushes, fw_advance_device, fw_first_element_events, the
        heap-format and fw_ds_* key-group calls and the profiling calls return FW_E_INVALID on a
-       session handle.  A full session list raises FW_ERRF_STATE and drops the tile's rows. */
+       session handle.  A full session list raises FW_ERRF_STATE and drops the tile's rows.
+
+       v11 (additive), with api == FW_API_SQL: the SESSION window TVF aggregate,
+       SESSION(TABLE t PARTITION BY k, DESCRIPTOR(rowtime), gap) grouped by (k, window_start,
+       window_end), event time on a TIMESTAMP rowtime.  It replaces the unslicing window aggregate
+       (recalled, parity unpinned: UnsliceWindowAggProcessor, UnsliceAssigners.SessionUnsliceAssigner,
+       MergingWindowProcessFunction.assignActualWindows, MergingFunctionImpl.merge,
+       WindowAggOperator.processWatermark).  The interval rules are the ones above; a late row that
+       intersects no session of its key is dropped and counted (num_late_records_dropped), there is
+       no side output.  size_ms carries the gap; n_aggs in 1 .. FW_MAX_AGGS of COUNT_STAR / COUNT /
+       SUM / MIN / MAX / AVG over I64 / I32 / F64, except MIN / MAX over F64; nullable_cols is
+       honoured (pushes carry the null-flag columns; a NULL value still opens or extends its
+       session).  The plan may use at most 8 accumulator words.  Keys are BINROW_BIGINT, BINROW_INT
+       or PRECOMPUTED (LONG / INT are DataStream key hashes; KEYROW is refused).  slide_ms,
+       offset_ms, allowed_lateness_ms, late_side_output, ds_first_ordinals and tz_n must be 0,
+       agg_phase FW_PHASE_ONE; count_star_index may name a COUNT and is otherwise ignored (a
+       session always holds a row).  fw_results / fw_results_reset return key, window_start (the
+       session's smallest rowtime), window_end (its largest rowtime + gap), values[a] per aggregate
+       and the null mask (SUM / MIN / MAX without a non-NULL input and AVG over a zero count are
+       NULL, COUNT(col) is 0); first_ord is NULL.  Snapshot blobs carry every accumulator word and
+       restore only into a handle of the same aggregate list.  The calls a DataStream session handle
+       refuses are refused here too, fw_late_records included. */
     FW_WIN_SESSION = 4
 } fw_window_kind;
 
@@ -774,6 +795,22 @@ int fw_host_count_step(const fw_config* cfg, int64_t index, int64_t* slice, int3
    configuration fw_create would reject, FW_E_CAPACITY when a new session does not fit. */
 int fw_host_session_add(const fw_config* cfg, int64_t watermark, int64_t ts, int64_t value, int64_t* starts, int64_t* ends,
                         int64_t* accs, int32_t* n, int32_t capacity, int32_t* outcome);
+/* v11 (additive): the same for a SQL session configuration (FW_WIN_SESSION with FW_API_SQL), whose
+   sessions carry the accumulator words of the aggregate list.  fw_host_sql_session_words returns
+   the number of words nw the plan uses (1 .. 8; the device rounds it up to 1, 2, 4 or 8).
+   fw_host_sql_session_add applies one row of one key -- values[n_value_cols] (DOUBLE as bits) and
+   nulls[n_value_cols] (non-zero: NULL; read for the nullable columns only, may be NULL when there
+   are none) -- to that key's *n sessions: starts / ends as above, session i's words at
+   acc_words[i * nw ..].  A NULL value still opens or extends its session; only the aggregates
+   skip it.  *outcome = 1 kept, 0 dropped as late; FW_E_CAPACITY when a new session does not fit.
+   fw_host_sql_session_result turns one session's words into the emitted aggregate values
+   (values[n_aggs], a NULL's value is 0) and the null mask (bit g: aggregate g is NULL).  All three
+   return FW_E_INVALID with fw_create's message for a configuration fw_create would reject, and for
+   a configuration that is not a SQL session.  They run the routines the device code calls. */
+int fw_host_sql_session_words(const fw_config* cfg, int32_t* nw);
+int fw_host_sql_session_add(const fw_config* cfg, int64_t watermark, int64_t ts, const int64_t* values, const uint8_t* nulls,
+                            int64_t* starts, int64_t* ends, int64_t* acc_words, int32_t* n, int32_t capacity, int32_t* outcome);
+int fw_host_sql_session_result(const fw_config* cfg, const int64_t* acc_words, int64_t* values, uint32_t* null_mask);
 
 #ifdef __cplusplus
 }

@@ -9,7 +9,15 @@ tile).  Push s carries event times in [10 s * s, 10 s * (s + 1)) and is followed
 the advance and the (stream-ordered) result reset; it is timed on the host around a handle sync.
 Prints one JSON line per stream.
 
-    python tools/session_window_bench.py [--rows N] [--warmup 5] [--steps 20] [--streams uniform,zipf,hot]
+    python tools/session_window_bench.py [--rows N] [--warmup 5] [--steps 20] [--streams uniform,zipf,hot] [--sql AGGS]
+
+--sql AGGS runs the same streams through a SQL session handle (the SESSION window TVF aggregate,
+BINROW_BIGINT keys) instead: AGGS is a comma-separated aggregate list over two value columns, a
+NOT NULL BIGINT ``a`` and a NULL-able DOUBLE ``b`` (a tenth of its rows are NULL), out of
+COUNT(*), COUNT(b), SUM(a), MIN(a), MAX(a), AVG(a), SUM(b), AVG(b); the line then also reports the
+accumulator words of the plan.  SUM(a) plans one word, SUM(a),COUNT(*) two,
+SUM(a),COUNT(*),MIN(a),MAX(a) four and SUM(a),MIN(a),MAX(a),COUNT(*),AVG(b),SUM(b),COUNT(b) six,
+which the eight-word kernels carry.
 """
 import argparse
 import json
@@ -39,17 +47,33 @@ def _keys(kind, n_keys, rows, pushes, device):
             for _ in range(pushes)]
 
 
-def run(kind, rows, warmup, steps, n_keys=10**6):
+_SQL_AGGS = {"COUNT(*)": ("COUNT_STAR", 0, "BIGINT"), "COUNT(b)": ("COUNT", 1, "DOUBLE"), "SUM(a)": ("SUM", 0, "BIGINT"),
+             "MIN(a)": ("MIN", 0, "BIGINT"), "MAX(a)": ("MAX", 0, "BIGINT"), "AVG(a)": ("AVG", 0, "BIGINT"),
+             "SUM(b)": ("SUM", 1, "DOUBLE"), "AVG(b)": ("AVG", 1, "DOUBLE")}
+
+
+def run(kind, rows, warmup, steps, n_keys=10**6, sql=None):
     import torch
+    from flink_amd import abi
     from flink_amd.datastream import SessionWindowOperator
+    from flink_amd.table import SessionWindowAggOperator
     dev = torch.device("cuda", 0)
     if kind == "hot":  # a step of the hot key takes far longer than the others: fewer of them
         warmup, steps = min(warmup, 1), min(steps, 3)
-    op = SessionWindowOperator(GAP_MS, ("sum", "LONG"), state_capacity=1 << 21, max_batch_rows=rows,
-                               output_capacity=1 << 22).open()
+    if sql:
+        op = SessionWindowAggOperator(GAP_MS, [_SQL_AGGS[a] for a in sql.split(",")], ["BIGINT", "DOUBLE"], nullable_cols=(1,),
+                                      state_capacity=1 << 21, max_batch_rows=rows, output_capacity=1 << 22).open()
+    else:
+        op = SessionWindowOperator(GAP_MS, ("sum", "LONG"), state_capacity=1 << 21, max_batch_rows=rows,
+                                   output_capacity=1 << 22).open()
     try:
         keys = _keys(kind, n_keys, rows, min(warmup + steps, 8), dev)
         vals = torch.randint(1, 10**6, (rows,), device=dev, dtype=torch.int64)
+        if sql:
+            g = torch.Generator(device=dev)
+            g.manual_seed(99)
+            dbl = torch.rand(rows, generator=g, device=dev, dtype=torch.float64) + 0.5
+            isnull = (torch.rand(rows, generator=g, device=dev) < 0.1).to(torch.uint8)
         offs = torch.randint(0, SPAN_MS, (rows,), device=dev, dtype=torch.int64)
         torch.cuda.synchronize()
         ms = []
@@ -57,7 +81,10 @@ def run(kind, rows, warmup, steps, n_keys=10**6):
             ts = offs + s * SPAN_MS
             torch.cuda.synchronize()
             t0 = time.perf_counter()
-            op.process_batch_device(keys[s % len(keys)], ts, vals)
+            if sql:
+                op.process_batch_device(keys[s % len(keys)], ts, [vals, dbl], None, nulls={1: isnull})
+            else:
+                op.process_batch_device(keys[s % len(keys)], ts, vals)
             op.handle.advance((s + 1) * SPAN_MS - 1)
             op.handle.reset_results()  # the rows count as consumed (stream-ordered)
             op.handle.sync()
@@ -65,7 +92,12 @@ def run(kind, rows, warmup, steps, n_keys=10**6):
                 ms.append((time.perf_counter() - t0) * 1e3)
         ms = np.array(ms)
         st = op.handle.stats()
-        return {"tool": "session_window_bench", "stream": kind, "window": "EventTimeSessionWindows.withGap(3s).sum LONG",
+        window = "EventTimeSessionWindows.withGap(3s).sum LONG"
+        extra = {}
+        if sql:
+            window = "SQL SESSION(gap 3s) " + sql
+            extra = {"accumulator_words": abi.host_sql_session_words(op.cfg)}
+        return {"tool": "session_window_bench", "stream": kind, "window": window, **extra,
                 "rows_per_push": rows, "keys": 1 if kind == "hot" else n_keys, "warmup": warmup, "steps": steps,
                 "ms_per_push_median": round(float(np.median(ms)), 4), "ms_per_push_min": round(float(ms.min()), 4),
                 "events_per_s": round(rows / (float(np.median(ms)) * 1e-3)), "fired_windows": st["num_fired_windows"],
@@ -81,9 +113,12 @@ def main():
     ap.add_argument("--warmup", type=int, default=5)
     ap.add_argument("--steps", type=int, default=20)
     ap.add_argument("--streams", default="uniform,zipf,hot")
+    ap.add_argument("--sql", default=None, metavar="AGGS", help="run a SQL session handle with this aggregate list")
     a = ap.parse_args()
+    if a.sql and any(x not in _SQL_AGGS for x in a.sql.split(",")):
+        ap.error("--sql takes a comma-separated list out of " + ", ".join(_SQL_AGGS))
     for kind in a.streams.split(","):
-        print(json.dumps(run(kind, a.rows, a.warmup, a.steps)), flush=True)
+        print(json.dumps(run(kind, a.rows, a.warmup, a.steps, sql=a.sql)), flush=True)
 
 
 if __name__ == "__main__":
