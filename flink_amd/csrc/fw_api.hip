@@ -1026,12 +1026,13 @@ int read_ctrl(fw_handle* h, Ctrl* out) {
     HIP_TRY(hipMemcpyAsync(out, h->ctrl, sizeof(Ctrl), hipMemcpyDeviceToHost, h->stream));
     HIP_TRY(hipStreamSynchronize(h->stream));
     if (out->error) {
-        return fail(FW_E_CAPACITY, "device error (bits 0x%x:%s%s%s%s%s%s%s)", out->error,
+        return fail(FW_E_CAPACITY, "device error (bits 0x%x:%s%s%s%s%s%s%s%s)", out->error,
                     out->error & ERR_CHUNKS ? " partial-buffer" : "", out->error & ERR_STATE ? " state-table" : "",
                     out->error & ERR_OUTPUT ? " result-buffer" : "", out->error & ERR_TREQ ? " timer-requests" : "",
                     out->error & ERR_KEYGROUP ? " key-group-not-owned" : "",
                     out->error & ERR_LATE ? " late-rows (call fw_late_records more often)" : "",
-                    out->error & ERR_ORDEV ? " first-element-events (call fw_first_element_events after each advance)" : "");
+                    out->error & ERR_ORDEV ? " first-element-events (call fw_first_element_events after each advance)" : "",
+                    out->error & ERR_KEYROW ? " key-rows (table full, or a row over key_row_max_bytes)" : "");
     }
     return FW_OK;
 }
@@ -1059,6 +1060,7 @@ MergeArgs merge_args(fw_handle* h, int64_t wm, int force) {
     a.max_nch = h->cell_cols;
     a.cap_rows = h->cap_rows;
     a.treq = h->treq;
+    a.treq_cap = h->treq_cap;
     a.state = h->state;
     a.state_count = h->state_count;
     a.sb_min_timer = h->sb_min_timer;
@@ -1760,7 +1762,7 @@ int fw_advance(fw_handle* h, int64_t watermark) {
     if (h->keyrow)  // key rows no state / partial / timer request / unread result holds any more
         HIP_TRY(launch_kr_collect(h->kr, h->ctrl, h->state, h->state_count, h->sb_nar, h->nw_t, h->ks.n_sb, h->cap_e, h->pwe,
                                   2 + h->nw_t, h->parts, h->cap_rows, h->treq, h->out_key, h->sb_out, h->slab_cap,
-                                  h->stream));
+                                  h->treq_cap, h->out_cap, h->stream));
     if (watermark > h->host_cur) h->host_cur = watermark;
     return FW_OK;
 }
@@ -1784,7 +1786,7 @@ int fw_advance_device(fw_handle* h, const int64_t* d_watermark) {
     if (h->keyrow)
         HIP_TRY(launch_kr_collect(h->kr, h->ctrl, h->state, h->state_count, h->sb_nar, h->nw_t, h->ks.n_sb, h->cap_e, h->pwe,
                                   2 + h->nw_t, h->parts, h->cap_rows, h->treq, h->out_key, h->sb_out, h->slab_cap,
-                                  h->stream));
+                                  h->treq_cap, h->out_cap, h->stream));
     return FW_OK;
 }
 
@@ -1895,12 +1897,9 @@ int fw_results(fw_handle* h, fw_result* out, int copy_to_host) {
     Ctrl c;
     int rc = read_ctrl(h, &c);
     if (rc) return rc;
-    int64_t total = 0;
-    HIP_TRY(hipMemcpy(&total, h->coff + h->ks.n_sb + 1, sizeof total, hipMemcpyDeviceToHost));
-    if (total > h->out_cap)
-        return fail(FW_E_CAPACITY, "%lld result rows exceed output_capacity %lld (read results more often)",
-                    (long long)total, (long long)h->out_cap);
-    const int64_t n = total;
+    // (more rows than the result columns hold: the compaction raised ERR_OUTPUT, which failed read_ctrl)
+    int64_t n = 0;  // the rows the compaction copied, <= out_cap
+    HIP_TRY(hipMemcpy(&n, h->coff + h->ks.n_sb + 1, sizeof n, hipMemcpyDeviceToHost));
     memset(out, 0, sizeof *out);
     out->n = n;
     const int na = h->n_out;
@@ -2304,7 +2303,7 @@ int fw_get_stats(fw_handle* h, fw_stats* out) {
     out->compact_chunks = (int64_t)c.compact_chunks;
     out->peak_superbucket_entries = (int64_t)c.peak_entries;
     out->superbucket_capacity = h->cap_e;
-    out->key_rows = h->keyrow ? c.kr_next_id - std::max<int64_t>(0, c.kr_free_count - std::min(c.kr_free_cursor, c.kr_free_count)) : 0;
+    out->key_rows = h->keyrow ? std::min(c.kr_next_id, h->kr.cap_ids) - std::max<int64_t>(0, c.kr_free_count - std::min(c.kr_free_cursor, c.kr_free_count)) : 0;
     out->key_row_collections = c.kr_collections;
     return FW_OK;
 }
@@ -2455,28 +2454,38 @@ static int kr_section(fw_handle* h, const uint64_t* entries, int64_t n, int pwe,
     return FW_OK;
 }
 
-// interns a blob's key-row section: old id -> this handle's id (and its hash); *used = words read
-static int kr_restore_section(fw_handle* h, const uint64_t* sec, int64_t avail_words, std::vector<std::pair<int64_t, int64_t>>* map,
-                              std::vector<int32_t>* hashes, int64_t* used) {
-    map->clear();
-    hashes->clear();
+// a blob's key-row section on the host: the ids it names, their images and offsets; *used = words read
+static int kr_parse_section(const uint64_t* sec, int64_t avail_words, std::vector<int64_t>* old, std::vector<int64_t>* off,
+                            std::vector<uint64_t>* bytes, int64_t* used) {
+    old->clear();
+    off->assign(1, 0);
+    bytes->clear();
     if (avail_words < 1) return fail(FW_E_INVALID, "key-row section truncated");
     const int64_t nk = (int64_t)sec[0];
     int64_t p = 1;
-    std::vector<int64_t> off(1, 0);
-    std::vector<uint64_t> bytes;
-    std::vector<int64_t> old;
     for (int64_t k = 0; k < nk; k++) {
         if (p + 2 > avail_words) return fail(FW_E_INVALID, "key-row section truncated");
         const int64_t id = (int64_t)sec[p];
         const int64_t len = (int64_t)(uint32_t)sec[p + 1];
         if ((len & 7) || p + 2 + len / 8 > avail_words) return fail(FW_E_INVALID, "key-row section truncated");
-        old.push_back(id);
-        bytes.insert(bytes.end(), sec + p + 2, sec + p + 2 + len / 8);
-        off.push_back(off.back() + len);
+        old->push_back(id);
+        bytes->insert(bytes->end(), sec + p + 2, sec + p + 2 + len / 8);
+        off->push_back(off->back() + len);
         p += 2 + len / 8;
     }
     *used = p;
+    return FW_OK;
+}
+
+// interns a blob's key-row section: old id -> this handle's id (and its hash); *used = words read
+static int kr_restore_section(fw_handle* h, const uint64_t* sec, int64_t avail_words, std::vector<std::pair<int64_t, int64_t>>* map,
+                              std::vector<int32_t>* hashes, int64_t* used) {
+    map->clear();
+    hashes->clear();
+    std::vector<int64_t> off, old;
+    std::vector<uint64_t> bytes;
+    if (const int prc = kr_parse_section(sec, avail_words, &old, &off, &bytes, used)) return prc;
+    const int64_t nk = (int64_t)old.size();
     if (nk == 0) return FW_OK;
     int64_t* d_off = nullptr;
     uint8_t* d_bytes = nullptr;
@@ -2578,11 +2587,36 @@ int fw_restore(fw_handle* h, const void* buf, int64_t size) {
     memcpy(ent.data(), p, ent.size() * 8);
     int rc;
     if (h->keyrow) {  // this handle's ids for the blob's key rows
+        std::vector<uint64_t> sec((size_t)((size - ent_end) / 8));
+        memcpy(sec.data(), (const char*)buf + ent_end, sec.size() * 8);
+        {  // the blob is checked before the handle changes: a blob that fails here leaves it as it was
+            std::vector<int64_t> old, off;
+            std::vector<uint64_t> bytes;
+            int64_t used = 0;
+            if ((rc = kr_parse_section(sec.data(), (int64_t)sec.size(), &old, &off, &bytes, &used))) return rc;
+            if ((int64_t)old.size() > h->kr.cap_ids)
+                return fail(FW_E_CAPACITY, "snapshot holds %lld key rows, the table %lld", (long long)old.size(), (long long)h->kr.cap_ids);
+            for (size_t k = 0; k + 1 < off.size(); k++)
+                if (off[k + 1] - off[k] < 8 || off[k + 1] - off[k] > h->kr.max_len)
+                    return fail(FW_E_INVALID, "snapshot key row of %lld bytes (key_row_max_bytes %d)", (long long)(off[k + 1] - off[k]), (int)h->kr.max_len);
+            std::sort(old.begin(), old.end());
+            for (int64_t i = 0; i < hd.live; i++)
+                if (!std::binary_search(old.begin(), old.end(), (int64_t)ent[(size_t)i * pwe]))
+                    return fail(FW_E_INVALID, "snapshot entry without its key row");
+        }
+        // Everything that holds an id of before the restore goes with it (state, pending pushes, timer
+        // requests, uncollected rows): the table starts empty.  A handle whose table was full restores
+        // like a fresh one, and a device error of before the restore does not fail the interning.
+        HIP_TRY(hipStreamSynchronize(h->stream));
+        Ctrl k;
+        HIP_TRY(hipMemcpy(&k, h->ctrl, sizeof k, hipMemcpyDeviceToHost));
+        k.kr_next_id = k.kr_free_count = k.kr_free_cursor = 0;
+        k.error = 0;
+        HIP_TRY(hipMemcpy(h->ctrl, &k, sizeof k, hipMemcpyHostToDevice));
+        HIP_TRY(hipMemsetAsync(h->kr.slots, 0, sizeof(uint32_t) * h->kr.n_slots, h->stream));
         std::vector<std::pair<int64_t, int64_t>> map;
         std::vector<int32_t> hashes;
         int64_t used = 0;
-        std::vector<uint64_t> sec((size_t)((size - ent_end) / 8));
-        memcpy(sec.data(), (const char*)buf + ent_end, sec.size() * 8);
         if ((rc = kr_restore_section(h, sec.data(), (int64_t)sec.size(), &map, &hashes, &used))) return rc;
         for (int64_t i = 0; i < hd.live; i++) {
             size_t pos;
@@ -2642,6 +2676,9 @@ int fw_restore(fw_handle* h, const void* buf, int64_t size) {
     h->dev_cur = c.cur;
     h->dev_ntp = INT64_MIN;
     h->push_seq = std::max<int64_t>(h->push_seq, hd.push_seq);
+    // rows emitted before the restore and not collected go with the rest (a restored operator starts
+    // with none): out_count went with the control block, the next merge launch starts the slabs afresh
+    h->reset_pending = true;
     return FW_OK;
 }
 
@@ -2800,6 +2837,7 @@ int fw_restore_key_group(fw_handle* h, const void* buf, int64_t size) {
     h->dev_ntp = INT64_MIN;
     HIP_TRY(hipMemcpy(h->ctrl, &c, sizeof c, hipMemcpyHostToDevice));
     h->push_seq = std::max<int64_t>(h->push_seq, hd.push_seq);
+    h->reset_pending = true;  // as fw_restore: uncollected rows of before the restore are dropped
     return FW_OK;
 }
 

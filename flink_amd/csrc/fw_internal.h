@@ -378,8 +378,11 @@ constexpr int HB_R = 8;       // slices per HOP block entry
 // without data -- its mask bit clear -- holds the word's identity, restored on load.  One
 // accumulator word: 11 words wide, 6 at level 1, 4 at level 2; two: 19, 10, 6.
 constexpr int HB_LEVELS = 3;  // 0: wide (3 + HB_R * nw words), 1: int32 slots, 2: int16 slots
-constexpr int HB_HDR_BYTES = 14;  // narrow entry header: key, block index, flags
+// narrow entry header: key (8 B), block index (4 B), flags (2 B), 2 B unused; a multiple of 4, so that
+// no slot straddles two of the entry's 8-byte words (hb_load_narrow / hb_store_narrow shift within one)
+constexpr int HB_HDR_BYTES = 16;
 constexpr int hb_slot_bytes(int level) { return level == 1 ? 4 : 2; }
+static_assert(HB_HDR_BYTES % 4 == 0, "int32 slots of a narrow HOP block entry must not straddle its 8-byte words");
 constexpr int hb_narrow_words(int nw, int level = 1) { return (HB_HDR_BYTES + hb_slot_bytes(level) * HB_R * nw + 7) / 8; }
 constexpr uint32_t HB_MASK_SHIFT = 8;  // block entry flag bits 8.. : slot i holds data
 
@@ -703,7 +706,8 @@ struct MergeArgs {
     const int32_t* slot_nch;
     int64_t max_nch;
     int64_t cap_rows;
-    const int64_t* treq;
+    const int64_t* treq;     // [treq_cap] (key, window, sb) triples; Ctrl::n_treq may count past treq_cap
+    int64_t treq_cap;
     uint64_t* state;         // [n_sb][cap_e][3 + nw] words: key, slice, flags, acc...
     int32_t* state_count;    // live entries per superbucket
     int64_t* sb_min_timer;   // min windowEnd with a timer per superbucket (INT64_MAX: none)
@@ -853,7 +857,7 @@ hipError_t launch_kr_collect(const KeyRowTable& t, Ctrl* c, const uint64_t* stat
                              const uint8_t* sb_nar, int32_t hb_nw,
                              int32_t n_sb, int32_t cap_e, int32_t pwe, int32_t pw, const uint64_t* parts,
                              int64_t cap_rows, const int64_t* treq, const int64_t* out_key, const int32_t* sb_out,
-                             int64_t slab_cap, hipStream_t s);
+                             int64_t slab_cap, int64_t treq_cap, int64_t out_cap, hipStream_t s);
 hipError_t launch_kr_result_rows(const KeyRowTable& t, const int64_t* res_key, const int64_t* n_ptr, int64_t cap,
                                  int32_t* len, uint64_t* img, int32_t stride_words, hipStream_t s);
 

@@ -82,10 +82,16 @@ __global__ __launch_bounds__(BLOCK) void k_compact(CompactArgs a, int32_t R) {
     const int64_t ovf = (int64_t)min(a.ctrl->out_count[a.ctrl->ovf_sel & 1], (uint64_t)a.res_cap);
     copy((int64_t)a.n_sb * a.slab_cap, base, ovf);
     if (threadIdx.x == 0) {
-        a.off[a.n_sb] = base;          // slab rows
-        a.off[a.n_sb + 1] = base + ovf;  // total rows
+        // slabs and region together hold up to about three times res_cap rows without claim_out_row
+        // raising ERR_OUTPUT: the rows past res_cap are dropped here, so the bit is raised here.  The
+        // device-side count (fw_results_device's *d_n) is the rows copied; the host's copy of the
+        // count (fw_results_ready) stays the full total, which is its capacity check.
+        const int64_t total = base + ovf;
+        if (total > a.res_cap) __hip_atomic_fetch_or(&a.ctrl->error, ERR_OUTPUT, __ATOMIC_RELAXED, DEV_SCOPE);
+        a.off[a.n_sb] = base;                       // slab rows
+        a.off[a.n_sb + 1] = min(total, a.res_cap);  // rows copied
         if (a.host_n)  // fw_results_async: the count, next to the rows in mapped host memory (vector store)
-            __hip_atomic_store(a.host_n, base + ovf, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+            __hip_atomic_store(a.host_n, total, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
     }
 }
 

@@ -121,7 +121,7 @@ __global__ void k_kr_gc_begin(KeyRowTable t, Ctrl* c) {
 }
 
 __device__ __forceinline__ void kr_mark(const KeyRowTable& t, const Ctrl* c, int64_t id, uint32_t ep) {
-    if (id >= 0 && id < c->kr_next_id) t.mark[id] = ep;  // stale rows may hold anything: bounds
+    if (id >= 0 && id < min(c->kr_next_id, t.cap_ids)) t.mark[id] = ep;  // stale rows may hold anything: bounds
 }
 
 struct KrMarkArgs {
@@ -134,12 +134,16 @@ struct KrMarkArgs {
     int32_t n_sb, cap_e, pwe, pw;
     const uint64_t* parts;  // FW_MAX_PENDING slots of cap_rows rows of pw words
     int64_t cap_rows;
-    const int64_t* treq;    // (key, window, sb) triples
+    const int64_t* treq;    // [treq_cap] (key, window, sb) triples
+    int64_t treq_cap;
     const int64_t* out_key; // result slabs [n_sb][slab_cap] + overflow
     const int32_t* sb_out;
     int64_t slab_cap;
+    int64_t out_cap;        // rows of the overflow region
 };
 
+// The counters the ingest, the merge and kr_alloc bump (n_treq, out_count, kr_next_id) count on past
+// their buffers' capacities once the error bit is raised: every loop below clamps them.
 // mark every id a live state entry, pending partial row, timer request or unread result holds:
 // block b < n_sb marks superbucket b's entries and slab rows; the rest stride over the partials
 __global__ void k_kr_gc_mark(KrMarkArgs a) {
@@ -161,20 +165,21 @@ __global__ void k_kr_gc_mark(KrMarkArgs a) {
     const int64_t nrows = c->pending_pushes * a.cap_rows;  // every row of a pending slot (stale rows too)
     for (int64_t r = me * blockDim.x + threadIdx.x; r < nrows; r += nb * blockDim.x)
         kr_mark(a.t, c, (int64_t)a.parts[(size_t)r * a.pw], ep);
-    const int64_t nt = c->n_treq;
+    const int64_t nt = min(c->n_treq, a.treq_cap);
     for (int64_t r = me * blockDim.x + threadIdx.x; r < nt; r += nb * blockDim.x) kr_mark(a.t, c, a.treq[3 * r], ep);
-    const int64_t novf = (int64_t)c->out_count[c->ovf_sel & 1];
+    const int64_t novf = (int64_t)min(c->out_count[c->ovf_sel & 1], (uint64_t)a.out_cap);
     for (int64_t r = me * blockDim.x + threadIdx.x; r < novf; r += nb * blockDim.x)
         kr_mark(a.t, c, a.out_key[(size_t)a.n_sb * a.slab_cap + r], ep);
 }
 
-// sweep: every id below kr_next_id not marked goes to the free list; the index is cleared
+// sweep: every id handed out (below kr_next_id, at most cap_ids) not marked goes to the free list;
+// the index is cleared
 __global__ void k_kr_gc_sweep(KeyRowTable t, Ctrl* c) {
     if (!c->kr_gc) return;
     const uint32_t ep = c->kr_epoch;
     const int64_t g = (int64_t)blockIdx.x * blockDim.x + threadIdx.x, stride = (int64_t)gridDim.x * blockDim.x;
     for (int64_t s = g; s < t.n_slots; s += stride) t.slots[s] = 0u;
-    const int64_t n = c->kr_next_id;
+    const int64_t n = min(c->kr_next_id, t.cap_ids);
     for (int64_t id = g; id < n; id += stride) {
         if (t.mark[id] == ep) continue;
         const int64_t p = __hip_atomic_fetch_add(&c->kr_free_count, (int64_t)1, __ATOMIC_RELAXED, DEV_SCOPE);
@@ -187,7 +192,7 @@ __global__ void k_kr_gc_rebuild(KeyRowTable t, Ctrl* c) {
     if (!c->kr_gc) return;
     const uint32_t ep = c->kr_epoch;
     const int64_t g = (int64_t)blockIdx.x * blockDim.x + threadIdx.x, stride = (int64_t)gridDim.x * blockDim.x;
-    const int64_t n = c->kr_next_id;
+    const int64_t n = min(c->kr_next_id, t.cap_ids);
     for (int64_t id = g; id < n; id += stride) {
         if (t.mark[id] != ep) continue;
         const int32_t h = (int32_t)(t.arena[(size_t)id * t.stride_words] >> 32);
@@ -238,9 +243,9 @@ hipError_t launch_kr_collect(const KeyRowTable& t, Ctrl* c, const uint64_t* stat
                              const uint8_t* sb_nar, int32_t hb_nw,
                              int32_t n_sb, int32_t cap_e, int32_t pwe, int32_t pw, const uint64_t* parts,
                              int64_t cap_rows, const int64_t* treq, const int64_t* out_key, const int32_t* sb_out,
-                             int64_t slab_cap, hipStream_t s) {
+                             int64_t slab_cap, int64_t treq_cap, int64_t out_cap, hipStream_t s) {
     hipLaunchKernelGGL(k_kr_gc_begin, dim3(1), dim3(64), 0, s, t, c);
-    KrMarkArgs a{t, c, state, state_count, sb_nar, hb_nw, n_sb, cap_e, pwe, pw, parts, cap_rows, treq, out_key, sb_out, slab_cap};
+    KrMarkArgs a{t, c, state, state_count, sb_nar, hb_nw, n_sb, cap_e, pwe, pw, parts, cap_rows, treq, treq_cap, out_key, sb_out, slab_cap, out_cap};
     hipLaunchKernelGGL(k_kr_gc_mark, dim3((unsigned)n_sb + 256), dim3(256), 0, s, a);
     hipLaunchKernelGGL(k_kr_gc_reset_free, dim3(1), dim3(64), 0, s, c);
     const unsigned g = (unsigned)std::min<int64_t>(4096, (std::max(t.n_slots, t.cap_ids) + 255) / 256);

@@ -1480,7 +1480,7 @@ __global__ __launch_bounds__(MG_BLOCK, 4) void k_merge_fire(MergeArgs a) {
     // control decisions; the launch's last workgroup applies them to the control block (merge_finalize)
     const int64_t cur = __hip_atomic_load(&c->cur, __ATOMIC_RELAXED, DEV_SCOPE);
     const int64_t pend = __hip_atomic_load(&c->pending_pushes, __ATOMIC_RELAXED, DEV_SCOPE);
-    const int64_t ntreq = min(__hip_atomic_load(&c->n_treq, __ATOMIC_RELAXED, DEV_SCOPE), (int64_t)0x7fffffff);
+    const int64_t ntreq = min(__hip_atomic_load(&c->n_treq, __ATOMIC_RELAXED, DEV_SCOPE), a.treq_cap);  // the ingest counts on past the cap (ERR_TREQ)
     const int64_t nlf = KIND == KIND_DSWIN ? min(__hip_atomic_load(&c->n_lfire, __ATOMIC_RELAXED, DEV_SCOPE), a.lfire_cap) : 0;
     const int64_t ntp = __hip_atomic_load(&c->ntp, __ATOMIC_RELAXED, DEV_SCOPE);
     const int64_t minp = __hip_atomic_load(&c->min_pending, __ATOMIC_RELAXED, DEV_SCOPE);

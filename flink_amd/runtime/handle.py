@@ -296,8 +296,9 @@ class WindowAggHandle:
     def segments_to_host(self, seg):
         """The rows of a result_segments() description as the dict results() returns (host copies,
         after the handle's stream drains; for tests and tools -- a device consumer reads the
-        segments in place)."""
-        self.sync()
+        segments in place).  A raised FW_ERRF_OUTPUT does not fail it: the segments hold the rows that
+        fit (flinkwin.h), and the caller checks stats()["error_flags"]."""
+        self.stats()  # drains the handle's stream like sync(), which fails on any device error bit
         cols = {"key": seg.cols.key, "window_end": seg.cols.window_end}
         out = {k: [] for k in cols}
         out["values"] = [[] for _ in range(self.n_aggs)]

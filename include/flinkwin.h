@@ -494,9 +494,14 @@ typedef struct {
     fw_result cols;
 } fw_result_segments;
 int fw_results_device_segments(fw_handle* h, fw_result_segments* out);
-/* fw_stats.error_flags bits.  fw_results / fw_results_device turn FW_ERRF_OUTPUT into FW_E_CAPACITY;
-   fw_results_device_segments returns the rows it has (the overflow region's count is clamped to the
-   output capacity), so a segments consumer checks error_flags (fw_get_stats) for FW_ERRF_OUTPUT.
+/* fw_stats.error_flags bits.  More rows than output_capacity between two collections raise
+   FW_ERRF_OUTPUT: at the firing once slabs and overflow region are full, else at the collection that
+   finds more rows than its columns hold.  fw_results and fw_results_ready then fail with
+   FW_E_CAPACITY.  fw_results_device does not wait for the device and cannot fail: its *d_n is the
+   number of rows it copied (at most output_capacity, the rows past it are dropped), and its caller
+   checks error_flags (fw_get_stats) for FW_ERRF_OUTPUT, as a consumer of
+   fw_results_device_segments does, which returns the rows it has (the overflow region's count is
+   clamped to the output capacity).
    A segments consumer also finishes with the rows before ANY call that can run a merge: fw_advance,
    fw_advance_device, fw_flush, and every push (a push starts a flush by itself once the pending
    pushes fill the handle's FW_MAX_PENDING slots). */
@@ -574,6 +579,15 @@ int32_t fw_host_ig_pack_choice(int32_t mode, uint64_t mirror, uint64_t pushes_si
    call with buf == NULL to query it. */
 int fw_snapshot(fw_handle* h, void* buf, int64_t capacity, int64_t* size);
 int fw_restore(fw_handle* h, const void* buf, int64_t size);
+/* Restoring into a handle that has already worked: fw_restore and fw_restore_key_group* drop the
+   result rows emitted before the call and not yet collected, and fw_restore also drops the pending
+   pushes.  The next collection returns only rows fired after the restore, as a freshly restored
+   reference operator holds no output.  fw_restore clears the device error bits.
+   On a FW_KEYHASH_KEYROW handle fw_restore checks the blob first (layout, key-row section, every
+   entry's key row present, no more key rows than the table holds) and changes nothing if that
+   fails; then it restarts the key-row table, empty, and interns the blob's key rows.  Should a
+   later step of the call fail (a device error), the handle is unusable until a fw_restore
+   succeeds. */
 
 /* Key-group-partitioned checkpoint, for restoring at a different parallelism (rescaling).
    fw_snapshot_key_group flushes, then serialises the live (key, slice) entries and timers of ONE

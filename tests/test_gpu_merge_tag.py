@@ -215,12 +215,58 @@ def test_crowded_table(monkeypatch):
 @pytest.mark.parametrize("push", [PUSH, 2200])
 def test_state_overflow_is_reported(monkeypatch, push):
     """Case 4, beyond cap_e: 8000 keys on two superbuckets are more than 3072 groups each;
-    FW_ERRF_STATE is raised in both modes (rows not compared)."""
+    FW_ERRF_STATE is raised in both modes (rows not compared).  While the bit is up the tables stay
+    within their bounds, and the handle recovers: a snapshot taken while 500 keys were live, restored
+    into the same handle after the overflow, continues with 500 keys bit-exactly against the oracle."""
     pool = np.arange(8000, dtype=np.int64) * 7 + 11
     for mode in ("1", "0"):
         monkeypatch.setenv("FW_MG_TAG", mode)
-        _run_steps(_cfg(_kw("sum"), max_batch_rows=1 << 14, **TWO), _stream(6, pool=pool, push=push),
-                   expect_error=abi.ERRF["STATE"])
+        cfg = _cfg(_kw("sum"), max_batch_rows=1 << 14, **TWO)
+        st, _ = _run_steps(cfg, _stream(6, pool=pool, push=push), expect_error=abi.ERRF["STATE"])
+        assert st["live_state_entries"] <= st["num_superbuckets"] * st["superbucket_capacity"], st
+        assert st["peak_superbucket_entries"] > st["superbucket_capacity"], st
+        _overflow_then_recover(cfg, _stream(12, pool=pool[:500], push=push), _stream(6, pool=pool, push=push))
+
+
+def _overflow_then_recover(cfg, small, big):
+    """`small` fits the state tables, `big` does not.  Batch 0 of `small`, a snapshot, `big` until the
+    handle reports FW_ERRF_STATE, the snapshot restored into the same handle (the oracle restarts at the
+    same cut), then the rest of `small`, every watermark's rows against the oracle."""
+    from flink_amd.runtime.handle import WindowAggHandle
+    from oracle.oracle import OracleOperator
+    o, g = OracleOperator(cfg), WindowAggHandle(cfg)
+
+    def step(bi):
+        k, t, iv, dv, wm = small[bi]
+        vals = [iv, dv.view(np.int64)]
+        o.process_batch(k, t, vals, None)
+        o.process_watermark(wm)
+        for part in np.array_split(np.arange(len(k)), SPLIT):
+            g.push_host(k[part], t[part], [v[part] for v in vals])
+        g.advance(wm)
+        _compare(_rows(g.results(reset=True), cfg, set()), _rows(o.results(clear=True), cfg, set()), set(), f"batch {bi}")
+
+    try:
+        step(0)
+        assert g.stats()["live_state_entries"] > 0
+        blob = g.snapshot()
+        o.snapshot_restore()
+        with pytest.raises(_native.FlinkWinError) as err:
+            for k, t, iv, dv, wm in big:
+                for part in np.array_split(np.arange(len(k)), SPLIT):
+                    g.push_host(k[part], t[part], [iv[part], dv.view(np.int64)[part]])
+                g.advance(wm)
+                g.results(reset=True)
+        assert err.value.code == abi.FW_E_CAPACITY
+        assert g.stats()["error_flags"] == abi.ERRF["STATE"]
+        g.restore(blob)
+        assert g.stats()["error_flags"] == 0
+        for bi in range(1, len(small)):
+            step(bi)
+        st = g.stats()
+        assert st["num_late_records_dropped"] == o.late_dropped and st["error_flags"] == 0, st
+    finally:
+        g.close()
 
 
 def _key_group(keys):

@@ -1060,3 +1060,19 @@ def test_hop_block_state_narrow_and_wide_layouts(agg, narrow, monkeypatch):
         out.append((k, t, iv, dv, wm))
     for snap in (None, 11):
         _run_both(_cfg(kw), out, _double_cols(kw), snapshot_at=snap)
+
+
+# The int32 layout with the value word FIRST in a slot (SUM before COUNT(*): accumulator word 0).  Values
+# of +-10^5 do not fit int16 and are negative half of the time, so every superbucket is written back with
+# 4-byte slots whose upper halves and signs matter -- which COUNT(*) in word 0, a small non-negative
+# number, never showed: the slots of word 0 straddled two 8-byte words of the entry and lost their
+# upper 16 bits.  One accumulator word as well: COUNT(*) alone, with slice counts past 65 535.
+@pytest.mark.parametrize("aggs,csi,n,n_keys,n_wm", [
+    ([(abi.AGG_SUM, 0, I64), (abi.AGG_COUNT_STAR, 0, I64)], 1, 192000, 400, 24),
+    ([(abi.AGG_COUNT_STAR, 0, I64)], 0, 640000, 1, 8)],  # one key, 80 000 rows per slice
+    ids=["sum_first", "count_past_65535"])
+def test_hop_block_state_int32_layout_every_slot(aggs, csi, n, n_keys, n_wm, monkeypatch):
+    monkeypatch.setenv("FW_HB_NARROW", "1")
+    kw = dict(window_kind=abi.WIN_HOP, size_ms=6000, slide_ms=2000, count_star_index=csi, aggs=aggs)
+    out = [(k, t, iv * 100, dv, wm) for k, t, iv, dv, wm in _stream(77, n, n_keys, ooo=3000, step_ms=2000, n_wm=n_wm)]
+    _run_both(_cfg(kw), out, _double_cols(kw), snapshot_at=n_wm // 2)
