@@ -26,6 +26,7 @@ WIN_HOP = 1
 WIN_CUMULATE = 2
 WIN_COUNT = 3  # DataStream countWindow: size_ms / slide_ms carry element counts
 WIN_SESSION = 4  # DataStream EventTimeSessionWindows.withGap: size_ms carries the gap
+WIN_SESSION_DYNAMIC = 5  # ... withDynamicGap: value column 1 carries each element's gap, size_ms the largest allowed
 # fw_agg_kind
 AGG_COUNT_STAR = 0
 AGG_COUNT = 1
@@ -53,7 +54,8 @@ KEYHASH_PRECOMPUTED = 4
 KEYHASH_KEYROW = 5
 
 # fw_stats.error_flags bits (FW_ERRF_*)
-ERRF = {"CHUNKS": 1, "STATE": 2, "OUTPUT": 4, "TREQ": 8, "KEYGROUP": 16, "LATE": 32, "ORDEV": 64, "KEYROW": 128}
+ERRF = {"CHUNKS": 1, "STATE": 2, "OUTPUT": 4, "TREQ": 8, "KEYGROUP": 16, "LATE": 32, "ORDEV": 64, "KEYROW": 128,
+        "GAP": 256}
 
 # fw_key_field_kind (key-row fields for fw_key_row_hash)
 KF_STRING, KF_FIXED1, KF_FIXED2, KF_FIXED4, KF_FIXED8 = 0, 1, 2, 4, 8

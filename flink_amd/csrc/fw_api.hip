@@ -537,7 +537,7 @@ int validate_and_plan(fw_handle* h) {
         h->stage_cap = c.max_batch_rows;
         return FW_OK;
     }
-    if (c.window_kind == FW_WIN_SESSION) {  // session windows: a plan of their own (fw_session.hip)
+    if (c.window_kind == FW_WIN_SESSION || c.window_kind == FW_WIN_SESSION_DYNAMIC) {  // session windows: a plan of their own (fw_session.hip)
         int rc = sw_plan(c, &h->sw);
         if (rc) return rc;
         h->ks = h->sw.ks;
@@ -545,6 +545,10 @@ int validate_and_plan(fw_handle* h) {
             h->nv = h->sw.n_slots;
             for (int s = 0; s < h->nv; s++) h->slot_col[s] = h->sw.slot_col[s];
             h->ad = h->sw.ad;
+        } else if (h->sw.dyn) {  // the aggregated field (unless a count) and the gap column
+            h->nv = 0;
+            if (!h->sw.d.is_count) h->slot_col[h->nv++] = 0;
+            h->slot_col[h->nv++] = 1;
         } else {
             h->nv = h->sw.d.is_count ? 0 : 1;
             h->slot_col[0] = h->sw.val_col;
@@ -1026,13 +1030,14 @@ int read_ctrl(fw_handle* h, Ctrl* out) {
     HIP_TRY(hipMemcpyAsync(out, h->ctrl, sizeof(Ctrl), hipMemcpyDeviceToHost, h->stream));
     HIP_TRY(hipStreamSynchronize(h->stream));
     if (out->error) {
-        return fail(FW_E_CAPACITY, "device error (bits 0x%x:%s%s%s%s%s%s%s%s)", out->error,
+        return fail(FW_E_CAPACITY, "device error (bits 0x%x:%s%s%s%s%s%s%s%s%s)", out->error,
                     out->error & ERR_CHUNKS ? " partial-buffer" : "", out->error & ERR_STATE ? " state-table" : "",
                     out->error & ERR_OUTPUT ? " result-buffer" : "", out->error & ERR_TREQ ? " timer-requests" : "",
                     out->error & ERR_KEYGROUP ? " key-group-not-owned" : "",
                     out->error & ERR_LATE ? " late-rows (call fw_late_records more often)" : "",
                     out->error & ERR_ORDEV ? " first-element-events (call fw_first_element_events after each advance)" : "",
-                    out->error & ERR_KEYROW ? " key-rows (table full, or a row over key_row_max_bytes)" : "");
+                    out->error & ERR_KEYROW ? " key-rows (table full, or a row over key_row_max_bytes)" : "",
+                    out->error & ERR_GAP ? " session-gap (a row's gap outside (0, size_ms])" : "");
     }
     return FW_OK;
 }
@@ -2177,7 +2182,7 @@ static int sw_late_records(fw_handle* h, fw_late_rows* out) {
         h->lr_ts[i] = p[1];
         h->lr_seq[i] = (int64_t)((uint64_t)p[2] >> 32);
         h->lr_row[i] = p[2] & 0xffffffffll;
-        if (h->nv > 0) h->lr_val[h->slot_col[0]][i] = p[3];
+        if (!w.d.is_count) h->lr_val[w.val_col][i] = p[3];  // (a dynamic-gap handle's gap column stays 0: the row is named by push_seq, row)
     }
     out->n = n;
     out->key = h->lr_key.data();
@@ -3546,6 +3551,28 @@ int fw_host_session_add(const fw_config* cfg, int64_t watermark, int64_t ts, int
     for (int32_t i = 0; i < *n; i++) accs[i] = (int64_t)session_word_of_result(d, (uint64_t)accs[i]);
     const uint64_t word = session_word(d, (uint64_t)value);
     const int r = session_add<1>(d.gap, d.ops, watermark, ts, &word, 1, starts, ends, (uint64_t*)accs, 1, 1, n, capacity);
+    for (int32_t i = 0; i < *n; i++) accs[i] = (int64_t)session_result(d, (uint64_t)accs[i]);
+    if (r < 0) return fail(FW_E_CAPACITY, "the session list is full (%d sessions)", capacity);
+    *outcome = r;
+    return FW_OK;
+}
+
+int fw_host_session_add_gap(const fw_config* cfg, int64_t watermark, int64_t ts, int64_t gap, int64_t value, int64_t* starts,
+                            int64_t* ends, int64_t* accs, int32_t* n, int32_t capacity, int32_t* outcome) {
+    if (!cfg || !n || !outcome || (capacity > 0 && (!starts || !ends || !accs))) return fail(FW_E_INVALID, "null argument");
+    if (cfg->window_kind != FW_WIN_SESSION_DYNAMIC)
+        return fail(FW_E_INVALID, "fw_host_session_add_gap needs a FW_WIN_SESSION_DYNAMIC configuration");
+    fw_handle h;
+    h.cfg = *cfg;
+    const int rc = validate_and_plan(&h);
+    if (rc) return rc;
+    const SessionDesc& d = h.sw.d;
+    if (gap < 1 || gap > d.gap)
+        return fail(FW_E_INVALID, "session gap %lld is outside (0, size_ms = %lld]", (long long)gap, (long long)d.gap);
+    if (*n < 0 || *n > capacity) return fail(FW_E_INVALID, "bad session count %d (capacity %d)", *n, capacity);
+    for (int32_t i = 0; i < *n; i++) accs[i] = (int64_t)session_word_of_result(d, (uint64_t)accs[i]);
+    const uint64_t word = session_word(d, (uint64_t)value);
+    const int r = session_add<1>(gap, d.ops, watermark, ts, &word, 1, starts, ends, (uint64_t*)accs, 1, 1, n, capacity);
     for (int32_t i = 0; i < *n; i++) accs[i] = (int64_t)session_result(d, (uint64_t)accs[i]);
     if (r < 0) return fail(FW_E_CAPACITY, "the session list is full (%d sessions)", capacity);
     *outcome = r;

@@ -255,6 +255,8 @@ constexpr uint32_t ERR_KEYGROUP = 16u;  // a record's key group is outside this 
 constexpr uint32_t ERR_LATE = 32u;      // late-fire rows or late side-output rows over capacity
 constexpr uint32_t ERR_ORDEV = 64u;     // first-element retain / release events over capacity
 constexpr uint32_t ERR_KEYROW = 128u;   // key-row table full, or a key row over key_row_max_bytes / misaligned
+constexpr uint32_t ERR_GAP = 256u;      // dynamic-gap session windows: a row's gap outside (0, size_ms]
+static_assert(ERR_GAP == FW_ERRF_GAP, "error bits and the public FW_ERRF_* values");
 static_assert(ERR_CHUNKS == FW_ERRF_CHUNKS && ERR_STATE == FW_ERRF_STATE && ERR_OUTPUT == FW_ERRF_OUTPUT &&
                   ERR_TREQ == FW_ERRF_TREQ && ERR_KEYGROUP == FW_ERRF_KEYGROUP && ERR_LATE == FW_ERRF_LATE &&
                   ERR_ORDEV == FW_ERRF_ORDEV && ERR_KEYROW == FW_ERRF_KEYROW,

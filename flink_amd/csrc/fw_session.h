@@ -17,6 +17,11 @@
 // of a list of aggregates over NULL-able columns (the planner's WordDesc / AggDesc), 1 to 8 words
 // rounded up to 1, 2, 4 or 8; a late row is dropped and counted, there is no side output.
 //
+// EventTimeSessionWindows.withDynamicGap(extractor) (FW_WIN_SESSION_DYNAMIC; recalled, parity
+// unpinned: DynamicEventTimeSessionWindows.assignWindows) differs only in the element's window,
+// [ts, ts + g) with g = extractor.extract(element) > 0: the gap arrives as a value column.  Window
+// ends are then no longer ordered like the starts -- a window may lie inside an earlier, longer one.
+//
 // This header holds the interval arithmetic the kernels and fw_host_session_add share (FW_HD), the
 // per-handle state of a session operator (SessionOp) and the entry points fw_api.hip dispatches to.
 #pragma once
@@ -101,7 +106,8 @@ FW_HD int32_t session_op_of_word(int32_t wop) {
 // and its NW accumulator words at acc[i * astride ..], word w folded under ops[w] (the word count is
 // a template parameter so the device's copies unroll).  The element's window and every session
 // it intersects become one session (MergingWindowSet.addWindow); an element that intersects nothing
-// and is late is dropped and leaves the list untouched.
+// and is late is dropped and leaves the list untouched.  `gap` is the element's own: the handle's for
+// a static-gap session, the row's for a dynamic-gap one.
 // Returns 1 merged or added, 0 dropped as late, -1 the list is full (capacity sessions).
 template <int NW>
 FW_HD int session_add(int64_t gap, const int32_t* ops, int64_t watermark, int64_t ts, const uint64_t* words, int wstride,
@@ -159,6 +165,7 @@ constexpr int64_t SW_SIDE_WORDS = 4;               // late side-output row: key,
 // start) and dense -- no tombstones: a fold rewrites the list, a fire compacts it.
 struct SessionOp {
     bool on = false;
+    bool dyn = false;         // FW_WIN_SESSION_DYNAMIC: value column 1 is the row's gap, d.gap the largest allowed
     SessionDesc d{};
     AggDesc ad{};             // SQL: the aggregates over the words (sql_agg_result)
     KeySpace ks{};

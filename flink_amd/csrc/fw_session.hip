@@ -9,7 +9,8 @@
 //   k_sw_advance  one workgroup per superbucket: emit the due sessions, compact the rest
 // k_sw_fold and k_sw_advance are templates on the accumulator words a session carries (NW = 1, 2, 4
 // or 8; 3 + NW words per session): the DataStream handle is the NW = 1 instance, a SQL session handle
-// takes the instance of its plan's word count and a merge class per word.
+// takes the instance of its plan's word count and a merge class per word.  k_sw_fold<1, true> is the
+// dynamic-gap form (FW_WIN_SESSION_DYNAMIC): a gap per row, read from value column 1.
 // No workgroup waits on another: the only cross-workgroup traffic is counters (atomic adds).
 #include <hip/hip_runtime.h>
 
@@ -269,8 +270,11 @@ __device__ __forceinline__ void sw_row_words(const SwFoldArgs& a, uint32_t row, 
     }
 }
 
-template <int NW>
+// DYN (NW = 1 only): the dynamic-gap form.  A row's gap is the word of value column 1 and a.d.gap the
+// largest a row may carry; everything that reads `ts + gap` in the static form reads the row's own end.
+template <int NW, bool DYN = false>
 __global__ __launch_bounds__(SW_TILE) void k_sw_fold(SwFoldArgs a) {
+    static_assert(!DYN || NW == 1, "the dynamic-gap fold is a DataStream instance");
     constexpr int SWS = sw_stride(NW);   // words per session
     __shared__ uint64_t sk[SW_TILE];     // sorted keys; then the coalesce chunk's keys
     __shared__ int64_t sts[SW_TILE];     // their timestamps; then the chunk's ends
@@ -304,10 +308,15 @@ __global__ __launch_bounds__(SW_TILE) void k_sw_fold(SwFoldArgs a) {
     int64_t tile_min_end = INT64_MAX;
 
     for (int64_t base = seg0; base < seg1; base += SW_TILE) {
-        const int nt = (int)(seg1 - base < SW_TILE ? seg1 - base : SW_TILE);
-        const int n2 = sw_pow2(nt);
+        const int nrows = (int)(seg1 - base < SW_TILE ? seg1 - base : SW_TILE);
+        const int n2 = sw_pow2(nrows);
         if (t == 0) n_drop = 0;
-        if (t < nt) {
+        bool badgap = false;  // (dynamic) a row with a gap out of range is padding: it adds nothing
+        if (DYN && t < nrows) {
+            const int64_t g = (int64_t)a.vals[1][a.perm[base + t]];
+            badgap = g < 1 || g > gap;
+        }
+        if (t < nrows && !badgap) {
             const uint32_t row = a.perm[base + t];
             sk[t] = (uint64_t)a.key[row];
             sts[t] = a.ts[row];
@@ -318,11 +327,21 @@ __global__ __launch_bounds__(SW_TILE) void k_sw_fold(SwFoldArgs a) {
             sp[t] = SW_PAD | (uint32_t)t;
         }
         hlen[t] = 0;
+        int nbad = 0;
+        if (DYN) {
+            nbad = __syncthreads_count(badgap);
+            if (nbad && t == 0) atomicOr(&a.ctrl->error, ERR_GAP);
+            if (nbad == nrows) continue;  // (uniform)
+        }
+        const int nt = nrows - nbad;  // the rows the tile folds
         __syncthreads();
         sw_sort(sk, sts, sp, n2);
         const bool valid = t < nt;  // the padding sorted behind the rows
         const uint64_t mykey = sk[t];
         const int64_t myts = sts[t];
+        // the end of the row's own window (dynamic: its gap through perm, as its words below)
+        const int64_t mygap = DYN && valid ? (int64_t)a.vals[1][a.perm[base + sp[t]]] : 0;
+#define SW_END (DYN ? myts + mygap : myts + gap)
         const bool head = valid && (t == 0 || sk[t - 1] != mykey);
         hx[t] = head ? t : 0;
         __syncthreads();
@@ -331,7 +350,7 @@ __global__ __launch_bounds__(SW_TILE) void k_sw_fold(SwFoldArgs a) {
         const int rank = t - hi_;
         // a key run that holds a late candidate is folded in arrival order (rule: an element that is
         // late when it arrives stays only if a session intersects it then)
-        if (valid && session_late(myts, gap, W)) atomicOr((uint32_t*)&hlen[hi_], 1u << 30);
+        if (valid && session_late(myts, DYN ? mygap : gap, W)) atomicOr((uint32_t*)&hlen[hi_], 1u << 30);
         const bool runtail = valid && (t == nt - 1 || sk[t + 1] != mykey);
         if (runtail) atomicOr((uint32_t*)&hlen[hi_], (uint32_t)(rank + 1));
         if (head) {
@@ -342,10 +361,29 @@ __global__ __launch_bounds__(SW_TILE) void k_sw_fold(SwFoldArgs a) {
         const bool slow = valid && (hlen[hi_] >> 30) != 0;
         const int len = valid ? (hlen[hi_] & 0xFFFF) : 0;
         const int lo = valid ? hlo[hi_] : 0, hi = valid ? hhi[hi_] : 0;
+        // dynamic gaps: a row's window may lie wholly inside an earlier, longer one of its key, so the
+        // difference to the previous row says nothing.  The cut is where ts exceeds the run's running
+        // maximum of end over the rows before it (touching windows merge: strictly greater) -- a
+        // forward key-segmented max scan, in `se`, which is free until the reverse reduce below
+        int64_t pmax = INT64_MIN, imax = INT64_MIN;  // the run's max end before the row / with it
+        if (DYN) {
+            se[t] = valid ? SW_END : INT64_MIN;
+            __syncthreads();
+            for (int dd = 1; dd < n2; dd <<= 1) {
+                const bool take = valid && t - dd >= hi_;
+                const int64_t ov = take ? se[t - dd] : INT64_MIN;
+                __syncthreads();
+                if (take && ov > se[t]) se[t] = ov;
+                __syncthreads();
+            }
+            imax = se[t];
+            if (valid && rank > 0) pmax = se[t - 1];
+            // (se is written again behind the barrier of __syncthreads_count below)
+        }
         // tile sessions of the other runs: a new one where the gap to the previous row is exceeded
-        const bool shead = valid && !slow && (rank == 0 || myts - sts[t - 1] > gap);
-        const bool stail = valid && !slow && (runtail || sts[t + 1] - myts > gap);
-        tile_min_end = valid && myts + gap < tile_min_end ? myts + gap : tile_min_end;
+        const bool shead = valid && !slow && (rank == 0 || (DYN ? myts > pmax : myts - sts[t - 1] > gap));
+        const bool stail = valid && !slow && (runtail || (DYN ? sts[t + 1] > imax : sts[t + 1] - myts > gap));
+        tile_min_end = valid && SW_END < tile_min_end ? SW_END : tile_min_end;
         // the sessions the tile can add at most; if they might not fit, the coalesce pass below runs
         // once more in front, only counting (uniform)
         const int may_add = __syncthreads_count(shead || slow);
@@ -361,7 +399,7 @@ __global__ __launch_bounds__(SW_TILE) void k_sw_fold(SwFoldArgs a) {
             if (t < n2) {
 #pragma unroll
                 for (int w = 0; w < NW; w++) sa[w][t] = myword[w];
-                se[t] = myts + gap;
+                se[t] = SW_END;
                 sf[t] = (!valid || slow || stail) ? 1u : 0u;
             }
         }
@@ -441,9 +479,10 @@ __global__ __launch_bounds__(SW_TILE) void k_sw_fold(SwFoldArgs a) {
 #pragma unroll
                 for (int w = 0; w < NW; w++) ops[w] = SW_OP(w);
                 // the row's words: a late-candidate run's rows are segments of their own in the scan
-                // above, so sa[.][u] still holds the words of the row at sorted index u
-                const int rc = session_add<NW>(gap, ops, W, ts, &sa[0][u], SW_TILE, (int64_t*)reg + 1, (int64_t*)reg + 2, reg + 3, SWS,
-                                               SWS, &n, room);
+                // above, so sa[.][u] still holds the words of the row at sorted index u (and se[u] its
+                // own end: a dynamic gap travels like the word)
+                const int rc = session_add<NW>(DYN ? se[u] - ts : gap, ops, W, ts, &sa[0][u], SW_TILE, (int64_t*)reg + 1,
+                                               (int64_t*)reg + 2, reg + 3, SWS, SWS, &n, room);
                 if (rc == 0) {  // dropped: counted (SQL has no side output: late_side is 0)
                     atomicAdd(&n_drop, 1u);
                     if (NW == 1 && a.late_side) {
@@ -616,6 +655,7 @@ __global__ __launch_bounds__(SW_TILE) void k_sw_fold(SwFoldArgs a) {
     if (t == 0 && sts[0] < a.min_end[blockIdx.x]) a.min_end[blockIdx.x] = sts[0];
 #undef SW_OP
 #undef SW_IDN
+#undef SW_END
 }
 
 // ---- the watermark -----------------------------------------------------------------------------
@@ -870,8 +910,26 @@ static int sw_plan_ds(const fw_config& c, SessionOp* op) {
     return FW_OK;
 }
 
+// the dynamic-gap form: EventTimeSessionWindows.withDynamicGap.  Everything sw_plan_ds refuses, with
+// its messages; value column 1 carries the element's gap and size_ms (d.gap) the largest one
+static int sw_plan_dyn(const fw_config& c, SessionOp* op) {
+    const int rc = sw_plan_ds(c, op);
+    if (rc) return rc;
+    if (c.n_value_cols != 2)
+        return set_error(FW_E_INVALID, "dynamic-gap session windows take two value columns, the aggregated field and the gap "
+                                       "(n_value_cols == 2), got %d", c.n_value_cols);
+    if (c.value_col_types[1] != FW_T_I64)
+        return set_error(FW_E_INVALID, "dynamic-gap session windows: the gap column (value column 1) must be FW_T_I64");
+    if (!op->d.is_count && c.aggs[0].input_col != 0)
+        return set_error(FW_E_INVALID, "dynamic-gap session windows: the aggregate reads value column 0 (input_col %d: column 1 is the gap)",
+                         c.aggs[0].input_col);
+    op->dyn = true;
+    return FW_OK;
+}
+
 int sw_plan(const fw_config& c, SessionOp* op) {
-    const int prc = c.api == FW_API_SQL ? sw_plan_sql(c, op) : sw_plan_ds(c, op);
+    const bool dyn = c.window_kind == FW_WIN_SESSION_DYNAMIC;
+    const int prc = dyn ? sw_plan_dyn(c, op) : c.api == FW_API_SQL ? sw_plan_sql(c, op) : sw_plan_ds(c, op);
     if (prc) return prc;
     const SessionDesc& d = op->d;
 
@@ -907,9 +965,9 @@ int sw_plan(const fw_config& c, SessionOp* op) {
             x *= 0x100000001b3ull;
         }
     };
-    if (!d.sql) {  // (the DataStream blobs' fingerprint since their first build)
-        for (int64_t v : {(int64_t)c.api, (int64_t)FW_WIN_SESSION, d.gap, (int64_t)d.op, (int64_t)d.vtype, (int64_t)d.is_count,
-                          (int64_t)ks.hash_kind, (int64_t)ks.max_p})
+    if (!d.sql) {  // (the DataStream blobs' fingerprint since their first build; the dynamic form's names its kind)
+        for (int64_t v : {(int64_t)c.api, (int64_t)(op->dyn ? FW_WIN_SESSION_DYNAMIC : FW_WIN_SESSION), d.gap, (int64_t)d.op,
+                          (int64_t)d.vtype, (int64_t)d.is_count, (int64_t)ks.hash_kind, (int64_t)ks.max_p})
             mix(v);
     } else {  // the API, every aggregate, the NULL-able columns, key hash, gap, max parallelism
         for (int64_t v : {(int64_t)c.api, (int64_t)FW_WIN_SESSION, d.gap, (int64_t)c.n_aggs, (int64_t)c.nullable_cols,
@@ -1016,6 +1074,7 @@ int sw_push(SessionOp* op, int64_t watermark, int64_t n, const int64_t* d_key, c
             if (col >= 0) fa.vals[col] = (const uint64_t*)d_vals[col] + o;
             if (gate >= 0) fa.nulls[gate] = d_nulls[gate] + o;
         }
+        if (op->dyn) fa.vals[1] = (const uint64_t*)d_vals[1] + o;  // the gap column
         fa.perm = op->perm;
         fa.seg = op->seg;
         fa.d = op->d;
@@ -1031,13 +1090,18 @@ int sw_push(SessionOp* op, int64_t watermark, int64_t n, const int64_t* d_key, c
         fa.side = op->side;
         fa.side_cap = op->side_cap;
         fa.ord_base = (op->push_seq << 32) + o;
-        SW_LAUNCH_NW(k_sw_fold, op->nw_t, dim3(n_sb), dim3(SW_TILE), 0, s, fa);
+        if (op->dyn) {
+            hipLaunchKernelGGL((k_sw_fold<1, true>), dim3(n_sb), dim3(SW_TILE), 0, s, fa);
+        } else {
+            SW_LAUNCH_NW(k_sw_fold, op->nw_t, dim3(n_sb), dim3(SW_TILE), 0, s, fa);
+        }
         SW_TRY(hipGetLastError());
     }
     op->push_seq++;
     return FW_OK;
 }
 
+// (a dynamic-gap handle runs the NW = 1 instance too: sessions carry their ends, no gap is read)
 int sw_advance(SessionOp* op, int64_t watermark) {
     SwAdvArgs a{};
     a.d = op->d;

@@ -2,9 +2,11 @@
 sum/min/max), count windows (countWindow) and event-time session windows."""
 from .windowing import EventTimeTrigger, SlidingEventTimeWindows, TumblingEventTimeWindows  # noqa: F401
 from .windowing import CountEvictor, CountTrigger, GlobalWindows, PurgingTrigger  # noqa: F401
-from .windowing import EventTimeSessionWindows  # noqa: F401
+from .windowing import DynamicEventTimeSessionWindows, EventTimeSessionWindows  # noqa: F401
 from .window_operator import WindowOperator, is_gpu_eligible  # noqa: F401
 from .count_window_operator import CountWindowOperator  # noqa: F401
 from .count_window_operator import is_gpu_eligible as is_count_window_gpu_eligible  # noqa: F401
 from .session_window_operator import SessionWindowOperator  # noqa: F401
 from .session_window_operator import is_gpu_eligible as is_session_window_gpu_eligible  # noqa: F401
+from .dynamic_session_window_operator import DynamicSessionWindowOperator  # noqa: F401
+from .dynamic_session_window_operator import is_gpu_eligible as is_dynamic_session_window_gpu_eligible  # noqa: F401

@@ -4,8 +4,9 @@ subset.
 WindowOperatorBuilder would return this operator iff the assigner is EventTimeSessionWindows with a
 static gap, the trigger the default EventTimeTrigger, no evictor, allowedLateness 0, and the
 function a built-in field aggregation sum / min / max (SumAggregator / ComparableAggregator) or a
-count on a LONG / INT / DOUBLE field of (key, field) tuples.  Dynamic gaps, lateness > 0, other
-triggers, evictors and minBy / maxBy stay on the reference operator.
+count on a LONG / INT / DOUBLE field of (key, field) tuples.  Lateness > 0, other triggers, evictors
+and minBy / maxBy stay on the reference operator; dynamic gaps have an operator of their own
+(dynamic_session_window_operator.DynamicSessionWindowOperator).
 
 Semantics (WindowOperator.processElement's merging branch, MergingWindowSet.addWindow,
 TimeWindow.intersects / mergeWindows, EventTimeTrigger): an element's window [ts, ts + gap) and

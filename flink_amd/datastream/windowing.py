@@ -129,3 +129,31 @@ class EventTimeSessionWindows:
 
     def is_event_time(self):
         return True
+
+    @staticmethod
+    def with_dynamic_gap(extractor):
+        return DynamicEventTimeSessionWindows(extractor)
+
+
+class DynamicEventTimeSessionWindows:
+    """EventTimeSessionWindows.withDynamicGap(extractor)
+    (assigners/DynamicEventTimeSessionWindows.java): a merging assigner; every element gets the
+    window [ts, ts + extractor.extract(element)), and a gap <= 0 throws."""
+
+    def __init__(self, extractor):
+        if not callable(extractor):
+            raise ValueError("the session gap extractor must be callable")
+        self.extractor = extractor
+
+    @staticmethod
+    def with_dynamic_gap(extractor):
+        return DynamicEventTimeSessionWindows(extractor)
+
+    def assign_windows(self, element, ts):
+        gap = int(self.extractor(element))
+        if gap <= 0:
+            raise ValueError("Dynamic session time gap must satisfy 0 < gap")
+        return [(ts, ts + gap)]
+
+    def is_event_time(self):
+        return True

@@ -145,7 +145,22 @@ typedef enum {
        NULL, COUNT(col) is 0); first_ord is NULL.  Snapshot blobs carry every accumulator word and
        restore only into a handle of the same aggregate list.  The calls a DataStream session handle
        refuses are refused here too, fw_late_records included. */
-    FW_WIN_SESSION = 4
+    FW_WIN_SESSION = 4,
+    /* v11 (additive), DataStream only: EventTimeSessionWindows.withDynamicGap(extractor)
+       (DynamicEventTimeSessionWindows, recalled, parity unpinned) with EventTimeTrigger, no evictor,
+       allowedLateness 0.  A session handle: everything above holds except where an element's window
+       is named -- it is [ts, ts + g) with the element's own gap g, so a window may lie inside an
+       earlier, longer one, and an element is a late candidate iff ts + g - 1 <= watermark.
+       n_value_cols must be 2: value column 0 is the aggregated field (the one aggregate's
+       input_col; COUNT_STAR reads none), value column 1 the per-element gap, FW_T_I64, which no
+       aggregate may read.  size_ms is the largest gap an element may carry, in (0, 2^40].  A row
+       whose gap is outside (0, size_ms] adds nothing and raises FW_ERRF_GAP (the reference throws
+       IllegalArgumentException for g <= 0; the bound above is this library's).  Every call a
+       FW_WIN_SESSION DataStream handle refuses is refused with the same message; api FW_API_SQL is
+       refused.  Snapshot blobs have the entry format of FW_WIN_SESSION (a session stores start and
+       end) and a fingerprint of their own: they restore only into a dynamic-gap handle of the same
+       size_ms. */
+    FW_WIN_SESSION_DYNAMIC = 5
 } fw_window_kind;
 
 typedef enum {
@@ -513,6 +528,7 @@ int fw_results_device_segments(fw_handle* h, fw_result_segments* out);
 #define FW_ERRF_LATE 32       /* late-fire rows or late side-output rows over capacity     */
 #define FW_ERRF_ORDEV 64      /* first-element retain / release events over capacity       */
 #define FW_ERRF_KEYROW 128    /* key-row table full, or a key row over key_row_max_bytes   */
+#define FW_ERRF_GAP 256       /* FW_WIN_SESSION_DYNAMIC: a row's gap outside (0, size_ms]  */
 int fw_get_stats(fw_handle* h, fw_stats* out);
 
 /* ---- per-kernel device timing (in-kernel clock stamps, or hipEvents around each launch) --- */
@@ -809,6 +825,12 @@ int fw_host_count_step(const fw_config* cfg, int64_t index, int64_t* slice, int3
    configuration fw_create would reject, FW_E_CAPACITY when a new session does not fit. */
 int fw_host_session_add(const fw_config* cfg, int64_t watermark, int64_t ts, int64_t value, int64_t* starts, int64_t* ends,
                         int64_t* accs, int32_t* n, int32_t capacity, int32_t* outcome);
+/* v11 (additive): the same for a FW_WIN_SESSION_DYNAMIC configuration: the element's window is
+   [ts, ts + gap) with its own gap.  Same lists, outcomes and capacity behaviour; FW_E_INVALID also
+   for a gap outside (0, size_ms] and for a configuration of another window kind.  It runs the
+   routine fw_host_session_add and the device code call. */
+int fw_host_session_add_gap(const fw_config* cfg, int64_t watermark, int64_t ts, int64_t gap, int64_t value, int64_t* starts,
+                            int64_t* ends, int64_t* accs, int32_t* n, int32_t capacity, int32_t* outcome);
 /* v11 (additive): the same for a SQL session configuration (FW_WIN_SESSION with FW_API_SQL), whose
    sessions carry the accumulator words of the aggregate list.  fw_host_sql_session_words returns
    the number of words nw the plan uses (1 .. 8; the device rounds it up to 1, 2, 4 or 8).

@@ -9,7 +9,7 @@ tile).  Push s carries event times in [10 s * s, 10 s * (s + 1)) and is followed
 the advance and the (stream-ordered) result reset; it is timed on the host around a handle sync.
 Prints one JSON line per stream.
 
-    python tools/session_window_bench.py [--rows N] [--warmup 5] [--steps 20] [--streams uniform,zipf,hot] [--sql AGGS]
+    python tools/session_window_bench.py [--rows N] [--warmup 5] [--steps 20] [--streams uniform,zipf,hot] [--sql AGGS | --dynamic-gap]
 
 --sql AGGS runs the same streams through a SQL session handle (the SESSION window TVF aggregate,
 BINROW_BIGINT keys) instead: AGGS is a comma-separated aggregate list over two value columns, a
@@ -18,6 +18,11 @@ COUNT(*), COUNT(b), SUM(a), MIN(a), MAX(a), AVG(a), SUM(b), AVG(b); the line the
 accumulator words of the plan.  SUM(a) plans one word, SUM(a),COUNT(*) two,
 SUM(a),COUNT(*),MIN(a),MAX(a) four and SUM(a),MIN(a),MAX(a),COUNT(*),AVG(b),SUM(b),COUNT(b) six,
 which the eight-word kernels carry.
+
+--dynamic-gap runs every stream three times in turn, twice over: through the static handle, through
+a dynamic-gap handle (EventTimeSessionWindows.withDynamicGap, max gap 3 s) whose gap column is the
+constant 3 s, and through one whose gaps are drawn from 0.5 / 1 / 2 / 3 s.  The dynamic fold reads
+8 B more per event (the gap column); the lines carry "gaps": "static" / "constant" / "mixed".
 """
 import argparse
 import json
@@ -31,6 +36,7 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 
 GAP_MS = 3000
 SPAN_MS = 10_000
+MIXED_GAPS_MS = (500, 1000, 2000, 3000)
 
 
 def _keys(kind, n_keys, rows, pushes, device):
@@ -52,10 +58,11 @@ _SQL_AGGS = {"COUNT(*)": ("COUNT_STAR", 0, "BIGINT"), "COUNT(b)": ("COUNT", 1, "
              "SUM(b)": ("SUM", 1, "DOUBLE"), "AVG(b)": ("AVG", 1, "DOUBLE")}
 
 
-def run(kind, rows, warmup, steps, n_keys=10**6, sql=None):
+def run(kind, rows, warmup, steps, n_keys=10**6, sql=None, gaps=None):
+    """``gaps``: None = the static handle; "constant" / "mixed" = a dynamic-gap handle"""
     import torch
     from flink_amd import abi
-    from flink_amd.datastream import SessionWindowOperator
+    from flink_amd.datastream import DynamicSessionWindowOperator, SessionWindowOperator
     from flink_amd.table import SessionWindowAggOperator
     dev = torch.device("cuda", 0)
     if kind == "hot":  # a step of the hot key takes far longer than the others: fewer of them
@@ -63,6 +70,9 @@ def run(kind, rows, warmup, steps, n_keys=10**6, sql=None):
     if sql:
         op = SessionWindowAggOperator(GAP_MS, [_SQL_AGGS[a] for a in sql.split(",")], ["BIGINT", "DOUBLE"], nullable_cols=(1,),
                                       state_capacity=1 << 21, max_batch_rows=rows, output_capacity=1 << 22).open()
+    elif gaps:
+        op = DynamicSessionWindowOperator(GAP_MS, ("sum", "LONG"), state_capacity=1 << 21, max_batch_rows=rows,
+                                          output_capacity=1 << 22).open()
     else:
         op = SessionWindowOperator(GAP_MS, ("sum", "LONG"), state_capacity=1 << 21, max_batch_rows=rows,
                                    output_capacity=1 << 22).open()
@@ -74,6 +84,13 @@ def run(kind, rows, warmup, steps, n_keys=10**6, sql=None):
             g.manual_seed(99)
             dbl = torch.rand(rows, generator=g, device=dev, dtype=torch.float64) + 0.5
             isnull = (torch.rand(rows, generator=g, device=dev) < 0.1).to(torch.uint8)
+        if gaps == "constant":
+            gcol = torch.full((rows,), GAP_MS, dtype=torch.int64, device=dev)
+        elif gaps == "mixed":
+            g = torch.Generator(device=dev)
+            g.manual_seed(7)
+            gcol = torch.tensor(MIXED_GAPS_MS, dtype=torch.int64, device=dev)[
+                torch.randint(0, len(MIXED_GAPS_MS), (rows,), generator=g, device=dev)]
         offs = torch.randint(0, SPAN_MS, (rows,), device=dev, dtype=torch.int64)
         torch.cuda.synchronize()
         ms = []
@@ -83,6 +100,8 @@ def run(kind, rows, warmup, steps, n_keys=10**6, sql=None):
             t0 = time.perf_counter()
             if sql:
                 op.process_batch_device(keys[s % len(keys)], ts, [vals, dbl], None, nulls={1: isnull})
+            elif gaps:
+                op.process_batch_device(keys[s % len(keys)], ts, vals, gcol)
             else:
                 op.process_batch_device(keys[s % len(keys)], ts, vals)
             op.handle.advance((s + 1) * SPAN_MS - 1)
@@ -97,6 +116,9 @@ def run(kind, rows, warmup, steps, n_keys=10**6, sql=None):
         if sql:
             window = "SQL SESSION(gap 3s) " + sql
             extra = {"accumulator_words": abi.host_sql_session_words(op.cfg)}
+        elif gaps:
+            window = "EventTimeSessionWindows.withDynamicGap(<= 3s).sum LONG"
+            extra = {"gaps": gaps}
         return {"tool": "session_window_bench", "stream": kind, "window": window, **extra,
                 "rows_per_push": rows, "keys": 1 if kind == "hot" else n_keys, "warmup": warmup, "steps": steps,
                 "ms_per_push_median": round(float(np.median(ms)), 4), "ms_per_push_min": round(float(ms.min()), 4),
@@ -114,11 +136,21 @@ def main():
     ap.add_argument("--steps", type=int, default=20)
     ap.add_argument("--streams", default="uniform,zipf,hot")
     ap.add_argument("--sql", default=None, metavar="AGGS", help="run a SQL session handle with this aggregate list")
+    ap.add_argument("--dynamic-gap", action="store_true", help="static, constant-gap dynamic and mixed-gap dynamic handles in turn")
     a = ap.parse_args()
+    if a.sql and a.dynamic_gap:
+        ap.error("--dynamic-gap is a DataStream run (no --sql)")
     if a.sql and any(x not in _SQL_AGGS for x in a.sql.split(",")):
         ap.error("--sql takes a comma-separated list out of " + ", ".join(_SQL_AGGS))
     for kind in a.streams.split(","):
-        print(json.dumps(run(kind, a.rows, a.warmup, a.steps, sql=a.sql)), flush=True)
+        if not a.dynamic_gap:
+            print(json.dumps(run(kind, a.rows, a.warmup, a.steps, sql=a.sql)), flush=True)
+            continue
+        for _ in range(2):      # alternating: static, constant, mixed, twice
+            for gaps in (None, "constant", "mixed"):
+                r = run(kind, a.rows, a.warmup, a.steps, gaps=gaps)
+                r.setdefault("gaps", "static")
+                print(json.dumps(r), flush=True)
 
 
 if __name__ == "__main__":
