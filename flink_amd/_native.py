@@ -68,6 +68,7 @@ def lib():
         "fw_set_profiling": (i32, [vp, i32]),
         "fw_get_kernel_times": (i32, [vp, P(abi.fw_kernel_times)]),
         "fw_ingest_pack_launches": (i64, [vp]),
+        "fw_ingest_pack_geometry": (i32, [vp, P(i32), P(i32), P(i32), P(i32)]),
         "fw_merge_path_superbuckets": (i64, [vp, i32]),
         "fw_host_ig_pack_choice": (i32, [i32, C.c_uint64, C.c_uint64, C.c_uint64, C.c_uint32]),
         "fw_snapshot": (i32, [vp, vp, i64, P(i64)]),
@@ -118,7 +119,7 @@ def lib():
 EXPORTED = ["fw_create", "fw_destroy", "fw_last_error", "fw_abi_version", "fw_device_count", "fw_get_stream", "fw_sync",
             "fw_initialize_watermark", "fw_reserve", "fw_commit", "fw_commit_delta32", "fw_delta32_encode", "fw_push_device", "fw_push_device_segments", "fw_push_device_packed_segments", "fw_advance", "fw_advance_device",
             "fw_flush", "fw_results", "fw_results_reset", "fw_results_async", "fw_results_ready", "fw_results_device", "fw_get_stats", "fw_set_profiling",
-            "fw_get_kernel_times", "fw_ingest_pack_launches", "fw_merge_path_superbuckets", "fw_host_ig_pack_choice", "fw_snapshot", "fw_restore", "fw_snapshot_key_group", "fw_restore_key_group",
+            "fw_get_kernel_times", "fw_ingest_pack_launches", "fw_ingest_pack_geometry", "fw_merge_path_superbuckets", "fw_host_ig_pack_choice", "fw_snapshot", "fw_restore", "fw_snapshot_key_group", "fw_restore_key_group",
             "fw_snapshot_key_group_heap", "fw_restore_key_group_heap", "fw_ds_snapshot_key_group", "fw_ds_restore_key_group", "fw_results_device_segments", "fw_key_row_hash", "fw_host_key_row_hash",
             "fw_assign_key_groups", "fw_partition_by_dest", "fw_partition_packed", "fw_partition_packed_spill", "fw_partition_packed_spill_dn", "fw_partition_workspace_bytes",
             "fw_valve_local", "fw_valve_select",

@@ -312,6 +312,13 @@ struct fw_handle {
     // last completed push left the LDS fold skipped and valid PF_PACK fields, a flush epoch has been
     // opened, no fold measurement is due), 2 on every push of an eligible handle (tests)
     int ig_pack_mode = 1;
+    // k_ingest_pack's geometry (fw_internal.h).  FW_IGP_GEOM=0/1 fixes it (A/B, tests); otherwise (-1) each
+    // launch takes the 256 x 16 geometry when that makes the whole push resident and 512 x 8 does not
+    // (more chunks than igp_res[0], at most igp_res[1]: workgroups per CU x CUs), else 512 x 8, which
+    // is faster at every other size
+    int igp_geom = -1;
+    int igp_last = 0;             // geometry of the last k_ingest_pack launch
+    int64_t igp_res[2] = {0, 0};  // chunks resident at once per geometry
     uint64_t ig_since_fold = 0;      // pushes since the last one on which k_ingest folded (that one included)
     uint64_t ig_merges = 0;          // merge launches since the control block was initialised
     bool mg_tag = false;      // planned: the merge launches its GF_TAG variant (tag path for PF_PACK flushes)
@@ -837,6 +844,10 @@ int dalloc(T** p, size_t count) {
     return FW_OK;
 }
 
+// the hash kinds whose 256 x 16 instance keeps its rows in registers (the other two spill 4 VGPRs to
+// scratch: tools/regs.sh), which the automatic geometry choice may take
+static bool igp_auto_kind(int hash_kind) { return hash_kind == KH_BINROW_BIGINT || hash_kind == KH_BINROW_INT; }
+
 int allocate(fw_handle* h) {
     const fw_config& c = h->cfg;
     HIP_TRY(hipSetDevice(c.device));
@@ -879,6 +890,15 @@ int allocate(fw_handle* h) {
         } else {
             h->runs = (uint64_t*)r;
             h->run_ranks = (uint8_t*)rr;
+        }
+    }
+    if (h->ig_pack_ok && h->igp_geom < 0) {  // the resident sets the automatic geometry choice compares a push with
+        int cus = 0;
+        HIP_TRY(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, c.device));
+        for (int g = 0; g < 2; g++) {
+            const int occ = ingest_pack_occupancy(g);
+            if (occ < 0) return fail(FW_E_DEVICE, "k_ingest_pack occupancy query: %s", hipGetErrorString((hipError_t)-occ));
+            h->igp_res[g] = (int64_t)occ * cus;
         }
     }
     if (h->run_rows) {
@@ -1233,7 +1253,8 @@ int push(fw_handle* h, int64_t n, const int64_t* key, const int64_t* ts, const i
                 (stride != 1 ? FW_IGX_STRIDE : 0u) | (h->fold_always ? FW_IGX_FOLD_ALWAYS : 0u));
         const bool packing = choice == FW_IG_PACK;
         if (choice == FW_IG_FOLD) a.fold_always = 1;  // the push on which k_ingest folds and measures again
-        HIP_TRY(packing ? launch_ingest_pack(a, h->stream, h->timer) : launch_ingest(a, h->stream, h->timer));
+        if (packing) h->igp_last = h->igp_geom >= 0 ? h->igp_geom : (a.n_chunks > h->igp_res[0] && a.n_chunks <= h->igp_res[1] && igp_auto_kind(h->ks.hash_kind));
+        HIP_TRY(packing ? launch_ingest_pack(a, h->igp_last, h->stream, h->timer) : launch_ingest(a, h->stream, h->timer));
         // k_ingest does not write the mirror itself: a one-thread launch behind it does (in the steady
         // state of a uniform stream that is one push in 64)
         if (!packing && h->ig_pack_ok && h->ig_pack_mode == 1) HIP_TRY(launch_ig_report(h->tickets, h->ctrl, h->stream));
@@ -1362,6 +1383,7 @@ int fw_create(const fw_config* cfg, fw_handle** out) {
     if (const char* ab = getenv("FW_ABLATE")) h->ablate = atoi(ab);
     if (const char* fo = getenv("FW_FOLD")) h->fold_always = atoi(fo);
     if (const char* ip = getenv("FW_IG_PACK")) h->ig_pack_mode = std::min(std::max(atoi(ip), 0), 2);
+    if (const char* ge = getenv("FW_IGP_GEOM")) h->igp_geom = atoi(ge) != 0;
     if (const char* ak = getenv("FW_AR_KERNEL")) h->ar_kernel = atoi(ak);
     if (const char* fp = getenv("FW_FILL_PCT")) h->fill_pct = std::min(95, std::max(10, atoi(fp)));
     if (const char* si = getenv("FW_SKIP_IDLE")) h->skip_idle = atoi(si) != 0;
@@ -2334,6 +2356,21 @@ int fw_set_profiling(fw_handle* h, int enable) {
 
 int64_t fw_ingest_pack_launches(fw_handle* h) {
     return h ? h->ig_pack_launches : g_ig_pack_launches.load(std::memory_order_relaxed);
+}
+
+int fw_ingest_pack_geometry(fw_handle* h, int32_t* geom, int32_t* threads, int32_t* rows_per_thread, int32_t* workgroups_per_cu) {
+    if (!h) return fail(FW_E_INVALID, "null handle");
+    HIP_TRY(hipSetDevice(h->cfg.device));
+    const int g = h->igp_geom >= 0 ? h->igp_geom : h->igp_last;
+    if (geom) *geom = g;
+    if (threads) *threads = g ? IGP_BLOCK1 : IGP_BLOCK;
+    if (rows_per_thread) *rows_per_thread = g ? IGP_RPT1 : IGP_RPT;
+    if (workgroups_per_cu) {
+        const int n = ingest_pack_occupancy(g);
+        if (n < 0) return fail(FW_E_DEVICE, "k_ingest_pack occupancy query: %s", hipGetErrorString((hipError_t)-n));
+        *workgroups_per_cu = n;
+    }
+    return FW_OK;
 }
 
 int64_t fw_merge_path_superbuckets(fw_handle* h, int tag_path) {

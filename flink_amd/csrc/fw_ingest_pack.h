@@ -15,7 +15,7 @@ namespace fw {
 // and 39 KiB, three workgroups per CU, so one workgroup's column loads overlap the others' sorting
 // and stores.
 //
-// Same chunks (512 threads x 8 rows), same slot, cells, run claims, overflow flags, chunk statistics
+// Same chunks (4096 rows: 512 threads x 8 rows or 256 x 16, the template's geometry), same slot, cells, run claims, overflow flags, chunk statistics
 // and last-workgroup commit as k_ingest, which the merge kernel and the next push read; it never folds
 // and leaves Ctrl::fold_skip alone.  Whatever the packed word cannot hold makes the *chunk* slow: a
 // rolled, one-row-per-thread loop that reloads the columns and writes PF_WIDE rows, sorted by
@@ -98,12 +98,17 @@ __device__ __forceinline__ IgpLds igp_lds(uint64_t* lds, int n_sb) {
     return l;
 }
 
-// HK: the key-hash kind (KH_*, not KH_PRE), resolved per launch
-template <int HK>
-__global__ __launch_bounds__(IGP_BLOCK, IGP_WAVES) void k_ingest_pack(IngestPackArgs a) {
-    constexpr int BLK = IGP_BLOCK, RPT = IGP_RPT, CH = BLK * RPT, NWV = BLK / 64;
+// HK: the key-hash kind (KH_*, not KH_PRE), resolved per launch.  BLK threads x RPT rows, registers
+// bounded for WAVES waves per SIMD: the geometry (fw_internal.h), resolved per launch (fw_api.hip)
+template <int HK, int BLK, int RPT, int WAVES>
+__global__ __launch_bounds__(BLK, WAVES) void k_ingest_pack(IngestPackArgs a) {
+    constexpr int CH = BLK * RPT, NWV = BLK / 64, KMAX = igp_kmax(BLK);
+    constexpr int AHEAD = IGP_AHEAD < RPT ? IGP_AHEAD : RPT;
     constexpr int PW = 3;  // words of a PF_WIDE row: key, slice end, one accumulator word
-    static_assert(CH <= 4096, "a chunk position and a superbucket share a 32-bit word");
+    static_assert(CH == IGP_BLOCK * IGP_RPT && CH <= 4096, "a chunk position and a superbucket share a 32-bit word");
+    static_assert(BLK % 64 == 0 && NWV <= 8 && KMAX * BLK == IGP_MAX_SB, "wsum holds the waves' sums; the threads claim every superbucket");
+    static_assert((RPT - AHEAD) % 2 == 0, "rows past the first AHEAD are loaded two at a time");
+    static_assert(igp_stage_rows(IGP_MAX_SB) * 8 >= 10 * NWV * 8, "the last workgroup's reduction fits the stage");
     // dynamic LDS: [header 16 words][hist: n_sb u16][rbound: n_sb u16][roff: n_sb u32][stage words][stage destinations]
     extern __shared__ __attribute__((aligned(16))) uint64_t lds[];
     int64_t* s_min = (int64_t*)&lds[0];
@@ -172,12 +177,15 @@ __global__ __launch_bounds__(IGP_BLOCK, IGP_WAVES) void k_ingest_pack(IngestPack
         auto issue = [&](auto J) {
             constexpr int j = decltype(J)::value;
             const uint32_t o = min((uint32_t)(j * BLK + tid), last);
-            rk[j] = kp[o];
-            rs[j] = tp[o];
-            rv[j] = vp[o];
+            // (non-temporal: the columns are read once and should not push the run lines other chunks
+            // are still completing out of the L2; round 10: about -2 us per launch in the 512 x 8
+            // geometry, up to -5.9 us in the 256 x 16 one)
+            rk[j] = __builtin_nontemporal_load(kp + o);
+            rs[j] = __builtin_nontemporal_load(tp + o);
+            rv[j] = __builtin_nontemporal_load(vp + o);
         };
         const int64_t ts0v = a.ts[base];  // chunk base of the 32-bit slice arithmetic (loaded first: waited for alone)
-        static_for<IGP_AHEAD>(issue);
+        static_for<AHEAD>(issue);
         const int64_t ts0 = uni64(ts0v);
         // slice-aligned base 2^30 ms below the chunk's first row (as k_ingest): a row within 2^31 ms
         // of it has the slice end tbase + (q + 1) * interval, q = (ts - tbase) / interval in 32 bits
@@ -225,16 +233,16 @@ __global__ __launch_bounds__(IGP_BLOCK, IGP_WAVES) void k_ingest_pack(IngestPack
                 dup = ok & (atomicExch(&tags[(m >> 8) & (uint32_t)(IGP_TAGS - 1)], tag) == tag);
             }
         };
-        // (rows IGP_AHEAD.. are loaded two at a time as two earlier rows have shrunk to their words: the
-        // registers hold IGP_AHEAD loaded rows at most, the CU's workgroups keep HBM busy)
-        static_for<(RPT - IGP_AHEAD) / 2>([&](auto S) {
+        // (rows AHEAD.. are loaded two at a time as two earlier rows have shrunk to their words: the
+        // registers hold AHEAD loaded rows at most, the CU's workgroups keep HBM busy)
+        static_for<(RPT - AHEAD) / 2>([&](auto S) {
             constexpr int s2 = 2 * decltype(S)::value;
             eat(std::integral_constant<int, s2>{});
             eat(std::integral_constant<int, s2 + 1>{});
-            issue(std::integral_constant<int, IGP_AHEAD + s2>{});
-            issue(std::integral_constant<int, IGP_AHEAD + s2 + 1>{});
+            issue(std::integral_constant<int, AHEAD + s2>{});
+            issue(std::integral_constant<int, AHEAD + s2 + 1>{});
         });
-        static_for<IGP_AHEAD>([&](auto J) { eat(std::integral_constant<int, RPT - IGP_AHEAD + decltype(J)::value>{}); });
+        static_for<AHEAD>([&](auto J) { eat(std::integral_constant<int, RPT - AHEAD + decltype(J)::value>{}); });
         if (foreign)  // key group not owned by this subtask
             __hip_atomic_fetch_or(&la->ctrl->error, ERR_KEYGROUP, __ATOMIC_RELAXED, DEV_SCOPE);
         // rank the partials per superbucket (16-bit counters, 32-bit LDS adds on the counter's half)
@@ -342,9 +350,9 @@ __global__ __launch_bounds__(IGP_BLOCK, IGP_WAVES) void k_ingest_pack(IngestPack
         // the claims' round trip overlaps the scan; superbuckets strided over the threads
         const uint32_t xr = (uint32_t)c & (RUN_X - 1);
         uint32_t* fill = la->run_fill + ((size_t)slot * RUN_X + xr) * n_sb;
-        uint32_t pos[IGP_KMAX], cnt[IGP_KMAX];
+        uint32_t pos[KMAX], cnt[KMAX];
 #pragma unroll
-        for (int k = 0; k < IGP_KMAX; k++) {
+        for (int k = 0; k < KMAX; k++) {
             const int i = tid + k * BLK;
             cnt[k] = i < n_sb ? hist[i] : 0u;
             pos[k] = cnt[k] ? atomicAdd(fill + i, cnt[k]) : 0u;
@@ -364,7 +372,7 @@ __global__ __launch_bounds__(IGP_BLOCK, IGP_WAVES) void k_ingest_pack(IngestPack
         const uint32_t scap = la->sub_cap;
         uint32_t* ovf = la->run_ovf + (size_t)slot * n_sb;
 #pragma unroll
-        for (int k = 0; k < IGP_KMAX; k++) {
+        for (int k = 0; k < KMAX; k++) {
             const int i = tid + k * BLK;
             if (i >= n_sb) break;
             const uint32_t st0 = hist[i], v = cnt[k];
@@ -641,18 +649,40 @@ inline IngestPackArgs igp_args(const IngestArgs& a) {
     return p;
 }
 
-template <int HK>
+template <int HK, int BLK, int RPT, int WAVES>
 static hipError_t ingest_pack_hk(const IngestArgs& a, hipStream_t s, KTimer* t) {
     static bool attr_set = false;
     if (!attr_set) {
-        hipError_t e = hipFuncSetAttribute((const void*)k_ingest_pack<HK>, hipFuncAttributeMaxDynamicSharedMemorySize, IGP_LDS);
+        hipError_t e = hipFuncSetAttribute((const void*)k_ingest_pack<HK, BLK, RPT, WAVES>, hipFuncAttributeMaxDynamicSharedMemorySize, IGP_LDS);
         if (e != hipSuccess) return e;
         attr_set = true;
     }
     kt_mark(t, FW_KT_REDUCE, false, s);
-    hipLaunchKernelGGL((k_ingest_pack<HK>), dim3((unsigned)a.n_chunks), dim3(IGP_BLOCK), IGP_LDS, s, igp_args(a));
+    hipLaunchKernelGGL((k_ingest_pack<HK, BLK, RPT, WAVES>), dim3((unsigned)a.n_chunks), dim3(BLK), IGP_LDS, s, igp_args(a));
     kt_mark(t, FW_KT_REDUCE, true, s);
     return hipGetLastError();
+}
+// one geometry's launcher: the instantiations of the four key-hash kinds
+template <int BLK, int RPT, int WAVES>
+static hipError_t ingest_pack_geom(const IngestArgs& a, hipStream_t s, KTimer* t) {
+    if (a.n_chunks == 0) return hipSuccess;
+    if (!igp_serves(a)) return hipErrorInvalidValue;
+    switch (a.ks.hash_kind) {
+        case KH_LONG: return ingest_pack_hk<KH_LONG, BLK, RPT, WAVES>(a, s, t);
+        case KH_INT: return ingest_pack_hk<KH_INT, BLK, RPT, WAVES>(a, s, t);
+        case KH_BINROW_BIGINT: return ingest_pack_hk<KH_BINROW_BIGINT, BLK, RPT, WAVES>(a, s, t);
+        default: return ingest_pack_hk<KH_BINROW_INT, BLK, RPT, WAVES>(a, s, t);
+    }
+}
+// workgroups of the CFG2 instance (KH_BINROW_BIGINT) a CU holds; < 0: the runtime's error, negated
+template <int BLK, int RPT, int WAVES>
+static int ingest_pack_wg_per_cu() {
+    int n = 0;
+    hipError_t e = hipFuncSetAttribute((const void*)k_ingest_pack<KH_BINROW_BIGINT, BLK, RPT, WAVES>,
+                                       hipFuncAttributeMaxDynamicSharedMemorySize, IGP_LDS);
+    if (e == hipSuccess)
+        e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, (const void*)k_ingest_pack<KH_BINROW_BIGINT, BLK, RPT, WAVES>, BLK, IGP_LDS);
+    return e == hipSuccess ? n : -(int)e;
 }
 
 }  // namespace fw

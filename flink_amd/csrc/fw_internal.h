@@ -111,17 +111,26 @@ constexpr bool ig_runs_fit(int n_isb, int block, int rpt, int nw) {
     return n_isb <= RUN_KMAX * block && lds - fixed >= 256 * 8 * (2 + nw);
 }
 
-// ---- k_ingest_pack (fw_ingest_pack.h): the early-packing ingest of PF_PACK pushes.  512 threads x 8
+// ---- k_ingest_pack (fw_ingest_pack.h): the early-packing ingest of PF_PACK pushes.  Chunks of 4096
 // rows like k_ingest's narrow variant (same chunks, same cells), but a row is packed to its 8-B run
 // word as soon as it is routed, so a routed row holds 3 registers, and the LDS holds no fold table:
-// at most 80 VGPRs and 39 KiB, three workgroups per CU instead of two.
+// 39 KiB.  The kernel is a template on its geometry (threads, rows per thread, waves per SIMD its
+// registers are bounded for); two are built.  FW_IGP_GEOM=0/1 fixes one at fw_create; otherwise the host
+// chooses per launch (fw_api.hip: 1 when it makes the whole push resident and 0 does not):
+//   0: 512 threads x 8 rows, 6 waves per SIMD (at most 80 VGPRs): three workgroups per CU
+//   1: 256 threads x 16 rows, 4 waves per SIMD (at most 128 VGPRs): four workgroups per CU, one wave
+//      of each on every SIMD, so a push of 1024 chunks is resident at once on 256 CUs
 constexpr int IGP_BLOCK = 512;
 constexpr int IGP_RPT = 8;
+constexpr int IGP_WAVES = 6;
+constexpr int IGP_BLOCK1 = 256;
+constexpr int IGP_RPT1 = 16;
+constexpr int IGP_WAVES1 = 4;
 constexpr int IGP_LDS = 39 * 1024;
 constexpr int IGP_AHEAD = 8;                       // rows per thread whose column loads are in flight at once
-constexpr int IGP_WAVES = 6;                       // waves per SIMD the registers are bounded for (6: 80 VGPRs, 3 workgroups per CU)
 constexpr int IGP_MAX_SB = 1024;                   // superbuckets its histogram / run bookkeeping holds
-constexpr int IGP_KMAX = IGP_MAX_SB / IGP_BLOCK;   // superbuckets per thread for the run claims
+constexpr int igp_kmax(int block) { return IGP_MAX_SB / block; }  // superbuckets per thread for the run claims
+static_assert(IGP_BLOCK * IGP_RPT == IGP_BLOCK1 * IGP_RPT1, "both geometries work on the same chunks");
 // LDS bytes in front of the store stage: header, u16 histogram, u16 rbound, u32 roff (16-B multiples)
 constexpr int igp_fixed_bytes(int n_sb) { return 8 * (IG_HDR_WORDS + ig_hist_words(n_sb)) + 6 * ((n_sb + 7) & ~7); }
 // rows of a store window: an 8-B word and a 4-B destination per row
@@ -847,7 +856,10 @@ inline void kt_mark(KTimer* t, int kind, bool end, hipStream_t s) {
 // launchers (fw_kernels.hip)
 hipError_t launch_compact(const CompactArgs& a, hipStream_t s, KTimer* t);
 hipError_t launch_ingest(const IngestArgs& a, hipStream_t s, KTimer* t);
-hipError_t launch_ingest_pack(const IngestArgs& a, hipStream_t s, KTimer* t);  // k_ingest_pack.hip
+hipError_t launch_ingest_pack(const IngestArgs& a, int geom, hipStream_t s, KTimer* t);  // k_ingest_pack.hip
+hipError_t launch_ingest_pack_g1(const IngestArgs& a, hipStream_t s, KTimer* t);         // k_ingest_pack_g1.hip
+int ingest_pack_occupancy(int geom);  // workgroups per CU of k_ingest_pack's KH_BINROW_BIGINT instance
+int ingest_pack_occupancy_g1();       // k_ingest_pack_g1.hip
 hipError_t launch_ig_report(const Tickets* tk, const Ctrl* ctrl, hipStream_t s);   // k_ingest_pack.hip
 hipError_t launch_merge_fire(const MergeArgs& a, hipStream_t s, KTimer* t);
 hipError_t launch_init_ctrl(Ctrl* c, hipStream_t s);

@@ -1,4 +1,5 @@
-// k_ingest_pack.hip -- k_ingest_pack instantiations, one per key-hash kind
+// k_ingest_pack.hip -- k_ingest_pack instantiations of the 512 x 8 geometry, one per key-hash kind, and
+// the launcher that chooses the geometry (the 256 x 16 instantiations: k_ingest_pack_g1.hip)
 #include "fw_ingest_pack.h"
 
 namespace fw {
@@ -10,14 +11,10 @@ hipError_t launch_ig_report(const Tickets* tk, const Ctrl* ctrl, hipStream_t s) 
     return hipGetLastError();
 }
 
-hipError_t launch_ingest_pack(const IngestArgs& a, hipStream_t s, KTimer* t) {
-    if (a.n_chunks == 0) return hipSuccess;
-    if (!igp_serves(a)) return hipErrorInvalidValue;
-    switch (a.ks.hash_kind) {
-        case KH_LONG: return ingest_pack_hk<KH_LONG>(a, s, t);
-        case KH_INT: return ingest_pack_hk<KH_INT>(a, s, t);
-        case KH_BINROW_BIGINT: return ingest_pack_hk<KH_BINROW_BIGINT>(a, s, t);
-        default: return ingest_pack_hk<KH_BINROW_INT>(a, s, t);
-    }
+hipError_t launch_ingest_pack(const IngestArgs& a, int geom, hipStream_t s, KTimer* t) {
+    return geom ? launch_ingest_pack_g1(a, s, t) : ingest_pack_geom<IGP_BLOCK, IGP_RPT, IGP_WAVES>(a, s, t);
+}
+int ingest_pack_occupancy(int geom) {
+    return geom ? ingest_pack_occupancy_g1() : ingest_pack_wg_per_cu<IGP_BLOCK, IGP_RPT, IGP_WAVES>();
 }
 }  // namespace fw

@@ -434,6 +434,13 @@ class WindowAggHandle:
         m = {"device": 1, "events": 2, "events_all": 3}[mode]
         check(lib().fw_set_profiling(self._h, m if enable else 0))
 
+    def ingest_pack_geometry(self, occupancy=False):
+        """(geometry, threads, rows per thread[, workgroups per CU]) of this handle's k_ingest_pack launches."""
+        import ctypes as C
+        g, t, r, w = C.c_int32(), C.c_int32(), C.c_int32(), C.c_int32()
+        check(lib().fw_ingest_pack_geometry(self._h, C.byref(g), C.byref(t), C.byref(r), C.byref(w) if occupancy else None))
+        return (g.value, t.value, r.value) + ((w.value,) if occupancy else ())
+
     def ingest_pack_launches(self):
         """Ingest launches of this handle the early-packing kernel (k_ingest_pack) took."""
         return int(lib().fw_ingest_pack_launches(self._h))

@@ -562,6 +562,12 @@ int fw_get_kernel_times(fw_handle* h, fw_kernel_times* out);
    with one NOT NULL integer aggregate; FW_IG_PACK=0 never, 1 by the last push's report, 2 on every push of
    such a handle).  h == NULL: over every handle of the process.  No device call. */
 int64_t fw_ingest_pack_launches(fw_handle* h);
+/* The geometry of the handle's k_ingest_pack launches (0 is 512 threads x 8 rows, 1 is 256 threads x 16
+   rows; a chunk is 4096 rows in both): the one FW_IGP_GEOM=0/1 fixed at fw_create, else the one the
+   host chose for the handle's last such launch (1 when that makes the whole push resident and 0 does
+   not; 0 before the first).  When workgroups_per_cu is not NULL, also the workgroups of it that the
+   runtime reports a CU holds at once.  NULL outputs are skipped. */
+int fw_ingest_pack_geometry(fw_handle* h, int32_t* geom, int32_t* threads, int32_t* rows_per_thread, int32_t* workgroups_per_cu);
 /* Superbuckets with work that the merge launches of a PF_PACK handle (SQL TUMBLE, one integer aggregate,
    not the LOCAL phase) served on the tag path (tag_path != 0: flushes whose pending pushes are all
    PF_PACK and whose state converts) or on the entry-table path (tag_path == 0), cumulative.  Other

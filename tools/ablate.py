@@ -1,5 +1,6 @@
 #!/usr/bin/env python3
-"""Development timing tool: times fw::k_ingest with phases switched off (FW_ABLATE bits, see
+"""Development timing tool: `pack` times fw::k_ingest_pack alone by push size and geometry (pack_main);
+the other modes time fw::k_ingest with phases switched off (FW_ABLATE bits, see
 fw_internal.h AB_*).  The ablations and phase stamps exist only in a diagnostic build of the
 library (make -C flink_amd/csrc DIAG=1); the production build compiles them out.  Only pushes (<= 6 per handle, so no merge ever reads the ablated
 partials); results are meaningless, only the per-kernel device times matter."""
@@ -111,8 +112,60 @@ def merge_main(wl_name, variants, steps=12):
     os.environ.pop("FW_ABLATE", None)
 
 
+def pack_main(geoms, sizes, reps=2, pushes=5):
+    """k_ingest_pack alone (production build, in-kernel stamps): device time per launch by push size in
+    chunks of 4096 rows, per geometry (FW_IGP_GEOM), on slices of CFG2's generated batches.  One JSON
+    line per (geometry, size); `packed` is the share of the timed chunks that took the packing path."""
+    wl = bench.WORKLOADS["cfg2"]
+    dev = torch.device("cuda", 0)
+    L = _native.lib()
+    gp, keys_total = bench.gen_params(wl, 1, None)
+    ch = bench.chunk_rows(wl)
+    nb = 1 + pushes + -(-max(sizes) * ch // bench.B)
+    gk = torch.empty(nb * bench.B, dtype=torch.int64, device=dev)
+    gt, gv = torch.empty_like(gk), torch.empty_like(gk)
+    s = torch.cuda.current_stream(dev).cuda_stream
+    _native.check(L.fw_generate(C.byref(gp), 0, nb * bench.B, gk.data_ptr(), gt.data_ptr(), gv.data_ptr(), s))
+    torch.cuda.synchronize()
+    cfg = bench.build_config(wl, 1, 0, keys_total, 1 << 22)
+    os.environ["FW_IG_PACK"] = "2"
+    for geom in geoms:
+        os.environ["FW_IGP_GEOM"] = str(geom)
+        for nch in sizes:
+            n = nch * ch
+            us, launches, packed = 0.0, 0, 0
+            for rep in range(reps):
+                h = WindowAggHandle(cfg)
+                g, threads, rpt, occ = h.ingest_pack_geometry(occupancy=True)
+                # a watermark (the kernel packs only against one), then one push and a flush: the timed
+                # pushes open a flush epoch with measured PF_PACK fields, as in the bench's steady state
+                h.initialize_watermark(bench.T0 - bench.J - 1)
+                h.push_device(gk[:bench.B], gt[:bench.B], [gv[:bench.B]])
+                h.flush()
+                c0 = h.stats()["compact_chunks"]
+                p0 = h.ingest_pack_launches()
+                h.set_profiling(True)
+                for b in range(1, 1 + pushes):
+                    o = b * bench.B
+                    h.push_device(gk[o:o + n], gt[o:o + n], [gv[o:o + n]])
+                ms, k = h.kernel_times()["reduce"]
+                assert k == pushes and h.ingest_pack_launches() - p0 == pushes, (k, h.ingest_pack_launches() - p0)
+                us += ms * 1e3
+                launches += k
+                packed += h.stats()["compact_chunks"] - c0
+                h.close()
+            print(json.dumps({"geom": g, "threads": threads, "rows_per_thread": rpt, "workgroups_per_cu": occ, "chunks": nch,
+                              "launches": launches, "k_ingest_pack_us": round(us / launches, 2),
+                              "packed": round(packed / (launches * nch), 4)}), flush=True)
+    os.environ.pop("FW_IGP_GEOM", None)
+    os.environ.pop("FW_IG_PACK", None)
+
+
 if __name__ == "__main__":
     if len(sys.argv) > 1 and sys.argv[1] == "merge":
         merge_main(sys.argv[2], [int(x) for x in sys.argv[3].split(",")])
+    elif len(sys.argv) > 1 and sys.argv[1] == "pack":  # pack [geometries [sizes]], e.g. pack 0,1 256,512,768,1024,1280,1536
+        pack_main([int(x) for x in sys.argv[2].split(",")] if len(sys.argv) > 2 else [0, 1],
+                  [int(x) for x in sys.argv[3].split(",")] if len(sys.argv) > 3 else [256, 512, 768, 1024, 1280, 1536])
     else:
         main()

@@ -13,7 +13,7 @@ cd "$(dirname "$0")/../flink_amd/csrc"
 FLAGS="-O3 -std=c++17 -fPIC --offload-arch=gfx950 -DFW_DIAG=0"
 if [ "$1" = "--mix" ]; then
   shift
-  units=${@:-"k_ingest_pack"}
+  units=${@:-"k_ingest_pack k_ingest_pack_g1"}
   for f in $units; do
     /opt/rocm/bin/hipcc $FLAGS --cuda-device-only -S -o /tmp/_mix_$f.s $f.hip 2>/dev/null || exit 1
     python3 - /tmp/_mix_$f.s <<'EOF'
@@ -58,7 +58,7 @@ EOF
   done
   exit 0
 fi
-units=${@:-"k_ingest_nv0 k_ingest_nv1 k_ingest_nv2 k_ingest_pack k_merge_nw1 k_merge_nw2 k_merge_nw4"}
+units=${@:-"k_ingest_nv0 k_ingest_nv1 k_ingest_nv2 k_ingest_pack k_ingest_pack_g1 k_merge_nw1 k_merge_nw2 k_merge_nw4"}
 for f in $units; do
   /opt/rocm/bin/hipcc $FLAGS -c -o /tmp/_regs_$f.o $f.hip \
       -Rpass-analysis=kernel-resource-usage 2>&1 |
