@@ -48,12 +48,6 @@ int fail(int code, const char* fmt, ...) {
         if (e_ != hipSuccess) return fail(FW_E_DEVICE, "%s: %s", #expr, hipGetErrorString(e_)); \
     } while (0)
 
-int64_t next_pow2(int64_t x) {
-    int64_t p = 1;
-    while (p < x) p <<= 1;
-    return p;
-}
-
 int64_t gcd64(int64_t a, int64_t b) {
     while (b) {
         int64_t t = a % b;
@@ -690,7 +684,7 @@ int validate_and_plan(fw_handle* h) {
     h->cap_e = mg_entries(h->nw_t, c.api == FW_API_DATASTREAM ? KIND_DSWIN : w.hopb ? KIND_HOPB : c.window_kind);
     const int64_t fill = h->cap_e * h->fill_pct / 100;
     int64_t per_kg = (cap_target + ks.n_kg - 1) / ks.n_kg;
-    int64_t sbk = next_pow2((per_kg + fill - 1) / fill);
+    int64_t sbk = fd_next_pow2((per_kg + fill - 1) / fill);
     // beyond IG_MAX_SB superbuckets the ingest partitions coarser than the state (KeySpace
     // pass_log2): up to MAX_PASS_LOG2 merge passes share one ingest superbucket's partial rows.  A
     // pass re-routes each row's key, so precomputed-hash keys (no hash in the partial rows) cap
@@ -794,7 +788,7 @@ int validate_and_plan(fw_handle* h) {
     if (h->keyrow) {
         h->kr.cap_ids = std::max<int64_t>(1024, std::max<int64_t>(c.state_capacity, 0) + (int64_t)FW_MAX_PENDING * c.max_batch_rows);
         if (h->kr.cap_ids >= (1ll << 31) - 2) return fail(FW_E_INVALID, "key-row table over 2^31 ids");
-        h->kr.n_slots = next_pow2(2 * h->kr.cap_ids);
+        h->kr.n_slots = fd_next_pow2(2 * h->kr.cap_ids);
         h->krb_cap = c.max_batch_rows * (int64_t)h->kr.max_len;
     }
     return FW_OK;
@@ -836,13 +830,6 @@ void ar_kick(fw_handle* h) {
     }
 }
 
-template <typename T>
-int dalloc(T** p, size_t count) {
-    void* v = nullptr;
-    HIP_TRY(hipMalloc(&v, std::max<size_t>(count, 1) * sizeof(T)));
-    *p = (T*)v;
-    return FW_OK;
-}
 
 // the hash kinds whose 256 x 16 instance keeps its rows in registers (the other two spill 4 VGPRs to
 // scratch: tools/regs.sh), which the automatic geometry choice may take
@@ -854,7 +841,7 @@ int allocate(fw_handle* h) {
     HIP_TRY(hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking));
     int rc;
     const int PW = 2 + h->nw_t, PWE = h->pwe;
-    if ((rc = dalloc(&h->ctrl, 1))) return rc;
+    if ((rc = fd_dalloc(&h->ctrl, 1))) return rc;
     if (h->cw.on) {  // a count handle holds its control block and the count path's own buffers
         if ((rc = cw_allocate(&h->cw, h->stream, h->ctrl))) return rc;
         HIP_TRY(launch_init_ctrl(h->ctrl, h->stream));
@@ -867,11 +854,11 @@ int allocate(fw_handle* h) {
         HIP_TRY(hipStreamSynchronize(h->stream));
         return FW_OK;
     }
-    if ((rc = dalloc(&h->parts, (size_t)FW_MAX_PENDING * h->cap_rows * PW))) return rc;
-    if ((rc = dalloc(&h->cells, (size_t)FW_MAX_PENDING * (h->ks.n_sb >> h->ks.pass_log2) * h->cell_cols))) return rc;
-    if ((rc = dalloc(&h->slot_nch, FW_MAX_PENDING))) return rc;
-    if ((rc = dalloc(&h->slot_base, FW_MAX_PENDING))) return rc;
-    if (h->narrow && (rc = dalloc(&h->ranks, (size_t)FW_MAX_PENDING * h->cap_rows))) return rc;
+    if ((rc = fd_dalloc(&h->parts, (size_t)FW_MAX_PENDING * h->cap_rows * PW))) return rc;
+    if ((rc = fd_dalloc(&h->cells, (size_t)FW_MAX_PENDING * (h->ks.n_sb >> h->ks.pass_log2) * h->cell_cols))) return rc;
+    if ((rc = fd_dalloc(&h->slot_nch, FW_MAX_PENDING))) return rc;
+    if ((rc = fd_dalloc(&h->slot_base, FW_MAX_PENDING))) return rc;
+    if (h->narrow && (rc = fd_dalloc(&h->ranks, (size_t)FW_MAX_PENDING * h->cap_rows))) return rc;
     if (h->run_rows) {
         // the runs layout is a plan, not a requirement: FW_MAX_PENDING * run_rows partial rows (about
         // 1.25x the partial buffer) on top of it.  When the device cannot hold them the handle keeps
@@ -903,58 +890,58 @@ int allocate(fw_handle* h) {
     }
     if (h->run_rows) {
         const size_t n_isb = (size_t)(h->ks.n_sb >> h->ks.pass_log2);
-        if ((rc = dalloc(&h->run_fill, (size_t)FW_MAX_PENDING * RUN_X * n_isb))) return rc;
-        if ((rc = dalloc(&h->run_ovf, (size_t)FW_MAX_PENDING * n_isb))) return rc;
-        if ((rc = dalloc(&h->slot_fmt, FW_MAX_PENDING))) return rc;
+        if ((rc = fd_dalloc(&h->run_fill, (size_t)FW_MAX_PENDING * RUN_X * n_isb))) return rc;
+        if ((rc = fd_dalloc(&h->run_ovf, (size_t)FW_MAX_PENDING * n_isb))) return rc;
+        if ((rc = fd_dalloc(&h->slot_fmt, FW_MAX_PENDING))) return rc;
         HIP_TRY(hipMemsetAsync(h->run_fill, 0, sizeof(uint32_t) * FW_MAX_PENDING * RUN_X * n_isb, h->stream));
         HIP_TRY(hipMemsetAsync(h->run_ovf, 0, sizeof(uint32_t) * FW_MAX_PENDING * n_isb, h->stream));
         HIP_TRY(hipMemsetAsync(h->slot_fmt, 0, sizeof(int32_t) * FW_MAX_PENDING, h->stream));
     }
-    if ((rc = dalloc(&h->treq, (size_t)h->treq_cap * 3))) return rc;
-    if (h->lfire_cap && (rc = dalloc(&h->lfire, (size_t)h->lfire_cap * LFW))) return rc;
-    if (h->side_cap && (rc = dalloc(&h->side, (size_t)h->side_cap * SOW))) return rc;
-    if (h->ordev_cap && (rc = dalloc(&h->ordev, (size_t)h->ordev_cap))) return rc;
+    if ((rc = fd_dalloc(&h->treq, (size_t)h->treq_cap * 3))) return rc;
+    if (h->lfire_cap && (rc = fd_dalloc(&h->lfire, (size_t)h->lfire_cap * LFW))) return rc;
+    if (h->side_cap && (rc = fd_dalloc(&h->side, (size_t)h->side_cap * SOW))) return rc;
+    if (h->ordev_cap && (rc = fd_dalloc(&h->ordev, (size_t)h->ordev_cap))) return rc;
     if (h->keyrow) {
         KeyRowTable& t = h->kr;
-        if ((rc = dalloc(&t.slots, (size_t)t.n_slots))) return rc;
-        if ((rc = dalloc(&t.arena, (size_t)t.cap_ids * t.stride_words))) return rc;
-        if ((rc = dalloc(&t.mark, (size_t)t.cap_ids))) return rc;
-        if ((rc = dalloc(&t.free_list, (size_t)t.cap_ids))) return rc;
+        if ((rc = fd_dalloc(&t.slots, (size_t)t.n_slots))) return rc;
+        if ((rc = fd_dalloc(&t.arena, (size_t)t.cap_ids * t.stride_words))) return rc;
+        if ((rc = fd_dalloc(&t.mark, (size_t)t.cap_ids))) return rc;
+        if ((rc = fd_dalloc(&t.free_list, (size_t)t.cap_ids))) return rc;
         HIP_TRY(hipMemsetAsync(t.slots, 0, sizeof(uint32_t) * t.n_slots, h->stream));
         HIP_TRY(hipMemsetAsync(t.mark, 0, sizeof(uint32_t) * t.cap_ids, h->stream));
-        if ((rc = dalloc(&h->res_kr_len, (size_t)h->out_cap))) return rc;
-        if ((rc = dalloc(&h->res_kr_img, (size_t)h->out_cap * (t.stride_words - 1)))) return rc;
+        if ((rc = fd_dalloc(&h->res_kr_len, (size_t)h->out_cap))) return rc;
+        if ((rc = fd_dalloc(&h->res_kr_img, (size_t)h->out_cap * (t.stride_words - 1)))) return rc;
     }
     if (!h->tz_utc.empty()) {  // shift-zone table on the device; the kernels' WinDesc points at it
         const size_t n = h->tz_utc.size();
-        if ((rc = dalloc(&h->d_tz, 3 * n))) return rc;
+        if ((rc = fd_dalloc(&h->d_tz, 3 * n))) return rc;
         HIP_TRY(hipMemcpy(h->d_tz, h->tz_utc.data(), 8 * n, hipMemcpyHostToDevice));
         HIP_TRY(hipMemcpy(h->d_tz + n, h->tz_off.data(), 8 * n, hipMemcpyHostToDevice));
         HIP_TRY(hipMemcpy(h->d_tz + 2 * n, h->tz_bound.data(), 8 * n, hipMemcpyHostToDevice));
     }
-    if ((rc = dalloc(&h->state, (size_t)h->ks.n_sb * h->cap_e * PWE))) return rc;
-    if ((rc = dalloc(&h->state_count, h->ks.n_sb))) return rc;
-    if ((rc = dalloc(&h->sb_min_timer, h->ks.n_sb))) return rc;
-    if ((rc = dalloc(&h->sb_nar, h->ks.n_sb))) return rc;
+    if ((rc = fd_dalloc(&h->state, (size_t)h->ks.n_sb * h->cap_e * PWE))) return rc;
+    if ((rc = fd_dalloc(&h->state_count, h->ks.n_sb))) return rc;
+    if ((rc = fd_dalloc(&h->sb_min_timer, h->ks.n_sb))) return rc;
+    if ((rc = fd_dalloc(&h->sb_nar, h->ks.n_sb))) return rc;
     const size_t orows = (size_t)h->ks.n_sb * h->slab_cap + h->out_cap;
-    if ((rc = dalloc(&h->out_key, orows))) return rc;
-    if ((rc = dalloc(&h->out_we, orows))) return rc;
-    if ((rc = dalloc(&h->out_null, orows))) return rc;
+    if ((rc = fd_dalloc(&h->out_key, orows))) return rc;
+    if ((rc = fd_dalloc(&h->out_we, orows))) return rc;
+    if ((rc = fd_dalloc(&h->out_null, orows))) return rc;
     for (int g = 0; g < h->n_out; g++)
-        if ((rc = dalloc(&h->out_val[g], orows))) return rc;
-    if ((rc = dalloc(&h->res_key, h->out_cap))) return rc;
-    if ((rc = dalloc(&h->res_ws, h->out_cap))) return rc;
-    if ((rc = dalloc(&h->res_we, h->out_cap))) return rc;
-    if ((rc = dalloc(&h->res_null, h->out_cap))) return rc;
+        if ((rc = fd_dalloc(&h->out_val[g], orows))) return rc;
+    if ((rc = fd_dalloc(&h->res_key, h->out_cap))) return rc;
+    if ((rc = fd_dalloc(&h->res_ws, h->out_cap))) return rc;
+    if ((rc = fd_dalloc(&h->res_we, h->out_cap))) return rc;
+    if ((rc = fd_dalloc(&h->res_null, h->out_cap))) return rc;
     for (int g = 0; g < h->n_out; g++)
-        if ((rc = dalloc(&h->res_val[g], h->out_cap))) return rc;
-    if ((rc = dalloc(&h->sb_out, h->ks.n_sb + 1))) return rc;  // + the overflow region's rows
-    if ((rc = dalloc(&h->sb_fired, h->ks.n_sb))) return rc;
-    if ((rc = dalloc(&h->coff, h->ks.n_sb + 2))) return rc;
-    if ((rc = dalloc(&h->chunk_stats, CS_WORDS * (h->max_nch + 1)))) return rc;
-    if ((rc = dalloc(&h->stamps, N_STAMPS))) return rc;
-    if ((rc = dalloc(&h->kt_dev, FW_KT_N * KT_WORDS))) return rc;
-    if ((rc = dalloc(&h->tickets, 1))) return rc;
+        if ((rc = fd_dalloc(&h->res_val[g], h->out_cap))) return rc;
+    if ((rc = fd_dalloc(&h->sb_out, h->ks.n_sb + 1))) return rc;  // + the overflow region's rows
+    if ((rc = fd_dalloc(&h->sb_fired, h->ks.n_sb))) return rc;
+    if ((rc = fd_dalloc(&h->coff, h->ks.n_sb + 2))) return rc;
+    if ((rc = fd_dalloc(&h->chunk_stats, CS_WORDS * (h->max_nch + 1)))) return rc;
+    if ((rc = fd_dalloc(&h->stamps, N_STAMPS))) return rc;
+    if ((rc = fd_dalloc(&h->kt_dev, FW_KT_N * KT_WORDS))) return rc;
+    if ((rc = fd_dalloc(&h->tickets, 1))) return rc;
     HIP_TRY(hipHostMalloc((void**)&h->mirror, sizeof(unsigned long long), hipHostMallocMapped | hipHostMallocCoherent));
     *h->mirror = ~0ull;
     HIP_TRY(hipHostGetDevicePointer((void**)&h->d_mirror, (void*)h->mirror, 0));
@@ -998,16 +985,16 @@ int alloc_staging(fw_handle* h) {
         if (h->keyrow) {
             HIP_TRY(hipHostMalloc((void**)&h->h_kro[b], (n + 1) * 8, hipHostMallocDefault));
             HIP_TRY(hipHostMalloc((void**)&h->h_krb[b], (size_t)std::max<int64_t>(h->krb_cap, 8), hipHostMallocDefault));
-            if ((rc = dalloc(&h->d_kro[b], n + 1))) return rc;
-            if ((rc = dalloc(&h->d_krb[b], (size_t)std::max<int64_t>(h->krb_cap, 8)))) return rc;
+            if ((rc = fd_dalloc(&h->d_kro[b], n + 1))) return rc;
+            if ((rc = fd_dalloc(&h->d_krb[b], (size_t)std::max<int64_t>(h->krb_cap, 8)))) return rc;
         } else {
-            if ((rc = dalloc(&h->d_key[b], n))) return rc;
+            if ((rc = fd_dalloc(&h->d_key[b], n))) return rc;
         }
-        if ((rc = dalloc(&h->d_ts[b], n))) return rc;
-        if (c.key_hash == FW_KEYHASH_PRECOMPUTED && (rc = dalloc(&h->d_kh[b], n))) return rc;
+        if ((rc = fd_dalloc(&h->d_ts[b], n))) return rc;
+        if (c.key_hash == FW_KEYHASH_PRECOMPUTED && (rc = fd_dalloc(&h->d_kh[b], n))) return rc;
         for (int v = 0; v < c.n_value_cols; v++) {
-            if ((rc = dalloc(&h->d_val[b][v], n))) return rc;
-            if (((c.nullable_cols >> v) & 1u) && (rc = dalloc(&h->d_nul[b][v], n))) return rc;
+            if ((rc = fd_dalloc(&h->d_val[b][v], n))) return rc;
+            if (((c.nullable_cols >> v) & 1u) && (rc = fd_dalloc(&h->d_nul[b][v], n))) return rc;
         }
     }
     return FW_OK;
@@ -1030,12 +1017,12 @@ int alloc_async_results(fw_handle* h) {
         HIP_TRY(hipHostMalloc((void**)&h->ar_n[b], 8, hipHostMallocMapped | hipHostMallocCoherent));
         HIP_TRY(hipEventCreateWithFlags(&h->ar_ev[b], hipEventDisableTiming));
         HIP_TRY(hipEventCreateWithFlags(&h->ar_dma_ev[b], hipEventDisableTiming));
-        if ((rc = dalloc(&h->ard_key[b], n))) return rc;
-        if ((rc = dalloc(&h->ard_ws[b], n))) return rc;
-        if ((rc = dalloc(&h->ard_we[b], n))) return rc;
-        if ((rc = dalloc(&h->ard_null[b], n))) return rc;
+        if ((rc = fd_dalloc(&h->ard_key[b], n))) return rc;
+        if ((rc = fd_dalloc(&h->ard_ws[b], n))) return rc;
+        if ((rc = fd_dalloc(&h->ard_we[b], n))) return rc;
+        if ((rc = fd_dalloc(&h->ard_null[b], n))) return rc;
         for (int g = 0; g < h->n_out; g++)
-            if ((rc = dalloc(&h->ard_val[b][g], n))) return rc;
+            if ((rc = fd_dalloc(&h->ard_val[b][g], n))) return rc;
     }
     return FW_OK;
 }
@@ -1283,8 +1270,8 @@ int kr_intern(fw_handle* h, int64_t n, const int64_t* d_off, const uint8_t* d_by
         h->d_khash = nullptr;
         h->kr_scratch_n = 0;
         int rc;
-        if ((rc = dalloc(&h->d_kid, (size_t)n))) return rc;
-        if ((rc = dalloc(&h->d_khash, (size_t)n))) return rc;
+        if ((rc = fd_dalloc(&h->d_kid, (size_t)n))) return rc;
+        if ((rc = fd_dalloc(&h->d_khash, (size_t)n))) return rc;
         h->kr_scratch_n = n;
     }
     HIP_TRY(launch_kr_intern(h->kr, h->ctrl, n, d_off, d_bytes, h->d_kid, h->d_khash, h->stream));
@@ -2532,8 +2519,8 @@ static int kr_restore_section(fw_handle* h, const uint64_t* sec, int64_t avail_w
     int64_t* d_off = nullptr;
     uint8_t* d_bytes = nullptr;
     int rc;
-    if ((rc = dalloc(&d_off, off.size()))) return rc;
-    if ((rc = dalloc(&d_bytes, std::max<size_t>(bytes.size() * 8, 8)))) { hipFree(d_off); return rc; }
+    if ((rc = fd_dalloc(&d_off, off.size()))) return rc;
+    if ((rc = fd_dalloc(&d_bytes, std::max<size_t>(bytes.size() * 8, 8)))) { hipFree(d_off); return rc; }
     HIP_TRY(hipMemcpy(d_off, off.data(), off.size() * 8, hipMemcpyHostToDevice));
     HIP_TRY(hipMemcpy(d_bytes, bytes.data(), bytes.size() * 8, hipMemcpyHostToDevice));
     rc = kr_intern(h, nk, d_off, d_bytes);

@@ -10,7 +10,7 @@
 // This header holds the slice arithmetic the kernel and fw_host_count_step share (FW_HD), the
 // per-handle state of a count operator (CountOp) and the entry points fw_api.hip dispatches to.
 #pragma once
-#include "fw_internal.h"
+#include "fw_folded.h"
 
 namespace fw {
 
@@ -67,9 +67,8 @@ FW_HD uint64_t count_fold(int32_t op, uint64_t a, uint64_t b) {
 // the table's own slot hash of a key inside its superbucket (not a Flink-visible hash)
 FW_HD uint32_t count_slot_hash(int64_t key, uint32_t mask) { return (uint32_t)mix64((uint64_t)key) & mask; }
 
-constexpr int CW_TILE = 1024;                       // rows per tile = threads per workgroup
+constexpr int CW_TILE = FD_TILE;                    // rows per tile = threads per workgroup
 constexpr int64_t CW_CLAIMED = INT64_MIN;           // count word of an entry claimed in the running tile
-constexpr int64_t CW_MAX_HIST = (int64_t)1 << 26;   // [superbucket][chunk] partition counters a handle may hold
 
 // Per-handle state of a count operator.  The key table is open addressed, partitioned by
 // superbucket: entry e of superbucket sb is table[(sb * cap_e + e) * pwe ..]: key, count, ring[R].
@@ -83,19 +82,11 @@ struct CountOp {
     int32_t val_col = 0;    // value column the aggregate reads
     int32_t cap_e = 0;      // table slots per superbucket (power of two)
     int32_t pwe = 0;        // words per entry: 2 + R
-    int64_t cap_rows = 0;   // rows per launch (max_batch_rows)
-    int64_t max_nch = 0;    // partition chunks per launch
     int64_t out_cap = 0;
     hipStream_t stream = nullptr;  // the handle's
     Ctrl* ctrl = nullptr;          // the handle's control block: out_count[0], fired, live_entries, error
     uint64_t* table = nullptr;
-    // partition scratch of one launch
-    int32_t* hist = nullptr;       // [n_sb][n_chunks]: rows of chunk in superbucket, then their exclusive scan
-    int32_t* seg = nullptr;        // [n_sb + 1]: rows per superbucket, then segment starts
-    int32_t* s_sb = nullptr;       // [cap_rows] chunk-sorted: superbucket (-1: dropped), row, rank in (chunk, sb)
-    uint32_t* s_row = nullptr;
-    int32_t* s_rank = nullptr;
-    uint32_t* perm = nullptr;      // [cap_rows] row indices grouped by superbucket, arrival order inside
+    FoldedPart part{};             // the superbucket partition's buffers
     // result rows
     int64_t* out_key = nullptr;
     int64_t* out_ws = nullptr;
@@ -106,9 +97,6 @@ struct CountOp {
     int64_t push_seq = 0;
     int64_t watermark = INT64_MIN;
 };
-
-// error reporting of fw_api.hip (fw_last_error): returns code
-int set_error(int code, const char* fmt, ...) __attribute__((format(printf, 2, 3)));
 
 // validation + plan of a FW_WIN_COUNT configuration; no device call
 int cw_plan(const fw_config& c, CountOp* op);

@@ -1,12 +1,7 @@
 // fw_count.hip -- the count-window path (fw_count.h): kernels and the per-handle host code.
 //
-// One push is folded into the key table when it is pushed, in six stream-ordered launches:
-//   k_cw_part     per chunk of CW_TILE rows: route every key to its superbucket, sort (superbucket,
-//                 position) in LDS, and write the chunk's rows grouped by superbucket with each row's
-//                 rank inside its (chunk, superbucket) group, and the group sizes (hist)
-//   k_cw_scan     per superbucket: exclusive scan of its group sizes over the chunks
-//   k_cw_seg      exclusive scan of the superbucket totals: segment starts
-//   k_cw_scatter  row indices to their segment, input order kept inside a superbucket
+// One push is folded into the key table when it is pushed: the folded paths' stable superbucket
+// partition (fd_partition, fw_folded.hip: four stream-ordered launches), then
 //   k_cw_fold     one workgroup per superbucket walks its segment in arrival order, a tile at a time
 // No workgroup waits on another: the only cross-workgroup traffic is counters (atomic adds).
 #include <hip/hip_runtime.h>
@@ -19,174 +14,6 @@
 
 namespace fw {
 namespace {
-
-#define CW_TRY(expr)                                                                                 \
-    do {                                                                                             \
-        hipError_t e_ = (expr);                                                                      \
-        if (e_ != hipSuccess) return set_error(FW_E_DEVICE, "%s: %s", #expr, hipGetErrorString(e_)); \
-    } while (0)
-
-constexpr uint32_t CW_PAD = 0x80000000u;  // position word of a padding element: sorts after every row
-
-// (padding, key, position) order; positions are unique, so the order is total and the sort stable
-__device__ __forceinline__ bool cw_less(uint64_t ka, uint32_t pa, uint64_t kb, uint32_t pb) {
-    const uint32_t ia = pa >> 31, ib = pb >> 31;
-    if (ia != ib) return ia < ib;
-    if (ka != kb) return ka < kb;
-    return pa < pb;
-}
-
-// bitonic sort of the first n2 (a power of two <= CW_TILE) pairs; every thread of the workgroup
-// calls it, after a barrier behind the stores that filled k / p; it ends with a barrier
-__device__ void cw_sort(uint64_t* k, uint32_t* p, int n2) {
-    const int t = threadIdx.x;
-    for (int kk = 2; kk <= n2; kk <<= 1)
-        for (int j = kk >> 1; j > 0; j >>= 1) {
-            const int x = t ^ j;
-            if (t < n2 && x > t) {
-                const bool asc = (t & kk) == 0;
-                const uint64_t ka = k[t], kb = k[x];
-                const uint32_t pa = p[t], pb = p[x];
-                if (cw_less(kb, pb, ka, pa) == asc) {
-                    k[t] = kb;
-                    k[x] = ka;
-                    p[t] = pb;
-                    p[x] = pa;
-                }
-            }
-            __syncthreads();
-        }
-}
-
-// inclusive max scan of a[0 .. n2); every thread calls it after a barrier; ends with a barrier
-__device__ void cw_max_scan(int32_t* a, int n2) {
-    const int t = threadIdx.x;
-    for (int d = 1; d < n2; d <<= 1) {
-        const bool on = t < n2 && t >= d;
-        const int32_t v = on ? a[t - d] : 0;
-        __syncthreads();
-        if (on && v > a[t]) a[t] = v;
-        __syncthreads();
-    }
-}
-
-__device__ __forceinline__ int cw_pow2(int n) {
-    int p = 2;
-    while (p < n) p <<= 1;
-    return p;
-}
-
-struct CwPartArgs {
-    const int64_t* key;
-    const int32_t* khash;
-    int64_t n;
-    int32_t n_chunks;
-    KeySpace ks;
-    Ctrl* ctrl;
-    int32_t* hist;
-    int32_t* s_sb;
-    uint32_t* s_row;
-    int32_t* s_rank;
-};
-
-__global__ __launch_bounds__(CW_TILE) void k_cw_part(CwPartArgs a) {
-    __shared__ uint64_t sk[CW_TILE];
-    __shared__ uint32_t sp[CW_TILE];
-    __shared__ int32_t hx[CW_TILE];
-    const int t = threadIdx.x;
-    const int64_t c0 = (int64_t)blockIdx.x * CW_TILE;
-    const int nrows = (int)(a.n - c0 < CW_TILE ? a.n - c0 : CW_TILE);
-    const int n2 = cw_pow2(nrows);
-    int32_t sb = -1;
-    if (t < nrows) {
-        uint32_t m;
-        sb = route_key(a.ks, a.key[c0 + t], a.khash ? a.khash[c0 + t] : 0, &m);
-        if (sb < 0 || sb >= a.ks.n_sb) {  // key group outside the subtask's range: the row is dropped
-            atomicOr(&a.ctrl->error, ERR_KEYGROUP);
-            sb = -1;
-        }
-    }
-    sk[t] = sb >= 0 ? (uint64_t)sb : ~0ull;
-    sp[t] = sb >= 0 ? (uint32_t)t : (CW_PAD | (uint32_t)t);
-    __syncthreads();
-    cw_sort(sk, sp, n2);
-    const bool v = t < n2 && !(sp[t] >> 31);
-    const bool head = v && (t == 0 || sk[t - 1] != sk[t]);
-    hx[t] = head ? t : 0;
-    __syncthreads();
-    cw_max_scan(hx, n2);
-    if (v) {
-        const int32_t rank = t - hx[t];
-        const int32_t s = (int32_t)sk[t];
-        a.s_sb[c0 + t] = s;
-        a.s_row[c0 + t] = (uint32_t)(c0 + sp[t]);
-        a.s_rank[c0 + t] = rank;
-        const bool tail = t == n2 - 1 || (sp[t + 1] >> 31) || sk[t + 1] != sk[t];
-        if (tail) a.hist[(size_t)s * a.n_chunks + blockIdx.x] = rank + 1;
-    } else if (t < nrows) {
-        a.s_sb[c0 + t] = -1;
-    }
-}
-
-// inclusive scan over the workgroup's NT threads; every thread calls it; *total = the sum
-template <int NT>
-__device__ int32_t cw_block_scan(int32_t x, int32_t* buf, int32_t* total) {
-    const int t = threadIdx.x;
-    buf[t] = x;
-    __syncthreads();
-    for (int d = 1; d < NT; d <<= 1) {
-        const int32_t v = t >= d ? buf[t - d] : 0;
-        __syncthreads();
-        buf[t] += v;
-        __syncthreads();
-    }
-    const int32_t r = buf[t];
-    *total = buf[NT - 1];
-    __syncthreads();
-    return r;
-}
-
-// superbucket blockIdx.x: hist[sb][0 .. n_chunks) -> its exclusive scan; seg[sb] = the total
-__global__ __launch_bounds__(256) void k_cw_scan(int32_t* hist, int32_t* seg, int32_t n_chunks) {
-    __shared__ int32_t buf[256];
-    int32_t* row = hist + (size_t)blockIdx.x * n_chunks;
-    int32_t carry = 0;
-    for (int base = 0; base < n_chunks; base += 256) {
-        const int i = base + threadIdx.x;
-        const int32_t x = i < n_chunks ? row[i] : 0;
-        int32_t tot;
-        const int32_t inc = cw_block_scan<256>(x, buf, &tot);
-        if (i < n_chunks) row[i] = carry + inc - x;
-        carry += tot;
-    }
-    if (threadIdx.x == 0) seg[blockIdx.x] = carry;
-}
-
-// seg[0 .. n_sb) totals -> seg[0 .. n_sb] segment starts (one workgroup)
-__global__ __launch_bounds__(CW_TILE) void k_cw_seg(int32_t* seg, int32_t n_sb) {
-    __shared__ int32_t buf[CW_TILE];
-    int32_t carry = 0;
-    for (int base = 0; base < n_sb; base += CW_TILE) {
-        const int i = base + threadIdx.x;
-        const int32_t x = i < n_sb ? seg[i] : 0;
-        int32_t tot;
-        const int32_t inc = cw_block_scan<CW_TILE>(x, buf, &tot);
-        if (i < n_sb) seg[i] = carry + inc - x;
-        carry += tot;
-    }
-    if (threadIdx.x == 0) seg[n_sb] = carry;
-}
-
-__global__ __launch_bounds__(256) void k_cw_scatter(int64_t n, int32_t n_chunks, const int32_t* hist, const int32_t* seg,
-                                                     const int32_t* s_sb, const uint32_t* s_row, const int32_t* s_rank,
-                                                     uint32_t* perm) {
-    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
-    if (i >= n) return;
-    const int32_t sb = s_sb[i];
-    if (sb < 0) return;
-    const int64_t dst = (int64_t)seg[sb] + hist[(size_t)sb * n_chunks + (i / CW_TILE)] + s_rank[i];
-    if (dst < n) perm[dst] = s_row[i];  // (always: the groups' sizes sum to the kept rows)
-}
 
 struct CwFoldArgs {
     const int64_t* key;
@@ -230,7 +57,7 @@ __global__ __launch_bounds__(CW_TILE) void k_cw_fold(CwFoldArgs a) {
 
     for (int64_t base = seg0; base < seg1; base += CW_TILE) {
         const int nt = (int)(seg1 - base < CW_TILE ? seg1 - base : CW_TILE);
-        const int n2 = cw_pow2(nt);
+        const int n2 = fd_pow2(nt);
         if (t == 0) {
             n_fire = 0;
             n_new = 0;
@@ -245,15 +72,15 @@ __global__ __launch_bounds__(CW_TILE) void k_cw_fold(CwFoldArgs a) {
             prow[t] = row;
         } else {
             sk[t] = ~0ull;
-            sp[t] = CW_PAD | (uint32_t)t;
+            sp[t] = FD_PAD | (uint32_t)t;
         }
         __syncthreads();
-        cw_sort(sk, sp, n2);
+        fd_sort(sk, sp, n2);
         const bool valid = t < nt;  // the padding sorted behind the rows
         const bool head = valid && (t == 0 || sk[t - 1] != sk[t]);
         hx[t] = head ? t : 0;
         __syncthreads();
-        cw_max_scan(hx, n2);
+        fd_max_scan(hx, n2);
 
         // ---- the key's table slot: look every distinct key up, then insert the new ones
         int32_t slot = -1;
@@ -397,12 +224,6 @@ __global__ __launch_bounds__(CW_TILE) void k_cw_fold(CwFoldArgs a) {
     }
 }
 
-int64_t cw_next_pow2(int64_t x) {
-    int64_t p = 1;
-    while (p < x) p <<= 1;
-    return p;
-}
-
 int64_t cw_gcd(int64_t a, int64_t b) {
     while (b) {
         const int64_t t = a % b;
@@ -410,14 +231,6 @@ int64_t cw_gcd(int64_t a, int64_t b) {
         b = t;
     }
     return a;
-}
-
-template <typename T>
-int cw_dalloc(T** p, size_t count) {
-    void* v = nullptr;
-    CW_TRY(hipMalloc(&v, std::max<size_t>(count, 1) * sizeof(T)));
-    *p = (T*)v;
-    return FW_OK;
 }
 
 }  // namespace
@@ -474,26 +287,11 @@ int cw_plan(const fw_config& c, CountOp* op) {
     op->pwe = 2 + d.R;
 
     KeySpace& ks = op->ks;
-    ks.hash_kind = c.key_hash;
-    ks.max_p = c.max_parallelism;
-    ks.maxp_div = make_udiv32((uint32_t)c.max_parallelism);
-    ks.kg_start = (c.subtask_index * c.max_parallelism + c.parallelism - 1) / c.parallelism;
-    const int kg_end = ((c.subtask_index + 1) * c.max_parallelism - 1) / c.parallelism;
-    ks.n_kg = kg_end - ks.kg_start + 1;
-    ks.pass_log2 = 0;
-    // about 512 hinted keys per superbucket, at most 2048 superbuckets (one fold workgroup each)
-    const int64_t keys = std::max<int64_t>(c.state_capacity, 1024);
-    op->cap_rows = c.max_batch_rows;
-    op->max_nch = (c.max_batch_rows + CW_TILE - 1) / CW_TILE;
-    int64_t sbk = cw_next_pow2(((keys + 511) / 512 + ks.n_kg - 1) / ks.n_kg);
-    while (sbk > 1 && ((int64_t)ks.n_kg * sbk > 2048 || (int64_t)ks.n_kg * sbk * op->max_nch > CW_MAX_HIST)) sbk >>= 1;
-    if ((int64_t)ks.n_kg * sbk * op->max_nch > CW_MAX_HIST)
-        return set_error(FW_E_INVALID, "count windows: key groups per subtask x max_batch_rows too large for the partition table");
-    ks.sb_per_kg_log2 = 0;
-    while ((1ll << ks.sb_per_kg_log2) < sbk) ks.sb_per_kg_log2++;
-    ks.n_sb = ks.n_kg << ks.sb_per_kg_log2;
+    const int rc = fd_plan_keyspace(c, "count windows", &ks, &op->part);
+    if (rc) return rc;
     // <= 50% load at the hinted capacity
-    const int64_t ce = cw_next_pow2(std::max<int64_t>(64, 2 * ((keys + ks.n_sb - 1) / ks.n_sb)));
+    const int64_t keys = std::max<int64_t>(c.state_capacity, 1024);
+    const int64_t ce = fd_next_pow2(std::max<int64_t>(64, 2 * ((keys + ks.n_sb - 1) / ks.n_sb)));
     if (ce > (1ll << 24)) return set_error(FW_E_INVALID, "count windows: state_capacity too large per superbucket");
     op->cap_e = (int32_t)ce;
     op->out_cap = c.output_capacity;
@@ -506,33 +304,23 @@ int cw_allocate(CountOp* op, hipStream_t stream, Ctrl* ctrl) {
     op->ctrl = ctrl;
     int rc;
     const size_t tw = (size_t)op->ks.n_sb * op->cap_e * op->pwe;
-    if ((rc = cw_dalloc(&op->table, tw))) return rc;
-    CW_TRY(hipMemsetAsync(op->table, 0, tw * 8, stream));
-    if ((rc = cw_dalloc(&op->hist, (size_t)op->ks.n_sb * op->max_nch))) return rc;
-    if ((rc = cw_dalloc(&op->seg, (size_t)op->ks.n_sb + 1))) return rc;
-    if ((rc = cw_dalloc(&op->s_sb, (size_t)op->cap_rows))) return rc;
-    if ((rc = cw_dalloc(&op->s_row, (size_t)op->cap_rows))) return rc;
-    if ((rc = cw_dalloc(&op->s_rank, (size_t)op->cap_rows))) return rc;
-    if ((rc = cw_dalloc(&op->perm, (size_t)op->cap_rows))) return rc;
+    if ((rc = fd_dalloc(&op->table, tw))) return rc;
+    FD_TRY(hipMemsetAsync(op->table, 0, tw * 8, stream));
+    if ((rc = fd_allocate(&op->part, op->ks))) return rc;
     const size_t oc = (size_t)op->out_cap;
-    if ((rc = cw_dalloc(&op->out_key, oc))) return rc;
-    if ((rc = cw_dalloc(&op->out_ws, oc))) return rc;
-    if ((rc = cw_dalloc(&op->out_we, oc))) return rc;
-    if ((rc = cw_dalloc(&op->out_val, oc))) return rc;
-    if ((rc = cw_dalloc(&op->out_ord, oc))) return rc;
-    if ((rc = cw_dalloc(&op->out_null, oc))) return rc;
-    CW_TRY(hipMemsetAsync(op->out_null, 0, oc * 4, stream));
+    if ((rc = fd_dalloc(&op->out_key, oc))) return rc;
+    if ((rc = fd_dalloc(&op->out_ws, oc))) return rc;
+    if ((rc = fd_dalloc(&op->out_we, oc))) return rc;
+    if ((rc = fd_dalloc(&op->out_val, oc))) return rc;
+    if ((rc = fd_dalloc(&op->out_ord, oc))) return rc;
+    if ((rc = fd_dalloc(&op->out_null, oc))) return rc;
+    FD_TRY(hipMemsetAsync(op->out_null, 0, oc * 4, stream));
     return FW_OK;
 }
 
 void cw_free(CountOp* op) {
     hipFree(op->table);
-    hipFree(op->hist);
-    hipFree(op->seg);
-    hipFree(op->s_sb);
-    hipFree(op->s_row);
-    hipFree(op->s_rank);
-    hipFree(op->perm);
+    fd_free(&op->part);
     hipFree(op->out_key);
     hipFree(op->out_ws);
     hipFree(op->out_we);
@@ -545,32 +333,16 @@ int cw_push(CountOp* op, int64_t n, const int64_t* d_key, const int32_t* d_khash
     if (n >= (1ll << 32) || op->push_seq >= (1ll << 30))
         return set_error(FW_E_INVALID, "arrival ordinals need < 2^32 rows per call and < 2^30 calls");
     hipStream_t s = op->stream;
-    const int n_sb = op->ks.n_sb;
-    for (int64_t o = 0; o < n; o += op->cap_rows) {
-        const int64_t m = std::min(op->cap_rows, n - o);
-        const int32_t nch = (int32_t)((m + CW_TILE - 1) / CW_TILE);
-        CW_TRY(hipMemsetAsync(op->hist, 0, (size_t)n_sb * nch * 4, s));
-        CwPartArgs pa{};
-        pa.key = d_key + o;
-        pa.khash = d_khash ? d_khash + o : nullptr;
-        pa.n = m;
-        pa.n_chunks = nch;
-        pa.ks = op->ks;
-        pa.ctrl = op->ctrl;
-        pa.hist = op->hist;
-        pa.s_sb = op->s_sb;
-        pa.s_row = op->s_row;
-        pa.s_rank = op->s_rank;
-        hipLaunchKernelGGL(k_cw_part, dim3(nch), dim3(CW_TILE), 0, s, pa);
-        hipLaunchKernelGGL(k_cw_scan, dim3(n_sb), dim3(256), 0, s, op->hist, op->seg, nch);
-        hipLaunchKernelGGL(k_cw_seg, dim3(1), dim3(CW_TILE), 0, s, op->seg, (int32_t)n_sb);
-        hipLaunchKernelGGL(k_cw_scatter, dim3((unsigned)((m + 255) / 256)), dim3(256), 0, s, m, nch, op->hist, op->seg,
-                           op->s_sb, op->s_row, op->s_rank, op->perm);
+    const int64_t cap_rows = op->part.cap_rows;
+    for (int64_t o = 0; o < n; o += cap_rows) {
+        const int64_t m = std::min(cap_rows, n - o);
+        const int rc = fd_partition(op->part, op->ks, op->ctrl, s, m, d_key + o, d_khash ? d_khash + o : nullptr);
+        if (rc) return rc;
         CwFoldArgs fa{};
         fa.key = d_key + o;
         fa.val = op->is_count ? nullptr : d_val + o;
-        fa.perm = op->perm;
-        fa.seg = op->seg;
+        fa.perm = op->part.perm;
+        fa.seg = op->part.seg;
         fa.d = op->d;
         fa.cap_e = op->cap_e;
         fa.pwe = op->pwe;
@@ -585,8 +357,8 @@ int cw_push(CountOp* op, int64_t n, const int64_t* d_key, const int32_t* d_khash
         fa.out_ord = op->out_ord;
         fa.out_cap = op->out_cap;
         fa.ord_base = (op->push_seq << 32) + o;
-        hipLaunchKernelGGL(k_cw_fold, dim3(n_sb), dim3(CW_TILE), 0, s, fa);
-        CW_TRY(hipGetLastError());
+        hipLaunchKernelGGL(k_cw_fold, dim3(op->ks.n_sb), dim3(CW_TILE), 0, s, fa);
+        FD_TRY(hipGetLastError());
     }
     op->push_seq++;
     return FW_OK;
@@ -612,17 +384,12 @@ const uint64_t CW_KG_MAGIC = 0x464c4b57434b3031ull;  // "FLKWCK01"
 int cw_snapshot(CountOp* op, int32_t key_group, void* buf, int64_t capacity, int64_t* size) {
     const KeySpace& ks = op->ks;
     const int L = ks.sb_per_kg_log2, pwe = op->pwe;
-    int sb0 = 0, sb1 = ks.n_sb;
-    if (key_group >= 0) {
-        const int li = key_group - ks.kg_start;
-        if (li < 0 || li >= ks.n_kg) return set_error(FW_E_INVALID, "key group %d is not owned by this subtask", key_group);
-        sb0 = li << L;
-        sb1 = (li + 1) << L;
-    }
-    CW_TRY(hipStreamSynchronize(op->stream));
+    int sb0 = 0, sb1 = ks.n_sb, rc = 0;
+    if (key_group >= 0 && (rc = fd_sb_range(ks, key_group, &sb0, &sb1))) return rc;
+    FD_TRY(hipStreamSynchronize(op->stream));
     const size_t words = (size_t)(sb1 - sb0) * op->cap_e * pwe;
     std::vector<uint64_t> tab(words);
-    CW_TRY(hipMemcpy(tab.data(), op->table + (size_t)sb0 * op->cap_e * pwe, words * 8, hipMemcpyDeviceToHost));
+    FD_TRY(hipMemcpy(tab.data(), op->table + (size_t)sb0 * op->cap_e * pwe, words * 8, hipMemcpyDeviceToHost));
     std::vector<uint64_t> ent;
     int64_t n = 0;
     for (int sb = sb0; sb < sb1; sb++)
@@ -659,17 +426,12 @@ int cw_restore(CountOp* op, bool key_group, const void* buf, int64_t size) {
     if (hd.n < 0 || size < (int64_t)sizeof hd + hd.n * bw * 8) return set_error(FW_E_INVALID, "count-window snapshot truncated");
     if (ks.hash_kind == KH_PRE && L > hd.sb_log2)
         return set_error(FW_E_INVALID, "precomputed-hash keys cannot be split finer than the snapshot's sub-buckets");
-    int sb0 = 0, sb1 = ks.n_sb;
-    if (key_group) {
-        const int li = hd.key_group - ks.kg_start;
-        if (li < 0 || li >= ks.n_kg) return set_error(FW_E_INVALID, "key group %d is not owned by this subtask", hd.key_group);
-        sb0 = li << L;
-        sb1 = (li + 1) << L;
-    }
-    CW_TRY(hipStreamSynchronize(op->stream));
+    int sb0 = 0, sb1 = ks.n_sb, rc = 0;
+    if (key_group && (rc = fd_sb_range(ks, hd.key_group, &sb0, &sb1))) return rc;
+    FD_TRY(hipStreamSynchronize(op->stream));
     const size_t words = (size_t)(sb1 - sb0) * op->cap_e * pwe;
     std::vector<uint64_t> tab(words, 0);
-    if (key_group) CW_TRY(hipMemcpy(tab.data(), op->table + (size_t)sb0 * op->cap_e * pwe, words * 8, hipMemcpyDeviceToHost));
+    if (key_group) FD_TRY(hipMemcpy(tab.data(), op->table + (size_t)sb0 * op->cap_e * pwe, words * 8, hipMemcpyDeviceToHost));
     std::vector<uint64_t> src((size_t)hd.n * bw);
     if (hd.n) memcpy(src.data(), (const char*)buf + sizeof hd, src.size() * 8);
     const uint32_t mask = (uint32_t)op->cap_e - 1u;
@@ -677,15 +439,7 @@ int cw_restore(CountOp* op, bool key_group, const void* buf, int64_t size) {
         const uint64_t* e = src.data() + (size_t)i * bw;
         const int kg = (int)(e[2] >> 32);
         int sb;
-        if (ks.hash_kind == KH_PRE) {
-            sb = ((kg - ks.kg_start) << L) + (int)((uint32_t)e[2] & (uint32_t)((1 << L) - 1));
-        } else {
-            uint32_t m;
-            sb = route_key(ks, (int64_t)e[0], 0, &m);
-            if (sb >= 0 && sb < ks.n_sb && ks.kg_start + (sb >> L) != kg)
-                return set_error(FW_E_INVALID, "entry key does not belong to key group %d", kg);
-        }
-        if (sb < sb0 || sb >= sb1) return set_error(FW_E_INVALID, "snapshot entry of key group %d is not owned by this subtask", kg);
+        if ((rc = fd_restore_sb(ks, (int64_t)e[0], e[2], sb0, sb1, &sb))) return rc;
         uint64_t* t = tab.data() + (size_t)(sb - sb0) * op->cap_e * pwe;
         uint32_t s = count_slot_hash((int64_t)e[0], mask);
         int p = 0;
@@ -702,21 +456,12 @@ int cw_restore(CountOp* op, bool key_group, const void* buf, int64_t size) {
         if (p == op->cap_e)
             return set_error(FW_E_CAPACITY, "restored state exceeds the key table (%d entries per superbucket)", op->cap_e);
     }
-    CW_TRY(hipMemcpy(op->table + (size_t)sb0 * op->cap_e * pwe, tab.data(), words * 8, hipMemcpyHostToDevice));
+    FD_TRY(hipMemcpy(op->table + (size_t)sb0 * op->cap_e * pwe, tab.data(), words * 8, hipMemcpyHostToDevice));
     Ctrl c;
-    CW_TRY(hipMemcpy(&c, op->ctrl, sizeof c, hipMemcpyDeviceToHost));
-    if (key_group) {
-        c.live_entries += hd.n;
-        op->push_seq = std::max(op->push_seq, hd.push_seq);
-    } else {
-        c.live_entries = hd.n;
-        c.error = 0;
-        c.out_count[0] = 0;
-        op->push_seq = hd.push_seq;
-        op->watermark = hd.watermark;
-        c.cur = hd.watermark;
-    }
-    CW_TRY(hipMemcpy(op->ctrl, &c, sizeof c, hipMemcpyHostToDevice));
+    if ((rc = fd_restored_ctrl(op->ctrl, key_group, hd.n, hd.watermark, &c))) return rc;
+    op->push_seq = key_group ? std::max(op->push_seq, hd.push_seq) : hd.push_seq;
+    if (!key_group) op->watermark = hd.watermark;
+    FD_TRY(hipMemcpy(op->ctrl, &c, sizeof c, hipMemcpyHostToDevice));
     return FW_OK;
 }
 

@@ -156,8 +156,7 @@ FW_HD int session_add(int64_t gap, const int32_t* ops, int64_t watermark, int64_
     return 1;
 }
 
-constexpr int SW_TILE = CW_TILE;                   // rows per tile = threads per workgroup
-constexpr int64_t SW_MAX_HIST = CW_MAX_HIST;       // [superbucket][chunk] partition counters a handle may hold
+constexpr int SW_TILE = FD_TILE;                   // rows per tile = threads per workgroup
 constexpr int64_t SW_SIDE_WORDS = 4;               // late side-output row: key, ts, push_seq << 32 | row, value
 
 // Per-handle state of a session operator.  Superbucket sb's sessions are the first n_s[sb] entries of
@@ -176,8 +175,6 @@ struct SessionOp {
     int32_t val_col = 0;
     int32_t cap_s = 0;        // sessions per superbucket
     int32_t late_side = 0;    // late_side_output
-    int64_t cap_rows = 0;     // rows per launch (max_batch_rows)
-    int64_t max_nch = 0;      // partition chunks per launch
     int64_t out_cap = 0;
     int64_t side_cap = 0;     // late side-output rows: 2 * max_batch_rows
     uint64_t fingerprint = 0; // semantics fingerprint of the snapshot blobs
@@ -187,13 +184,7 @@ struct SessionOp {
     uint64_t* scratch = nullptr;   // [n_sb][cap_s + SW_TILE] sessions: the merged list of one tile's fold
     int32_t* n_s = nullptr;        // [n_sb] sessions held
     int64_t* min_end = nullptr;    // [n_sb] a lower bound of the superbucket's smallest session end
-    // partition scratch of one launch (as the count path's)
-    int32_t* hist = nullptr;
-    int32_t* seg = nullptr;
-    int32_t* s_sb = nullptr;
-    uint32_t* s_row = nullptr;
-    int32_t* s_rank = nullptr;
-    uint32_t* perm = nullptr;
+    FoldedPart part{};             // the superbucket partition's buffers
     // result rows and the late side output
     int64_t* out_key = nullptr;
     int64_t* out_ws = nullptr;

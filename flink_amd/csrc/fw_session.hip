@@ -1,7 +1,7 @@
 // fw_session.hip -- the session-window path (fw_session.h): kernels and the per-handle host code.
 //
-// One push is folded into the state when it is pushed, in five stream-ordered launches: the stable
-// superbucket partition of the count path (k_sw_part / scan / seg / scatter, copies of k_cw_*), then
+// One push is folded into the state when it is pushed: the folded paths' stable superbucket
+// partition (fd_partition, fw_folded.hip: four stream-ordered launches), then
 //   k_sw_fold     one workgroup per superbucket walks its rows in arrival order, a tile at a time:
 //                 LDS sort by (key, ts, position), tile sessions by a segmented scan, merge with the
 //                 sorted state into a scratch list, coalesce by a segmented running max of `end`
@@ -22,20 +22,6 @@
 
 namespace fw {
 namespace {
-
-#define SW_TRY(expr)                                                                                 \
-    do {                                                                                             \
-        hipError_t e_ = (expr);                                                                      \
-        if (e_ != hipSuccess) return set_error(FW_E_DEVICE, "%s: %s", #expr, hipGetErrorString(e_)); \
-    } while (0)
-
-constexpr uint32_t SW_PAD = 0x80000000u;  // position word of a padding element: sorts after every row
-
-__device__ __forceinline__ int sw_pow2(int n) {
-    int p = 2;
-    while (p < n) p <<= 1;
-    return p;
-}
 
 // (padding, key, ts, position) order; positions are unique, so the order is total
 __device__ __forceinline__ bool sw_less(uint64_t ka, int64_t ta, uint32_t pa, uint64_t kb, int64_t tb, uint32_t pb) {
@@ -87,132 +73,6 @@ __device__ void sw_sort32(uint32_t* a, int n2) {
             }
             __syncthreads();
         }
-}
-
-// inclusive max scan of a[0 .. n2); every thread calls it after a barrier; ends with a barrier
-__device__ void sw_max_scan(int32_t* a, int n2) {
-    const int t = threadIdx.x;
-    for (int d = 1; d < n2; d <<= 1) {
-        const bool on = t < n2 && t >= d;
-        const int32_t v = on ? a[t - d] : 0;
-        __syncthreads();
-        if (on && v > a[t]) a[t] = v;
-        __syncthreads();
-    }
-}
-
-// ---- the stable superbucket partition: k_cw_part / k_cw_scan / k_cw_seg / k_cw_scatter of
-// fw_count.hip, copied unchanged in behaviour (they are local to that translation unit)
-struct SwPartArgs {
-    const int64_t* key;
-    const int32_t* khash;
-    int64_t n;
-    int32_t n_chunks;
-    KeySpace ks;
-    Ctrl* ctrl;
-    int32_t* hist;
-    int32_t* s_sb;
-    uint32_t* s_row;
-    int32_t* s_rank;
-};
-
-__global__ __launch_bounds__(SW_TILE) void k_sw_part(SwPartArgs a) {
-    __shared__ uint64_t sk[SW_TILE];
-    __shared__ int64_t sz[SW_TILE];
-    __shared__ uint32_t sp[SW_TILE];
-    __shared__ int32_t hx[SW_TILE];
-    const int t = threadIdx.x;
-    const int64_t c0 = (int64_t)blockIdx.x * SW_TILE;
-    const int nrows = (int)(a.n - c0 < SW_TILE ? a.n - c0 : SW_TILE);
-    const int n2 = sw_pow2(nrows);
-    int32_t sb = -1;
-    if (t < nrows) {
-        uint32_t m;
-        sb = route_key(a.ks, a.key[c0 + t], a.khash ? a.khash[c0 + t] : 0, &m);
-        if (sb < 0 || sb >= a.ks.n_sb) {  // key group outside the subtask's range: the row is dropped
-            atomicOr(&a.ctrl->error, ERR_KEYGROUP);
-            sb = -1;
-        }
-    }
-    sk[t] = sb >= 0 ? (uint64_t)sb : ~0ull;
-    sz[t] = 0;
-    sp[t] = sb >= 0 ? (uint32_t)t : (SW_PAD | (uint32_t)t);
-    __syncthreads();
-    sw_sort(sk, sz, sp, n2);
-    const bool v = t < n2 && !(sp[t] >> 31);
-    const bool head = v && (t == 0 || sk[t - 1] != sk[t]);
-    hx[t] = head ? t : 0;
-    __syncthreads();
-    sw_max_scan(hx, n2);
-    if (v) {
-        const int32_t rank = t - hx[t];
-        const int32_t s = (int32_t)sk[t];
-        a.s_sb[c0 + t] = s;
-        a.s_row[c0 + t] = (uint32_t)(c0 + sp[t]);
-        a.s_rank[c0 + t] = rank;
-        const bool tail = t == n2 - 1 || (sp[t + 1] >> 31) || sk[t + 1] != sk[t];
-        if (tail) a.hist[(size_t)s * a.n_chunks + blockIdx.x] = rank + 1;
-    } else if (t < nrows) {
-        a.s_sb[c0 + t] = -1;
-    }
-}
-
-// inclusive scan over the workgroup's NT threads; every thread calls it; *total = the sum
-template <int NT>
-__device__ int32_t sw_block_scan(int32_t x, int32_t* buf, int32_t* total) {
-    const int t = threadIdx.x;
-    buf[t] = x;
-    __syncthreads();
-    for (int d = 1; d < NT; d <<= 1) {
-        const int32_t v = t >= d ? buf[t - d] : 0;
-        __syncthreads();
-        buf[t] += v;
-        __syncthreads();
-    }
-    const int32_t r = buf[t];
-    *total = buf[NT - 1];
-    __syncthreads();
-    return r;
-}
-
-__global__ __launch_bounds__(256) void k_sw_scan(int32_t* hist, int32_t* seg, int32_t n_chunks) {
-    __shared__ int32_t buf[256];
-    int32_t* row = hist + (size_t)blockIdx.x * n_chunks;
-    int32_t carry = 0;
-    for (int base = 0; base < n_chunks; base += 256) {
-        const int i = base + threadIdx.x;
-        const int32_t x = i < n_chunks ? row[i] : 0;
-        int32_t tot;
-        const int32_t inc = sw_block_scan<256>(x, buf, &tot);
-        if (i < n_chunks) row[i] = carry + inc - x;
-        carry += tot;
-    }
-    if (threadIdx.x == 0) seg[blockIdx.x] = carry;
-}
-
-__global__ __launch_bounds__(SW_TILE) void k_sw_seg(int32_t* seg, int32_t n_sb) {
-    __shared__ int32_t buf[SW_TILE];
-    int32_t carry = 0;
-    for (int base = 0; base < n_sb; base += SW_TILE) {
-        const int i = base + threadIdx.x;
-        const int32_t x = i < n_sb ? seg[i] : 0;
-        int32_t tot;
-        const int32_t inc = sw_block_scan<SW_TILE>(x, buf, &tot);
-        if (i < n_sb) seg[i] = carry + inc - x;
-        carry += tot;
-    }
-    if (threadIdx.x == 0) seg[n_sb] = carry;
-}
-
-__global__ __launch_bounds__(256) void k_sw_scatter(int64_t n, int32_t n_chunks, const int32_t* hist, const int32_t* seg,
-                                                     const int32_t* s_sb, const uint32_t* s_row, const int32_t* s_rank,
-                                                     uint32_t* perm) {
-    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
-    if (i >= n) return;
-    const int32_t sb = s_sb[i];
-    if (sb < 0) return;
-    const int64_t dst = (int64_t)seg[sb] + hist[(size_t)sb * n_chunks + (i / SW_TILE)] + s_rank[i];
-    if (dst < n) perm[dst] = s_row[i];  // (always: the groups' sizes sum to the kept rows)
 }
 
 // ---- the fold ------------------------------------------------------------------------------------
@@ -309,7 +169,7 @@ __global__ __launch_bounds__(SW_TILE) void k_sw_fold(SwFoldArgs a) {
 
     for (int64_t base = seg0; base < seg1; base += SW_TILE) {
         const int nrows = (int)(seg1 - base < SW_TILE ? seg1 - base : SW_TILE);
-        const int n2 = sw_pow2(nrows);
+        const int n2 = fd_pow2(nrows);
         if (t == 0) n_drop = 0;
         bool badgap = false;  // (dynamic) a row with a gap out of range is padding: it adds nothing
         if (DYN && t < nrows) {
@@ -324,7 +184,7 @@ __global__ __launch_bounds__(SW_TILE) void k_sw_fold(SwFoldArgs a) {
         } else {
             sk[t] = ~0ull;
             sts[t] = 0;
-            sp[t] = SW_PAD | (uint32_t)t;
+            sp[t] = FD_PAD | (uint32_t)t;
         }
         hlen[t] = 0;
         int nbad = 0;
@@ -345,7 +205,7 @@ __global__ __launch_bounds__(SW_TILE) void k_sw_fold(SwFoldArgs a) {
         const bool head = valid && (t == 0 || sk[t - 1] != mykey);
         hx[t] = head ? t : 0;
         __syncthreads();
-        sw_max_scan(hx, n2);
+        fd_max_scan(hx, n2);
         const int hi_ = valid ? hx[t] : 0;
         const int rank = t - hi_;
         // a key run that holds a late candidate is folded in arrival order (rule: an element that is
@@ -570,7 +430,7 @@ __global__ __launch_bounds__(SW_TILE) void k_sw_fold(SwFoldArgs a) {
                 __syncthreads();
                 // group index and the reduce of each group
                 int32_t total_heads;
-                const int32_t hcount = sw_block_scan<SW_TILE>(is_head ? 1 : 0, hx, &total_heads);
+                const int32_t hcount = fd_block_scan<SW_TILE>(is_head ? 1 : 0, hx, &total_heads);
                 se[t] = e;
                 sf[t] = is_head ? 1u : 0u;
                 __syncthreads();
@@ -690,7 +550,7 @@ __global__ __launch_bounds__(SW_TILE) void k_sw_advance(SwAdvArgs a) {
     int32_t mine = 0;
     for (int i = t; i < ns; i += SW_TILE) mine += session_due((int64_t)st[(size_t)i * SWS + 2], a.watermark) ? 1 : 0;
     int32_t n_due;
-    sw_block_scan<SW_TILE>(mine, buf, &n_due);
+    fd_block_scan<SW_TILE>(mine, buf, &n_due);
     if (t == 0) {
         out_base = 0;
         if (n_due) {
@@ -720,7 +580,7 @@ __global__ __launch_bounds__(SW_TILE) void k_sw_advance(SwAdvArgs a) {
         }
         const bool due = in && session_due(e, a.watermark);
         int32_t n_f;
-        const int32_t fi = sw_block_scan<SW_TILE>(due ? 1 : 0, buf, &n_f);  // (barriers: the chunk is in registers)
+        const int32_t fi = fd_block_scan<SW_TILE>(due ? 1 : 0, buf, &n_f);  // (barriers: the chunk is in registers)
         const int32_t n_in = ns - c0 < SW_TILE ? ns - c0 : SW_TILE;
         if (due) {
             const unsigned long long o = out_base + (unsigned long long)(fired + fi - 1);
@@ -774,20 +634,6 @@ __global__ __launch_bounds__(SW_TILE) void k_sw_advance(SwAdvArgs a) {
 __global__ void k_sw_fill(int64_t* p, int64_t v, int n) {
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i < n) p[i] = v;
-}
-
-int64_t sw_next_pow2(int64_t x) {
-    int64_t p = 1;
-    while (p < x) p <<= 1;
-    return p;
-}
-
-template <typename T>
-int sw_dalloc(T** p, size_t count) {
-    void* v = nullptr;
-    SW_TRY(hipMalloc(&v, std::max<size_t>(count, 1) * sizeof(T)));
-    *p = (T*)v;
-    return FW_OK;
 }
 
 }  // namespace
@@ -934,26 +780,11 @@ int sw_plan(const fw_config& c, SessionOp* op) {
     const SessionDesc& d = op->d;
 
     KeySpace& ks = op->ks;
-    ks.hash_kind = c.key_hash;
-    ks.max_p = c.max_parallelism;
-    ks.maxp_div = make_udiv32((uint32_t)c.max_parallelism);
-    ks.kg_start = (c.subtask_index * c.max_parallelism + c.parallelism - 1) / c.parallelism;
-    const int kg_end = ((c.subtask_index + 1) * c.max_parallelism - 1) / c.parallelism;
-    ks.n_kg = kg_end - ks.kg_start + 1;
-    ks.pass_log2 = 0;
-    // about 512 hinted sessions per superbucket, at most 2048 superbuckets (one fold workgroup each)
-    const int64_t hint = std::max<int64_t>(c.state_capacity, 1024);
-    op->cap_rows = c.max_batch_rows;
-    op->max_nch = (c.max_batch_rows + SW_TILE - 1) / SW_TILE;
-    int64_t sbk = sw_next_pow2(((hint + 511) / 512 + ks.n_kg - 1) / ks.n_kg);
-    while (sbk > 1 && ((int64_t)ks.n_kg * sbk > 2048 || (int64_t)ks.n_kg * sbk * op->max_nch > SW_MAX_HIST)) sbk >>= 1;
-    if ((int64_t)ks.n_kg * sbk * op->max_nch > SW_MAX_HIST)
-        return set_error(FW_E_INVALID, "session windows: key groups per subtask x max_batch_rows too large for the partition table");
-    ks.sb_per_kg_log2 = 0;
-    while ((1ll << ks.sb_per_kg_log2) < sbk) ks.sb_per_kg_log2++;
-    ks.n_sb = ks.n_kg << ks.sb_per_kg_log2;
+    const int rc = fd_plan_keyspace(c, "session windows", &ks, &op->part);
+    if (rc) return rc;
     // twice the hinted share of a superbucket
-    const int64_t cs = sw_next_pow2(std::max<int64_t>(64, 2 * ((hint + ks.n_sb - 1) / ks.n_sb)));
+    const int64_t hint = std::max<int64_t>(c.state_capacity, 1024);
+    const int64_t cs = fd_next_pow2(std::max<int64_t>(64, 2 * ((hint + ks.n_sb - 1) / ks.n_sb)));
     if (cs > (1ll << 22)) return set_error(FW_E_INVALID, "session windows: state_capacity too large per superbucket");
     op->cap_s = (int32_t)cs;
     op->out_cap = c.output_capacity;
@@ -987,28 +818,23 @@ int sw_allocate(SessionOp* op, hipStream_t stream, Ctrl* ctrl) {
     int rc;
     const int n_sb = op->ks.n_sb;
     const size_t sws = (size_t)sw_stride(op->nw_t);
-    if ((rc = sw_dalloc(&op->state, (size_t)n_sb * op->cap_s * sws))) return rc;
-    if ((rc = sw_dalloc(&op->scratch, (size_t)n_sb * ((size_t)op->cap_s + SW_TILE) * sws))) return rc;
-    if ((rc = sw_dalloc(&op->n_s, (size_t)n_sb))) return rc;
-    SW_TRY(hipMemsetAsync(op->n_s, 0, (size_t)n_sb * 4, stream));
-    if ((rc = sw_dalloc(&op->min_end, (size_t)n_sb))) return rc;
+    if ((rc = fd_dalloc(&op->state, (size_t)n_sb * op->cap_s * sws))) return rc;
+    if ((rc = fd_dalloc(&op->scratch, (size_t)n_sb * ((size_t)op->cap_s + SW_TILE) * sws))) return rc;
+    if ((rc = fd_dalloc(&op->n_s, (size_t)n_sb))) return rc;
+    FD_TRY(hipMemsetAsync(op->n_s, 0, (size_t)n_sb * 4, stream));
+    if ((rc = fd_dalloc(&op->min_end, (size_t)n_sb))) return rc;
     hipLaunchKernelGGL(k_sw_fill, dim3((n_sb + 255) / 256), dim3(256), 0, stream, op->min_end, INT64_MAX, n_sb);
-    if ((rc = sw_dalloc(&op->hist, (size_t)n_sb * op->max_nch))) return rc;
-    if ((rc = sw_dalloc(&op->seg, (size_t)n_sb + 1))) return rc;
-    if ((rc = sw_dalloc(&op->s_sb, (size_t)op->cap_rows))) return rc;
-    if ((rc = sw_dalloc(&op->s_row, (size_t)op->cap_rows))) return rc;
-    if ((rc = sw_dalloc(&op->s_rank, (size_t)op->cap_rows))) return rc;
-    if ((rc = sw_dalloc(&op->perm, (size_t)op->cap_rows))) return rc;
+    if ((rc = fd_allocate(&op->part, op->ks))) return rc;
     const size_t oc = (size_t)op->out_cap;
-    if ((rc = sw_dalloc(&op->out_key, oc))) return rc;
-    if ((rc = sw_dalloc(&op->out_ws, oc))) return rc;
-    if ((rc = sw_dalloc(&op->out_we, oc))) return rc;
+    if ((rc = fd_dalloc(&op->out_key, oc))) return rc;
+    if ((rc = fd_dalloc(&op->out_ws, oc))) return rc;
+    if ((rc = fd_dalloc(&op->out_we, oc))) return rc;
     for (int g = 0; g < op->n_out; g++)
-        if ((rc = sw_dalloc(&op->out_val[g], oc))) return rc;
-    if ((rc = sw_dalloc(&op->out_null, oc))) return rc;
-    SW_TRY(hipMemsetAsync(op->out_null, 0, oc * 4, stream));
-    if (op->side_cap && (rc = sw_dalloc(&op->side, (size_t)op->side_cap * SW_SIDE_WORDS))) return rc;
-    SW_TRY(hipGetLastError());
+        if ((rc = fd_dalloc(&op->out_val[g], oc))) return rc;
+    if ((rc = fd_dalloc(&op->out_null, oc))) return rc;
+    FD_TRY(hipMemsetAsync(op->out_null, 0, oc * 4, stream));
+    if (op->side_cap && (rc = fd_dalloc(&op->side, (size_t)op->side_cap * SW_SIDE_WORDS))) return rc;
+    FD_TRY(hipGetLastError());
     return FW_OK;
 }
 
@@ -1017,12 +843,7 @@ void sw_free(SessionOp* op) {
     hipFree(op->scratch);
     hipFree(op->n_s);
     hipFree(op->min_end);
-    hipFree(op->hist);
-    hipFree(op->seg);
-    hipFree(op->s_sb);
-    hipFree(op->s_row);
-    hipFree(op->s_rank);
-    hipFree(op->perm);
+    fd_free(&op->part);
     hipFree(op->out_key);
     hipFree(op->out_ws);
     hipFree(op->out_we);
@@ -1046,26 +867,11 @@ int sw_push(SessionOp* op, int64_t watermark, int64_t n, const int64_t* d_key, c
         return set_error(FW_E_INVALID, "arrival ordinals need < 2^32 rows per call and < 2^30 calls");
     hipStream_t s = op->stream;
     const int n_sb = op->ks.n_sb;
-    for (int64_t o = 0; o < n; o += op->cap_rows) {
-        const int64_t m = std::min(op->cap_rows, n - o);
-        const int32_t nch = (int32_t)((m + SW_TILE - 1) / SW_TILE);
-        SW_TRY(hipMemsetAsync(op->hist, 0, (size_t)n_sb * nch * 4, s));
-        SwPartArgs pa{};
-        pa.key = d_key + o;
-        pa.khash = d_khash ? d_khash + o : nullptr;
-        pa.n = m;
-        pa.n_chunks = nch;
-        pa.ks = op->ks;
-        pa.ctrl = op->ctrl;
-        pa.hist = op->hist;
-        pa.s_sb = op->s_sb;
-        pa.s_row = op->s_row;
-        pa.s_rank = op->s_rank;
-        hipLaunchKernelGGL(k_sw_part, dim3(nch), dim3(SW_TILE), 0, s, pa);
-        hipLaunchKernelGGL(k_sw_scan, dim3(n_sb), dim3(256), 0, s, op->hist, op->seg, nch);
-        hipLaunchKernelGGL(k_sw_seg, dim3(1), dim3(SW_TILE), 0, s, op->seg, (int32_t)n_sb);
-        hipLaunchKernelGGL(k_sw_scatter, dim3((unsigned)((m + 255) / 256)), dim3(256), 0, s, m, nch, op->hist, op->seg, op->s_sb,
-                           op->s_row, op->s_rank, op->perm);
+    const int64_t cap_rows = op->part.cap_rows;
+    for (int64_t o = 0; o < n; o += cap_rows) {
+        const int64_t m = std::min(cap_rows, n - o);
+        const int rc = fd_partition(op->part, op->ks, op->ctrl, s, m, d_key + o, d_khash ? d_khash + o : nullptr);
+        if (rc) return rc;
         SwFoldArgs fa{};
         fa.key = d_key + o;
         fa.ts = d_ts + o;
@@ -1075,8 +881,8 @@ int sw_push(SessionOp* op, int64_t watermark, int64_t n, const int64_t* d_key, c
             if (gate >= 0) fa.nulls[gate] = d_nulls[gate] + o;
         }
         if (op->dyn) fa.vals[1] = (const uint64_t*)d_vals[1] + o;  // the gap column
-        fa.perm = op->perm;
-        fa.seg = op->seg;
+        fa.perm = op->part.perm;
+        fa.seg = op->part.seg;
         fa.d = op->d;
         for (int w = 0; w < SW_MAX_NW; w++) fa.opsp |= (uint32_t)op->d.ops[w] << (2 * w);
         fa.watermark = watermark;
@@ -1095,7 +901,7 @@ int sw_push(SessionOp* op, int64_t watermark, int64_t n, const int64_t* d_key, c
         } else {
             SW_LAUNCH_NW(k_sw_fold, op->nw_t, dim3(n_sb), dim3(SW_TILE), 0, s, fa);
         }
-        SW_TRY(hipGetLastError());
+        FD_TRY(hipGetLastError());
     }
     op->push_seq++;
     return FW_OK;
@@ -1119,7 +925,7 @@ int sw_advance(SessionOp* op, int64_t watermark) {
     a.out_null = op->out_null;
     a.out_cap = op->out_cap;
     SW_LAUNCH_NW(k_sw_advance, op->nw_t, dim3(op->ks.n_sb), dim3(SW_TILE), 0, op->stream, a);
-    SW_TRY(hipGetLastError());
+    FD_TRY(hipGetLastError());
     return FW_OK;
 }
 
@@ -1145,16 +951,11 @@ constexpr int SW_MAX_BLOB_WORDS = 3 + SW_MAX_NW + 1;
 int sw_snapshot(SessionOp* op, int64_t watermark, int32_t key_group, void* buf, int64_t capacity, int64_t* size) {
     const KeySpace& ks = op->ks;
     const int L = ks.sb_per_kg_log2;
-    int sb0 = 0, sb1 = ks.n_sb;
-    if (key_group >= 0) {
-        const int li = key_group - ks.kg_start;
-        if (li < 0 || li >= ks.n_kg) return set_error(FW_E_INVALID, "key group %d is not owned by this subtask", key_group);
-        sb0 = li << L;
-        sb1 = (li + 1) << L;
-    }
-    SW_TRY(hipStreamSynchronize(op->stream));
+    int sb0 = 0, sb1 = ks.n_sb, rc = 0;
+    if (key_group >= 0 && (rc = fd_sb_range(ks, key_group, &sb0, &sb1))) return rc;
+    FD_TRY(hipStreamSynchronize(op->stream));
     std::vector<int32_t> cnt(sb1 - sb0);
-    SW_TRY(hipMemcpy(cnt.data(), op->n_s + sb0, cnt.size() * 4, hipMemcpyDeviceToHost));
+    FD_TRY(hipMemcpy(cnt.data(), op->n_s + sb0, cnt.size() * 4, hipMemcpyDeviceToHost));
     std::vector<uint64_t> ent, tmp;
     const int SWS = sw_stride(op->nw_t);
     int64_t n = 0;
@@ -1162,7 +963,7 @@ int sw_snapshot(SessionOp* op, int64_t watermark, int32_t key_group, void* buf, 
         const int c = cnt[sb - sb0];
         if (c <= 0) continue;
         tmp.resize((size_t)c * SWS);
-        SW_TRY(hipMemcpy(tmp.data(), op->state + (size_t)sb * op->cap_s * SWS, tmp.size() * 8, hipMemcpyDeviceToHost));
+        FD_TRY(hipMemcpy(tmp.data(), op->state + (size_t)sb * op->cap_s * SWS, tmp.size() * 8, hipMemcpyDeviceToHost));
         for (int i = 0; i < c; i++) {
             ent.insert(ent.end(), tmp.begin() + (size_t)i * SWS, tmp.begin() + (size_t)(i + 1) * SWS);
             ent.push_back((uint64_t)(ks.kg_start + (sb >> L)) << 32 | (uint32_t)(sb & ((1 << L) - 1)));
@@ -1192,17 +993,12 @@ int sw_restore(SessionOp* op, bool key_group, const void* buf, int64_t size, int
     if (hd.n < 0 || size < (int64_t)sizeof hd + hd.n * SW_BLOB_WORDS * 8) return set_error(FW_E_INVALID, "session-window snapshot truncated");
     if (ks.hash_kind == KH_PRE && L > hd.sb_log2)
         return set_error(FW_E_INVALID, "precomputed-hash keys cannot be split finer than the snapshot's sub-buckets");
-    int sb0 = 0, sb1 = ks.n_sb;
-    if (key_group) {
-        const int li = hd.key_group - ks.kg_start;
-        if (li < 0 || li >= ks.n_kg) return set_error(FW_E_INVALID, "key group %d is not owned by this subtask", hd.key_group);
-        sb0 = li << L;
-        sb1 = (li + 1) << L;
-    }
-    SW_TRY(hipStreamSynchronize(op->stream));
+    int sb0 = 0, sb1 = ks.n_sb, rc = 0;
+    if (key_group && (rc = fd_sb_range(ks, hd.key_group, &sb0, &sb1))) return rc;
+    FD_TRY(hipStreamSynchronize(op->stream));
     std::vector<int32_t> cnt(sb1 - sb0, 0);
     if (key_group) {
-        SW_TRY(hipMemcpy(cnt.data(), op->n_s + sb0, cnt.size() * 4, hipMemcpyDeviceToHost));
+        FD_TRY(hipMemcpy(cnt.data(), op->n_s + sb0, cnt.size() * 4, hipMemcpyDeviceToHost));
         for (int32_t c : cnt)
             if (c != 0) return set_error(FW_E_STATE, "key group %d already holds state in this subtask", hd.key_group);
     }
@@ -1216,19 +1012,8 @@ int sw_restore(SessionOp* op, bool key_group, const void* buf, int64_t size, int
     for (int64_t i = 0; i < hd.n; i++) {
         uint64_t e[SW_MAX_BLOB_WORDS];
         memcpy(e, src + (size_t)i * SW_BLOB_WORDS, (size_t)SW_BLOB_WORDS * 8);
-        const uint64_t where = e[SWS];
-        const int kg = (int)(where >> 32);
         int sb;
-        if (ks.hash_kind == KH_PRE) {
-            // the recorded sub-bucket holds the low hd.sb_log2 quotient bits; this handle uses the low L of them
-            sb = ((kg - ks.kg_start) << L) + (int)((uint32_t)where & (uint32_t)((1 << L) - 1));
-        } else {
-            uint32_t m;
-            sb = route_key(ks, (int64_t)e[0], 0, &m);
-            if (sb >= 0 && sb < ks.n_sb && ks.kg_start + (sb >> L) != kg)
-                return set_error(FW_E_INVALID, "entry key does not belong to key group %d", kg);
-        }
-        if (sb < sb0 || sb >= sb1) return set_error(FW_E_INVALID, "snapshot entry of key group %d is not owned by this subtask", kg);
+        if ((rc = fd_restore_sb(ks, (int64_t)e[0], e[SWS], sb0, sb1, &sb))) return rc;
         Ent en{e[0], (int64_t)e[1], (int64_t)e[2], {}};
         for (int w = 0; w < NW; w++) en.acc[w] = e[3 + w];
         per[sb - sb0].push_back(en);
@@ -1250,25 +1035,18 @@ int sw_restore(SessionOp* op, bool key_group, const void* buf, int64_t size, int
         }
         cnt[sb - sb0] = (int32_t)v.size();
         if (!tmp.empty())
-            SW_TRY(hipMemcpy(op->state + (size_t)sb * op->cap_s * SWS, tmp.data(), tmp.size() * 8, hipMemcpyHostToDevice));
+            FD_TRY(hipMemcpy(op->state + (size_t)sb * op->cap_s * SWS, tmp.data(), tmp.size() * 8, hipMemcpyHostToDevice));
     }
-    SW_TRY(hipMemcpy(op->n_s + sb0, cnt.data(), cnt.size() * 4, hipMemcpyHostToDevice));
-    SW_TRY(hipMemcpy(op->min_end + sb0, mins.data(), mins.size() * 8, hipMemcpyHostToDevice));
+    FD_TRY(hipMemcpy(op->n_s + sb0, cnt.data(), cnt.size() * 4, hipMemcpyHostToDevice));
+    FD_TRY(hipMemcpy(op->min_end + sb0, mins.data(), mins.size() * 8, hipMemcpyHostToDevice));
     Ctrl c;
-    SW_TRY(hipMemcpy(&c, op->ctrl, sizeof c, hipMemcpyDeviceToHost));
-    if (key_group) {
-        c.live_entries += hd.n;
-        op->push_seq = std::max(op->push_seq, hd.push_seq);
-    } else {
-        c.live_entries = hd.n;
-        c.error = 0;
-        c.out_count[0] = 0;
+    if ((rc = fd_restored_ctrl(op->ctrl, key_group, hd.n, hd.watermark, &c))) return rc;
+    op->push_seq = key_group ? std::max(op->push_seq, hd.push_seq) : hd.push_seq;
+    if (!key_group) {
         c.n_side = 0;
-        op->push_seq = hd.push_seq;
         *watermark = hd.watermark;
-        c.cur = hd.watermark;
     }
-    SW_TRY(hipMemcpy(op->ctrl, &c, sizeof c, hipMemcpyHostToDevice));
+    FD_TRY(hipMemcpy(op->ctrl, &c, sizeof c, hipMemcpyHostToDevice));
     return FW_OK;
 }
 

@@ -109,17 +109,17 @@ def plain_reference(kind):
 
 def tile_sessions(push):
     """the sessions the push's rows form among themselves under no watermark: what k_sw_fold counts as
-    `may_add` (fw_session.hip:389) for a tile without late candidates"""
+    `may_add` (fw_session.hip:249) for a tile without late candidates"""
     ref = plain_reference(push.kind)
     push.feed(ref)
     return ref.live_sessions()
 
 
 class CappedReference:
-    """The plain reference under the contract k_sw_fold's comments give (fw_session.hip:633-639): a push
+    """The plain reference under the contract k_sw_fold's comments give (fw_session.hip:493-499): a push
     is cut into tiles of 1024 rows; a tile is fed to a copy of the reference; if the copy then holds more
     than ``cap_s`` sessions the copy's sessions are thrown away -- the tile is dropped whole -- but its
-    late drops stay counted (the kernel counts them at :486-515, before it decides) and the STATE bit
+    late drops stay counted (the kernel counts them at :346-375, before it decides) and the STATE bit
     is up; otherwise the copy becomes the reference.  All keys share one superbucket, so the list's
     length is the reference's live sessions.  ``cap_s`` None: no cap."""
 
@@ -178,7 +178,7 @@ class CappedReference:
 def merged_order(state, push):
     """the order of k_sw_fold's merged list M for a tile without late candidates: every held session
     (key, start) and every row (key, ts) by key, then time, a session before a row of its time
-    (fw_session.hip:432-467).  ``state``: [(key, start)].  Entries are ("s" | "r", key, time)."""
+    (fw_session.hip:292-327).  ``state``: [(key, start)].  Entries are ("s" | "r", key, time)."""
     ent = [(int(k), int(s), 0) for k, s in state] + [(int(k), int(t), 1) for k, t in zip(push.k, push.ts)]
     ent.sort()
     return [("sr"[tag], k, t) for k, t, tag in ent]

@@ -32,7 +32,7 @@ pytestmark = pytest.mark.gpu
 
 T0 = 1_600_000_000_000      # a multiple of 2 s, 4 s and 10 s
 MBR = 1 << 14               # max_batch_rows of every case but ORDEV; pushes are exactly this long
-CAP = max(2 * MBR, 1 << 16)  # treq_cap = lfire_cap = side_cap (fw_api.hip:769: max(2 * max_batch_rows, 65536))
+CAP = max(2 * MBR, 1 << 16)  # treq_cap = lfire_cap = side_cap (fw_api.hip:774: max(2 * max_batch_rows, 65536))
 N_OVER = 5                  # overflowing pushes: 81 920 rows against 65 536
 OUT_CAP = 4096              # output_capacity of the OUTPUT cases: 128 superbuckets, 64-row slabs
 ERRF = abi.ERRF
@@ -482,7 +482,7 @@ def test_first_element_event_capacity():
     mbr, scap, size = 1 << 12, 1 << 12, 4000
     kw = dict(api=abi.API_DATASTREAM, window_kind=abi.WIN_TUMBLE, size_ms=size, aggs=[(abi.AGG_SUM, 0, I64)])
     cfg = _cfg(kw, ds_first_ordinals=True, max_batch_rows=mbr, state_capacity=scap)
-    # fw_api.hip:776-777: ordev_cap = (FW_MAX_PENDING * cap_rows + state_capacity) * n_win + 65536, with
+    # fw_api.hip:781-782: ordev_cap = (FW_MAX_PENDING * cap_rows + state_capacity) * n_win + 65536, with
     # cap_rows = max_batch_rows rounded up to ingest chunks of 4096 rows and one window per element
     ordev_cap = (8 * mbr + scap) * 1 + (1 << 16)
     n_steps = ordev_cap // (2 * mbr) + 1  # every step leaves 4096 retains and 4096 releases
@@ -689,7 +689,7 @@ def test_key_row_table_full():
     runs the collection with the id counter past cap_ids."""
     mbr = 256
     cfg, ocfg = _kr_cfgs(mbr)
-    cap_ids = max(1024, 1024 + 8 * mbr)  # fw_api.hip:784: max(1024, state_capacity + FW_MAX_PENDING * max_batch_rows)
+    cap_ids = max(1024, 1024 + 8 * mbr)  # fw_api.hip:789: max(1024, state_capacity + FW_MAX_PENDING * max_batch_rows)
     rng = np.random.default_rng(9)
     warm = _push_of(rng, np.arange(100, dtype=np.int64) + 100_000, T0 + 20_000 + rng.integers(0, 2000, 100))
     wins = [_push_of(rng, np.arange(1100, dtype=np.int64) + 2000 * w, T0 + 2000 * w + rng.integers(0, 2000, 1100))

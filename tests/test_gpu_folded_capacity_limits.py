@@ -8,8 +8,8 @@ stable, so tile j of a push is its rows [1024 j, 1024 (j + 1)): the inputs (fold
 checked on the CPU by test_folded_capacity_inputs.py) sit exactly on each edge.  Every comparison goes
 through the path's own `_same` / `_check` (integers and NULL masks exactly, the one DOUBLE SUM / AVG
 layout at 1e-9 relative) and leaves out no row.  While an error bit is up every reader but stats and
-snapshot refuses with FW_E_CAPACITY (read_ctrl, fw_api.hip:1029); only a whole-handle restore clears
-the bits (fw_session.hip:1262-1270, fw_count.hip:711-717).  DESIGN section 9 states the contract."""
+snapshot refuses with FW_E_CAPACITY (read_ctrl, fw_api.hip:1036); only a whole-handle restore clears
+the bits (fd_restored_ctrl, fw_folded.hip:211-215; n_side in fw_session.hip:1046).  DESIGN section 9 states the contract."""
 import numpy as np
 import pytest
 import test_gpu_count_windows as cw
@@ -134,10 +134,10 @@ def _tight_tile(kind, c, **kw):
 @pytest.mark.parametrize("final", [63, 64, 65])
 def test_tight_tile_at_the_small_lists_capacity(kind, final):
     """Case 1.  cap_s = 64, 40 held sessions, one tile after which the list holds 63, 64 or 65:
-    `ns + may_add > cap_s` (fw_session.hip:389-390), so the coalesce runs twice (:521), pass 0 counting
-    and pass 1 writing with the carries reset between them (:522-530) and sa / sk / sts / se used again.
-    63 and 64 fit -- `c_groups == cap_s` is not `> cap_s` (:633) -- and fire what the reference fires;
-    65 raises STATE alone and leaves the list's bytes as they were (:636-639).  Every fold instance:
+    `ns + may_add > cap_s` (fw_session.hip:249-250), so the coalesce runs twice (:381), pass 0 counting
+    and pass 1 writing with the carries reset between them (:382-390) and sa / sk / sts / se used again.
+    63 and 64 fit -- `c_groups == cap_s` is not `> cap_s` (:493) -- and fire what the reference fires;
+    65 raises STATE alone and leaves the list's bytes as they were (:496-499).  Every fold instance:
     k_sw_fold<1>, <1, true>, <2>, <4>, <8>."""
     _tight_tile(kind, case1(kind, final))
 
@@ -146,19 +146,19 @@ def test_tight_tile_at_the_small_lists_capacity(kind, final):
 @pytest.mark.parametrize("n_new", [24, 25])
 def test_tight_tile_over_two_chunks_with_a_group_across_the_boundary(kind, n_new):
     """Case 2.  cap_s = 1024, 1000 held sessions and a full tile: L = 2024 spans two 1024-entry chunks of
-    M in both passes (fw_session.hip:532).  Key 500's tile session starts at entry 1000, its dead slots
+    M in both passes (fw_session.hip:392).  Key 500's tile session starts at entry 1000, its dead slots
     cross entry 1023 / 1024 and its held session at entry 1040 joins through the carries c_key / c_max
-    (:563-566) and c_acc / c_end, the `hcount == 0` branch (:601-605).  24 new sessions fill the list
-    exactly (1024), 25 are one too many (:633)."""
+    (:423-426) and c_acc / c_end, the `hcount == 0` branch (:461-465).  24 new sessions fill the list
+    exactly (1024), 25 are one too many (:493)."""
     _tight_tile(kind, case2(kind, n_new), max_parallelism=1)
 
 
 @pytest.mark.parametrize("kind", KINDS)
 def test_tile_dropped_in_the_middle_of_a_push(kind):
     """Case 3.  Three tiles in one push: tile 0 fits (50 sessions), tile 1 does not (80) and is dropped,
-    and the loop goes on (`continue`, fw_session.hip:636-639) to tile 2, which joins held sessions, tile
+    and the loop goes on (`continue`, fw_session.hip:496-499) to tile 2, which joins held sessions, tile
     0's among them.  STATE alone; the next collection raises FW_E_CAPACITY; a restore of the snapshot of
-    before the push clears the bit (:1264), and the push without tile 1's rows then leaves the very
+    before the push clears the bit (fw_folded.hip:213), and the push without tile 1's rows then leaves the very
     bytes the three-tile push left, and fires what the plain reference fires."""
     c = case3(kind)
     op, ref = _seeded(kind, c)
@@ -187,12 +187,12 @@ def _late_rows(lr):
 @pytest.mark.parametrize("kind", ["static", "dynamic"])
 @pytest.mark.parametrize("over", [False, True])
 def test_late_rows_of_a_tile_at_the_list_capacity(kind, over):
-    """Case 4.  A tile with late candidates (the serial path, fw_session.hip:470-512) -- 20 anchored and
+    """Case 4.  A tile with late candidates (the serial path, fw_session.hip:330-372) -- 20 anchored and
     kept, 15 unreachable and dropped -- that ends at 64 sessions, or at 65 and is dropped.  The kernel
-    counts the 15 and writes their side rows (:486-500) before it decides (:633), so they are counted
+    counts the 15 and writes their side rows (:346-360) before it decides (:493), so they are counted
     either way.  At 64 late_records() delivers exactly them.  At 65 STATE is up, late_records() refuses
-    (sw_late_records reads through read_ctrl, fw_api.hip:2167), and the restore that clears the bit also
-    clears n_side (:1266): the 15 stay counted in num_late_records_dropped, which a restore into the
+    (sw_late_records reads through read_ctrl, fw_api.hip:2176), and the restore that clears the bit also
+    clears n_side (:1046): the 15 stay counted in num_late_records_dropped, which a restore into the
     same handle does not reset, and are never delivered."""
     c = case4(kind, over)
     op, ref = _seeded(kind, c, late_side_output=True)
@@ -222,8 +222,8 @@ def test_late_rows_of_a_tile_at_the_list_capacity(kind, over):
 def test_lists_longer_than_one_tile():
     """Case 5.  cap_s = 2048 (state_capacity 2^21: 2048 superbuckets of 2048 sessions, a few hundred MB
     of state and scratch).  1500 sessions in one superbucket: a joining tile whose L = 2524 spans three
-    chunks of M with pass 0 run (fw_session.hip:521, :532); a watermark that fires an interleaved 700,
-    so k_sw_advance's chunk loop (:707) runs twice and its stable compaction (:748) moves 256 kept
+    chunks of M with pass 0 run (fw_session.hip:381, :392); a watermark that fires an interleaved 700,
+    so k_sw_advance's chunk loop (:567) runs twice and its stable compaction (:608) moves 256 kept
     sessions of chunk 1 into chunk 0's slots; a full tile on the 800 left (L = 1824); the final
     watermark.  No capacity is exceeded: this is the list-size edge."""
     c = case5()
@@ -248,13 +248,13 @@ def test_lists_longer_than_one_tile():
 @pytest.mark.parametrize("how", ["snapshot", "key_groups"])
 def test_session_output_capacity(kind, how):
     """Case 6.  output_capacity = 64, sessions over many superbuckets, so many workgroups claim rows
-    (fw_session.hip:697).  A watermark that fires exactly 64 is clean (`out_base + n_due > out_cap`,
-    :700, is false at 64).  One that fires 65 raises OUTPUT alone; fw_get_stats clamps results_available
-    to 64 (fw_api.hip:2269), the collection refuses (cw_results, fw_api.hip:1823-1828), and the 65
-    sessions are gone from the state (:699, :727): only a restore brings them back -- the whole-handle
-    snapshot into the same handle, which clears `error` and `out_count[0]` (:1264-1265), or key-group
+    (fw_session.hip:557).  A watermark that fires exactly 64 is clean (`out_base + n_due > out_cap`,
+    :560, is false at 64).  One that fires 65 raises OUTPUT alone; fw_get_stats clamps results_available
+    to 64 (fw_api.hip:2278), the collection refuses (cw_results, fw_api.hip:1832-1837), and the 65
+    sessions are gone from the state (:559, :587): only a restore brings them back -- the whole-handle
+    snapshot into the same handle, which clears `error` and `out_count[0]` (fw_folded.hip:213-214), or key-group
     snapshots into a fresh one (sw_restore(key_group) needs an empty key group and clears nothing,
-    :1259-1262).  Either way the 65 then come out exactly, read over two watermarks."""
+    fw_folded.hip:209-210).  Either way the 65 then come out exactly, read over two watermarks."""
     c = case6(kind)
     op, ref, fresh = _open(kind, output_capacity=OUT_CAP), CappedReference(kind), None
     try:
@@ -293,11 +293,11 @@ def test_session_output_capacity(kind, how):
 
 @pytest.mark.parametrize("n", [2048, 2049])
 def test_late_side_capacity(n):
-    """Case 7.  max_batch_rows = 1024, so the side output holds 2048 rows (fw_session.hip:960).  2048 late
-    rows uncollected are clean (`o < side_cap`, :491) and all come out with their (push_seq, row, ts,
-    value).  The 2049th raises LATE alone (:498); n_side goes on counting and the host clamps it
-    (fw_api.hip:2169) -- but late_records() refuses while the bit is up, and the restore that clears it
-    clears n_side too (:1266).  num_late_records_dropped is 2049 before and after; the handle then works
+    """Case 7.  max_batch_rows = 1024, so the side output holds 2048 rows (fw_session.hip:791).  2048 late
+    rows uncollected are clean (`o < side_cap`, :351) and all come out with their (push_seq, row, ts,
+    value).  The 2049th raises LATE alone (:358); n_side goes on counting and the host clamps it
+    (fw_api.hip:2178) -- but late_records() refuses while the bit is up, and the restore that clears it
+    clears n_side too (:1046).  num_late_records_dropped is 2049 before and after; the handle then works
     again, with the snapshot's push_seq."""
     c = case7(n)
     op, ref = _open("static", late_side_output=True, max_batch_rows=1024), CappedReference("static")
@@ -361,10 +361,10 @@ def _entries(blob, size, slide):
 @pytest.mark.parametrize("agg", COUNT_AGGS, ids=lambda a: a[0])
 def test_count_table_full_then_two_more_keys(size, slide, agg):
     """Case 8.  cap_e = 64 and 64 keys in one superbucket: every slot is usable -- the probe runs over
-    all cap_e slots (fw_count.hip:265, :281) -- and nothing is raised.  A push with two more keys raises
-    STATE alone (:294); the two keys get nothing, the table still holds 64, and the 64 keys' windows of
+    all cap_e slots (fw_count.hip:92, :108) -- and nothing is raised.  A push with two more keys raises
+    STATE alone (:121); the two keys get nothing, the table still holds 64, and the 64 keys' windows of
     that push are fired and counted -- but not delivered: collect() refuses while the bit is up
-    (cw_results, fw_api.hip:1823).  The route is restore and replay: the snapshot of before the push,
+    (cw_results, fw_api.hip:1832).  The route is restore and replay: the snapshot of before the push,
     and the push without the two keys' rows, deliver the reference's rows of the 64 keys in its order.
     The table the overflowing push left (a snapshot is not refused) holds the very entries the replay
     leaves, and restored it goes on exactly."""
@@ -411,9 +411,9 @@ def test_count_table_full_then_two_more_keys(size, slide, agg):
 @pytest.mark.parametrize("agg", COUNT_AGGS, ids=lambda a: a[0])
 def test_count_table_all_or_nothing_per_key_under_a_race(size, slide, agg):
     """Case 9.  One tile with 54 held keys and 40 new ones for 10 free slots: which 10 win the atomicCAS
-    (fw_count.hip:282) is not determined.  The invariant: the table then holds the 54 and a set S of
+    (fw_count.hip:109) is not determined.  The invariant: the table then holds the 54 and a set S of
     exactly 10 new keys, each with all of its rows (its count is its rows so far) -- a key is kept
-    whole or dropped whole (:294, `live` at :305) -- the windows fired are the reference's for the 54 and
+    whole or dropped whole (:121, `live` at :132) -- the windows fired are the reference's for the 54 and
     S, and the table restored (which clears STATE) goes on exactly for the 54 and S: the rows of the next
     push equal the reference's, whose windows reach back into the race tile."""
     c = case9(size, slide)
@@ -455,10 +455,10 @@ def test_count_table_all_or_nothing_per_key_under_a_race(size, slide, agg):
 @pytest.mark.parametrize("how", ["snapshot", "key_groups"])
 def test_count_output_capacity(size, slide, agg, how):
     """Case 10.  output_capacity = 64: a push that fires exactly 64 windows is clean (`o < out_cap`,
-    fw_count.hip:368); one that fires 65 raises OUTPUT alone (:378), fw_get_stats clamps
-    results_available to 64 (fw_api.hip:2253), collect() refuses, and the rings have moved on
-    (:384-394).  The whole-handle snapshot of before the push into the same handle (clears `error` and
-    `out_count[0]`, :713-714), or key-group snapshots into a fresh one, and the push in two parts
+    fw_count.hip:195); one that fires 65 raises OUTPUT alone (:205), fw_get_stats clamps
+    results_available to 64 (fw_api.hip:2262), collect() refuses, and the rings have moved on
+    (:211-221).  The whole-handle snapshot of before the push into the same handle (clears `error` and
+    `out_count[0]`, fw_folded.hip:213-214), or key-group snapshots into a fresh one, and the push in two parts
     deliver the 65 exactly."""
     c = case10(size, slide)
     (k1, v1), (k2, v2) = c["pushes"]
