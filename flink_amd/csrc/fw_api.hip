@@ -1352,6 +1352,13 @@ extern "C" {
 #define CW_REFUSE(h, name)                                                       \
     if ((h)->cw.on) return fail(FW_E_INVALID, name ": not for count windows");   \
     if ((h)->sw.on) return fail(FW_E_INVALID, name ": not for session windows")
+// The push entry points behind the N > 1 keyBy exchange (fw_push_device_segments,
+// fw_push_device_packed_segments; fw_advance_device likewise): a session handle has them iff its
+// configuration has parallelism > 1 -- only such a handle has an exchange in front of it.  One of
+// parallelism 1 refuses them as ever, and so does every count handle.
+#define CW_REFUSE_EXCHANGE(h, name)                                              \
+    if ((h)->cw.on) return fail(FW_E_INVALID, name ": not for count windows");   \
+    if ((h)->sw.on && (h)->cfg.parallelism <= 1) return fail(FW_E_INVALID, name ": not for session windows")
 
 const char* fw_last_error(void) { return g_err.c_str(); }
 int fw_abi_version(void) { return FW_ABI_VERSION; }
@@ -1708,7 +1715,7 @@ int fw_push_device_segments(fw_handle* h, int32_t n_segs, int64_t seg_len, const
                             const int64_t* d_key, const int64_t* d_ts, const int32_t* d_key_hash,
                             const void* const* d_values, const uint8_t* const* d_nulls) {
     if (!h) return fail(FW_E_INVALID, "null handle");
-    CW_REFUSE(h, "fw_push_device_segments");
+    CW_REFUSE_EXCHANGE(h, "fw_push_device_segments");
     if (n_segs < 0 || seg_len < 1 || (n_segs > 0 && !d_seg_counts)) return fail(FW_E_INVALID, "bad segments");
     if (h->keyrow) return fail(FW_E_INVALID, "a FW_KEYHASH_KEYROW operator takes key rows (fw_push_device_key_rows)");
     const int64_t n = (int64_t)n_segs * seg_len;
@@ -1722,13 +1729,17 @@ int fw_push_device_segments(fw_handle* h, int32_t n_segs, int64_t seg_len, const
         if (((h->cfg.nullable_cols >> v) & 1u) && (!d_nulls || !d_nulls[v]))
             return fail(FW_E_INVALID, "nullable value column %d needs its null-flag column", v);
     }
+    if (h->sw.on) {  // folded now, under Ctrl::cur at this point of the stream
+        ar_kick(h);
+        return sw_push_segments(&h->sw, n_segs, seg_len, d_seg_counts, d_key, d_ts, 1, d_key_hash, d_values, d_nulls);
+    }
     return push(h, n, d_key, d_ts, d_key_hash, d_values, d_nulls, d_seg_counts, seg_len);
 }
 
 int fw_push_device_packed_segments(fw_handle* h, int32_t n_segs, int64_t seg_len, const int64_t* d_seg_counts,
                                    const int64_t* d_rows, int32_t row_words) {
     if (!h) return fail(FW_E_INVALID, "null handle");
-    CW_REFUSE(h, "fw_push_device_packed_segments");
+    CW_REFUSE_EXCHANGE(h, "fw_push_device_packed_segments");
     if (n_segs < 0 || seg_len < 1 || (n_segs > 0 && !d_seg_counts)) return fail(FW_E_INVALID, "bad segments");
     if (row_words != 2 + h->cfg.n_value_cols) return fail(FW_E_INVALID, "row_words %d != 2 + value columns", row_words);
     if (h->cfg.key_hash == FW_KEYHASH_PRECOMPUTED || h->keyrow || h->cfg.nullable_cols)
@@ -1738,6 +1749,10 @@ int fw_push_device_packed_segments(fw_handle* h, int32_t n_segs, int64_t seg_len
     if (!d_rows) return fail(FW_E_INVALID, "null rows");
     const void* vals[FW_MAX_COLS] = {nullptr};
     for (int c = 0; c < h->cfg.n_value_cols; c++) vals[c] = d_rows + 2 + c;
+    if (h->sw.on) {
+        ar_kick(h);
+        return sw_push_segments(&h->sw, n_segs, seg_len, d_seg_counts, d_rows, d_rows + 1, row_words, nullptr, vals, nullptr);
+    }
     return push(h, n, d_rows, d_rows + 1, nullptr, vals, nullptr, d_seg_counts, seg_len, row_words);
 }
 
@@ -1749,6 +1764,9 @@ int fw_advance(fw_handle* h, int64_t watermark) {
         return FW_OK;
     }
     if (h->sw.on) {  // EventTimeTrigger: every session with end - 1 <= watermark fires; W' <= W changes nothing
+        // once advanced from the device the host's mirror is only a lower bound of Ctrl::cur: the
+        // device takes the maximum
+        if (h->sw.wm_dev) return sw_advance_device(&h->sw, nullptr, watermark);
         if (watermark <= h->host_cur) return FW_OK;
         h->host_cur = watermark;
         HIP_TRY(hipMemcpyAsync(&h->ctrl->cur, &h->host_cur, sizeof(int64_t), hipMemcpyHostToDevice, h->stream));
@@ -1783,7 +1801,14 @@ int fw_advance(fw_handle* h, int64_t watermark) {
 
 int fw_advance_device(fw_handle* h, const int64_t* d_watermark) {
     if (!h || !d_watermark) return fail(FW_E_INVALID, "null argument");
-    if (h->sw.on) return fail(FW_E_INVALID, "fw_advance_device: not for session windows (the late test needs the watermark on the host)");
+    if (h->sw.on) {
+        // parallelism 1: no exchange, no device valve; the fold takes its watermark from the host
+        if (h->cfg.parallelism <= 1)
+            return fail(FW_E_INVALID, "fw_advance_device: not for session windows (the late test needs the watermark on the host)");
+        // parallelism > 1: Ctrl::cur becomes the watermark of record (W' = max(cur, *d_watermark));
+        // two stream-ordered launches, no host wait
+        return sw_advance_device(&h->sw, d_watermark, INT64_MIN);
+    }
     if (h->cw.on) {  // recorded on the device (fw_stats.current_watermark), nothing fires
         HIP_TRY(hipMemcpyAsync(&h->ctrl->cur, d_watermark, sizeof(int64_t), hipMemcpyDeviceToDevice, h->stream));
         return FW_OK;
@@ -2271,6 +2296,7 @@ int fw_get_stats(fw_handle* h, fw_stats* out) {
         HIP_TRY(hipMemcpyAsync(&cc, h->ctrl, sizeof(Ctrl), hipMemcpyDeviceToHost, h->stream));
         HIP_TRY(hipStreamSynchronize(h->stream));
         memset(out, 0, sizeof *out);
+        if (h->sw.wm_dev) h->host_cur = cc.cur;  // the watermark of record, behind the synchronisation above
         out->current_watermark = h->host_cur;
         out->next_trigger_progress = INT64_MAX;
         out->num_late_records_dropped = (int64_t)cc.late_dropped;
@@ -2553,7 +2579,11 @@ int fw_snapshot(fw_handle* h, void* buf, int64_t capacity, int64_t* size) {
         h->cw.watermark = h->host_cur;
         return cw_snapshot(&h->cw, -1, buf, capacity, size);
     }
-    if (h->sw.on) return sw_snapshot(&h->sw, h->host_cur, -1, buf, capacity, size);
+    if (h->sw.on) {
+        int rc_wm;
+        if (h->sw.wm_dev && (rc_wm = sw_read_watermark(&h->sw, &h->host_cur))) return rc_wm;
+        return sw_snapshot(&h->sw, h->host_cur, -1, buf, capacity, size);
+    }
     int rc = force_flush(h);  // prepareSnapshotPreBarrier -> windowBuffer.flush()
     if (rc) return rc;
     Ctrl c;
@@ -2737,6 +2767,8 @@ int fw_snapshot_key_group(fw_handle* h, int32_t key_group, void* buf, int64_t ca
     }
     if (h->sw.on) {
         if (key_group < 0) return fail(FW_E_INVALID, "key group %d is not owned by this subtask", key_group);
+        int rc_wm;
+        if (h->sw.wm_dev && (rc_wm = sw_read_watermark(&h->sw, &h->host_cur))) return rc_wm;
         return sw_snapshot(&h->sw, h->host_cur, key_group, buf, capacity, size);
     }
     const KeySpace& ks = h->ks;

@@ -128,6 +128,16 @@ void fd_free(FoldedPart* part);
 // ERR_KEYGROUP.  Stream-ordered; the launches' errors are the caller's hipGetLastError to collect.
 int fd_partition(const FoldedPart& part, const KeySpace& ks, Ctrl* ctrl, hipStream_t stream, int64_t n, const int64_t* d_key,
                  const int32_t* d_khash);
+// The same over a launch's part of a padded exchange receive buffer: n_segs segments of seg_len rows,
+// segment s holding min(d_seg_counts[s], seg_len) live rows in front of its padding.  The launch covers
+// the buffer's rows [row0, row0 + n) (a call longer than cap_rows is split by buffer position, so a
+// segment may straddle launches); its row i has its key at d_key[i * stride] (1: a column, row_words:
+// packed rows) and its hash at d_khash[i].  A padding row is left out like a chunk's tile padding: it
+// is never routed and raises nothing, whatever bytes it holds; a live row of a foreign key group is
+// left out and raises ERR_KEYGROUP.  part->perm holds launch-local indices, buffer position order
+// inside a superbucket.
+int fd_partition_segments(const FoldedPart& part, const KeySpace& ks, Ctrl* ctrl, hipStream_t stream, int64_t n, const int64_t* d_key,
+                          int32_t stride, const int32_t* d_khash, const int64_t* d_seg_counts, int64_t seg_len, int64_t row0);
 
 // ---- snapshot / restore
 // the superbuckets [*sb0, *sb1) of key group `key_group`, which the subtask must own

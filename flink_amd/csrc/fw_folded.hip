@@ -10,6 +10,9 @@
 //   k_fd_seg      exclusive scan of the superbucket totals: segment starts
 //   k_fd_scatter  row indices to their segment, input order kept inside a superbucket
 // No workgroup waits on another.
+// k_fd_part_seg is k_fd_part over a padded exchange receive buffer (fd_partition_segments): the same
+// body, with the rows behind a segment's count treated as tile padding.  The unsegmented k_fd_part is
+// the instance the count path and direct pushes launch, unchanged.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -32,7 +35,21 @@ struct PartArgs {
     int32_t* s_rank;
 };
 
-__global__ __launch_bounds__(FD_TILE) void k_fd_part(PartArgs a) {
+// The segmented form's view of the launch (fd_partition_segments): the launch's row i is row row0 + i
+// of a padded buffer of segments of seg_len rows, live iff its index inside its segment is below
+// min(seg_counts[segment], seg_len) (a count above seg_len: the overflow went to the spill, as in the
+// ingest's seg_counts test), and its key is a.key[i * stride].
+struct PartSegArgs {
+    const int64_t* seg_counts;
+    int64_t seg_len;
+    int64_t row0;
+    int32_t stride;
+};
+
+// SEG: a padding row is sorted out like tile padding, whatever bytes it holds -- it is not routed,
+// so it raises nothing
+template <bool SEG>
+__device__ __forceinline__ void fd_part_body(const PartArgs& a, const PartSegArgs& g) {
     __shared__ uint64_t sk[FD_TILE];
     __shared__ uint32_t sp[FD_TILE];
     __shared__ int32_t hx[FD_TILE];
@@ -41,9 +58,15 @@ __global__ __launch_bounds__(FD_TILE) void k_fd_part(PartArgs a) {
     const int nrows = (int)(a.n - c0 < FD_TILE ? a.n - c0 : FD_TILE);
     const int n2 = fd_pow2(nrows);
     int32_t sb = -1;
-    if (t < nrows) {
+    bool live = t < nrows;
+    if (SEG && live) {
+        const int64_t pos = g.row0 + c0 + t;
+        const int64_t sg = pos / g.seg_len;
+        live = pos - sg * g.seg_len < g.seg_counts[sg];  // (an index is below seg_len already)
+    }
+    if (live) {
         uint32_t m;
-        sb = route_key(a.ks, a.key[c0 + t], a.khash ? a.khash[c0 + t] : 0, &m);
+        sb = route_key(a.ks, a.key[SEG ? (c0 + t) * g.stride : c0 + t], a.khash ? a.khash[c0 + t] : 0, &m);
         if (sb < 0 || sb >= a.ks.n_sb) {  // key group outside the subtask's range: the row is dropped
             atomicOr(&a.ctrl->error, ERR_KEYGROUP);
             sb = -1;
@@ -70,6 +93,9 @@ __global__ __launch_bounds__(FD_TILE) void k_fd_part(PartArgs a) {
         a.s_sb[c0 + t] = -1;
     }
 }
+
+__global__ __launch_bounds__(FD_TILE) void k_fd_part(PartArgs a) { fd_part_body<false>(a, PartSegArgs{}); }
+__global__ __launch_bounds__(FD_TILE) void k_fd_part_seg(PartArgs a, PartSegArgs g) { fd_part_body<true>(a, g); }
 
 // superbucket blockIdx.x: hist[sb][0 .. n_chunks) -> its exclusive scan; seg[sb] = the total
 __global__ __launch_bounds__(256) void k_fd_scan(int32_t* hist, int32_t* seg, int32_t n_chunks) {
@@ -156,8 +182,8 @@ void fd_free(FoldedPart* part) {
     hipFree(part->perm);
 }
 
-int fd_partition(const FoldedPart& part, const KeySpace& ks, Ctrl* ctrl, hipStream_t stream, int64_t n, const int64_t* d_key,
-                 const int32_t* d_khash) {
+static int fd_partition_launch(const FoldedPart& part, const KeySpace& ks, Ctrl* ctrl, hipStream_t stream, int64_t n,
+                               const int64_t* d_key, const int32_t* d_khash, const PartSegArgs* sg) {
     const int n_sb = ks.n_sb;
     const int32_t nch = (int32_t)((n + FD_TILE - 1) / FD_TILE);
     FD_TRY(hipMemsetAsync(part.hist, 0, (size_t)n_sb * nch * 4, stream));
@@ -172,12 +198,24 @@ int fd_partition(const FoldedPart& part, const KeySpace& ks, Ctrl* ctrl, hipStre
     pa.s_sb = part.s_sb;
     pa.s_row = part.s_row;
     pa.s_rank = part.s_rank;
-    hipLaunchKernelGGL(k_fd_part, dim3(nch), dim3(FD_TILE), 0, stream, pa);
+    if (sg) hipLaunchKernelGGL(k_fd_part_seg, dim3(nch), dim3(FD_TILE), 0, stream, pa, *sg);
+    else hipLaunchKernelGGL(k_fd_part, dim3(nch), dim3(FD_TILE), 0, stream, pa);
     hipLaunchKernelGGL(k_fd_scan, dim3(n_sb), dim3(256), 0, stream, part.hist, part.seg, nch);
     hipLaunchKernelGGL(k_fd_seg, dim3(1), dim3(FD_TILE), 0, stream, part.seg, (int32_t)n_sb);
     hipLaunchKernelGGL(k_fd_scatter, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream, n, nch, part.hist, part.seg,
                        part.s_sb, part.s_row, part.s_rank, part.perm);
     return FW_OK;
+}
+
+int fd_partition(const FoldedPart& part, const KeySpace& ks, Ctrl* ctrl, hipStream_t stream, int64_t n, const int64_t* d_key,
+                 const int32_t* d_khash) {
+    return fd_partition_launch(part, ks, ctrl, stream, n, d_key, d_khash, nullptr);
+}
+
+int fd_partition_segments(const FoldedPart& part, const KeySpace& ks, Ctrl* ctrl, hipStream_t stream, int64_t n, const int64_t* d_key,
+                          int32_t stride, const int32_t* d_khash, const int64_t* d_seg_counts, int64_t seg_len, int64_t row0) {
+    const PartSegArgs sg{d_seg_counts, seg_len, row0, stride};
+    return fd_partition_launch(part, ks, ctrl, stream, n, d_key, d_khash, &sg);
 }
 
 int fd_sb_range(const KeySpace& ks, int32_t key_group, int* sb0, int* sb1) {

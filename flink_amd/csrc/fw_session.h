@@ -165,6 +165,10 @@ constexpr int64_t SW_SIDE_WORDS = 4;               // late side-output row: key,
 struct SessionOp {
     bool on = false;
     bool dyn = false;         // FW_WIN_SESSION_DYNAMIC: value column 1 is the row's gap, d.gap the largest allowed
+    // Ctrl::cur in device memory is the watermark of record (a handle of parallelism > 1 that was
+    // advanced from the device, sw_advance_device): every fold and advance reads it there, and the
+    // host's mirror (fw_handle::host_cur) is only a lower bound until a reader synchronises
+    bool wm_dev = false;
     SessionDesc d{};
     AggDesc ad{};             // SQL: the aggregates over the words (sql_agg_result)
     KeySpace ks{};
@@ -206,8 +210,23 @@ void sw_free(SessionOp* op);
 // (DataStream: d_vals[val_col] is the one value column, d_nulls is not read)
 int sw_push(SessionOp* op, int64_t watermark, int64_t n, const int64_t* d_key, const int64_t* d_ts, const int32_t* d_khash,
             const void* const* d_vals, const uint8_t* const* d_nulls);
+// (op->wm_dev: under Ctrl::cur as it stands at that point of the stream; `watermark` is not read)
+// The same for a padded exchange receive buffer behind the N > 1 keyBy exchange: n_segs segments of
+// seg_len rows, segment s holding min(d_seg_counts[s], seg_len) live rows; row i's key, ts and value
+// words at col[i * stride] (1: SoA columns; row_words: packed rows, the columns at rows + 0, 1, 2 + c),
+// its hash and null flags at [i].  Padding rows are never read by the fold.  Folds under Ctrl::cur,
+// which every advance of either kind keeps current.  A late side-output record's row is the row's
+// position in the buffer.
+int sw_push_segments(SessionOp* op, int32_t n_segs, int64_t seg_len, const int64_t* d_seg_counts, const int64_t* d_key,
+                     const int64_t* d_ts, int32_t stride, const int32_t* d_khash, const void* const* d_vals,
+                     const uint8_t* const* d_nulls);
 // fires every session with end - 1 <= watermark and compacts the rest (stream-ordered, asynchronous)
 int sw_advance(SessionOp* op, int64_t watermark);
+// Ctrl::cur = W' = max(Ctrl::cur, *d_watermark or, with d_watermark NULL, watermark), then every session
+// with end - 1 <= W' fires: two stream-ordered launches, no host wait.  Sets op->wm_dev.
+int sw_advance_device(SessionOp* op, const int64_t* d_watermark, int64_t watermark);
+// *watermark = Ctrl::cur behind everything queued on the handle's stream (synchronises)
+int sw_read_watermark(SessionOp* op, int64_t* watermark);
 int sw_snapshot(SessionOp* op, int64_t watermark, int32_t key_group, void* buf, int64_t capacity, int64_t* size);
 int sw_restore(SessionOp* op, bool key_group, const void* buf, int64_t size, int64_t* watermark);
 

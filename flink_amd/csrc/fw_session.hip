@@ -11,6 +11,11 @@
 // or 8; 3 + NW words per session): the DataStream handle is the NW = 1 instance, a SQL session handle
 // takes the instance of its plan's word count and a merge class per word.  k_sw_fold<1, true> is the
 // dynamic-gap form (FW_WIN_SESSION_DYNAMIC): a gap per row, read from value column 1.
+// Behind the N > 1 keyBy exchange (a handle of parallelism > 1) both kernels have a device form, one
+// more template argument: k_sw_fold<NW, DYN, true> reads strided rows of a padded receive buffer, whose
+// live rows fd_partition_segments selected, and the watermark from Ctrl::cur; k_sw_advance<NW, true>
+// reads Ctrl::cur behind the one-thread k_sw_raise.  The instances above are unchanged and are what a
+// direct push of a host-watermark handle launches.
 // No workgroup waits on another: the only cross-workgroup traffic is counters (atomic adds).
 #include <hip/hip_runtime.h>
 
@@ -96,6 +101,7 @@ struct SwFoldArgs {
     int64_t* side;
     int64_t side_cap;
     int64_t ord_base;  // push_seq << 32 | row offset of this launch within its call
+    int32_t stride;    // the device form (DEV): key, ts and value words of row r at col[r * stride]
 };
 
 // first index in [lo, hi) of the sorted session list whose (key, start) is not below (k, s)
@@ -113,7 +119,8 @@ __device__ __forceinline__ int sw_lower(const uint64_t* st, int lo, int hi, uint
 
 // a row's NW accumulator words: the identity where the word's gate column is NULL, 1 for a count
 // word, 0 for a padding word, else the value of the word's column
-template <int NW>
+// (DEV: value columns are strided, null-flag columns never)
+template <int NW, bool DEV>
 __device__ __forceinline__ void sw_row_words(const SwFoldArgs& a, uint32_t row, uint64_t* out) {
 #pragma unroll
     for (int w = 0; w < NW; w++) {
@@ -123,7 +130,7 @@ __device__ __forceinline__ void sw_row_words(const SwFoldArgs& a, uint32_t row, 
         else if (col == SW_COL_ONE) v = 1ull;
         else if (col == SW_COL_PAD) v = 0ull;
         else {
-            v = a.vals[col][row];
+            v = a.vals[col][DEV ? (size_t)row * (size_t)a.stride : (size_t)row];
             if (NW == 1 && a.d.dbl_cmp) v = (uint64_t)dkey(v);
         }
         out[w] = v;
@@ -132,7 +139,13 @@ __device__ __forceinline__ void sw_row_words(const SwFoldArgs& a, uint32_t row, 
 
 // DYN (NW = 1 only): the dynamic-gap form.  A row's gap is the word of value column 1 and a.d.gap the
 // largest a row may carry; everything that reads `ts + gap` in the static form reads the row's own end.
-template <int NW, bool DYN = false>
+// DEV: the device form, behind the N > 1 keyBy exchange (sw_push_segments) and for every push of a
+// handle whose watermark of record is Ctrl::cur (sw_push with no host watermark).  The rows are read
+// as col[row * a.stride] -- stride 1 over separate column pointers is a SoA buffer, stride row_words
+// over rows + 0, 1, 2 + c a packed one -- and the watermark from a.ctrl->cur, a word no workgroup of
+// a fold launch writes.  Everything else is the one body.  The instances without DEV are the ones a
+// direct push of a host-watermark handle launches; they read neither a.stride nor Ctrl::cur.
+template <int NW, bool DYN = false, bool DEV = false>
 __global__ __launch_bounds__(SW_TILE) void k_sw_fold(SwFoldArgs a) {
     static_assert(!DYN || NW == 1, "the dynamic-gap fold is a DataStream instance");
     constexpr int SWS = sw_stride(NW);   // words per session
@@ -153,7 +166,8 @@ __global__ __launch_bounds__(SW_TILE) void k_sw_fold(SwFoldArgs a) {
     __shared__ uint32_t n_drop;
 
     const int t = threadIdx.x;
-    const int64_t gap = a.d.gap, W = a.watermark;
+    const int64_t gap = a.d.gap, W = DEV ? a.ctrl->cur : a.watermark;
+#define SW_AT(row) (DEV ? (size_t)(row) * (size_t)a.stride : (size_t)(row))
     // the words' merge classes, two bits each, and their identities, derived where they are used:
     // one scalar register instead of three per word across the scan loops
     const uint32_t opsp = a.opsp;
@@ -173,13 +187,13 @@ __global__ __launch_bounds__(SW_TILE) void k_sw_fold(SwFoldArgs a) {
         if (t == 0) n_drop = 0;
         bool badgap = false;  // (dynamic) a row with a gap out of range is padding: it adds nothing
         if (DYN && t < nrows) {
-            const int64_t g = (int64_t)a.vals[1][a.perm[base + t]];
+            const int64_t g = (int64_t)a.vals[1][SW_AT(a.perm[base + t])];
             badgap = g < 1 || g > gap;
         }
         if (t < nrows && !badgap) {
             const uint32_t row = a.perm[base + t];
-            sk[t] = (uint64_t)a.key[row];
-            sts[t] = a.ts[row];
+            sk[t] = (uint64_t)a.key[SW_AT(row)];
+            sts[t] = a.ts[SW_AT(row)];
             sp[t] = (uint32_t)t;
         } else {
             sk[t] = ~0ull;
@@ -200,7 +214,7 @@ __global__ __launch_bounds__(SW_TILE) void k_sw_fold(SwFoldArgs a) {
         const uint64_t mykey = sk[t];
         const int64_t myts = sts[t];
         // the end of the row's own window (dynamic: its gap through perm, as its words below)
-        const int64_t mygap = DYN && valid ? (int64_t)a.vals[1][a.perm[base + sp[t]]] : 0;
+        const int64_t mygap = DYN && valid ? (int64_t)a.vals[1][SW_AT(a.perm[base + sp[t]])] : 0;
 #define SW_END (DYN ? myts + mygap : myts + gap)
         const bool head = valid && (t == 0 || sk[t - 1] != mykey);
         hx[t] = head ? t : 0;
@@ -255,7 +269,7 @@ __global__ __launch_bounds__(SW_TILE) void k_sw_fold(SwFoldArgs a) {
             uint64_t myword[NW];
 #pragma unroll
             for (int w = 0; w < NW; w++) myword[w] = SW_IDN(w);
-            if (valid) sw_row_words<NW>(a, a.perm[base + sp[t]], myword);
+            if (valid) sw_row_words<NW, DEV>(a, a.perm[base + sp[t]], myword);
             if (t < n2) {
 #pragma unroll
                 for (int w = 0; w < NW; w++) sa[w][t] = myword[w];
@@ -346,7 +360,7 @@ __global__ __launch_bounds__(SW_TILE) void k_sw_fold(SwFoldArgs a) {
                 if (rc == 0) {  // dropped: counted (SQL has no side output: late_side is 0)
                     atomicAdd(&n_drop, 1u);
                     if (NW == 1 && a.late_side) {
-                        const uint64_t raw = a.d.is_count ? 1ull : a.vals[a.d.col[0]][row];
+                        const uint64_t raw = a.d.is_count ? 1ull : a.vals[a.d.col[0]][SW_AT(row)];
                         const unsigned long long o = atomicAdd((unsigned long long*)&a.ctrl->n_side, 1ull);
                         if (o < (unsigned long long)a.side_cap) {
                             int64_t* sd = a.side + (size_t)o * SW_SIDE_WORDS;
@@ -516,6 +530,7 @@ __global__ __launch_bounds__(SW_TILE) void k_sw_fold(SwFoldArgs a) {
 #undef SW_OP
 #undef SW_IDN
 #undef SW_END
+#undef SW_AT
 }
 
 // ---- the watermark -----------------------------------------------------------------------------
@@ -536,19 +551,22 @@ struct SwAdvArgs {
     int64_t out_cap;
 };
 
-template <int NW>
+// DEV: the watermark is Ctrl::cur, which k_sw_raise set in a launch of its own in front (no
+// workgroup of this launch writes it)
+template <int NW, bool DEV = false>
 __global__ __launch_bounds__(SW_TILE) void k_sw_advance(SwAdvArgs a) {
     constexpr int SWS = sw_stride(NW);
+    const int64_t W = DEV ? a.ctrl->cur : a.watermark;
     __shared__ int32_t buf[SW_TILE];
     __shared__ int64_t mn[SW_TILE];
     __shared__ unsigned long long out_base;
     const int t = threadIdx.x;
     const int ns = a.n_s[blockIdx.x];
-    if (ns == 0 || !session_due(a.min_end[blockIdx.x], a.watermark)) return;  // nothing is due (uniform)
+    if (ns == 0 || !session_due(a.min_end[blockIdx.x], W)) return;  // nothing is due (uniform)
     uint64_t* st = a.state + (size_t)blockIdx.x * a.cap_s * SWS;
     // the due sessions, counted first: one device atomic per workgroup claims their output rows
     int32_t mine = 0;
-    for (int i = t; i < ns; i += SW_TILE) mine += session_due((int64_t)st[(size_t)i * SWS + 2], a.watermark) ? 1 : 0;
+    for (int i = t; i < ns; i += SW_TILE) mine += session_due((int64_t)st[(size_t)i * SWS + 2], W) ? 1 : 0;
     int32_t n_due;
     fd_block_scan<SW_TILE>(mine, buf, &n_due);
     if (t == 0) {
@@ -578,7 +596,7 @@ __global__ __launch_bounds__(SW_TILE) void k_sw_advance(SwAdvArgs a) {
 #pragma unroll
             for (int w = 0; w < NW; w++) acc[w] = st[(size_t)i * SWS + 3 + w];
         }
-        const bool due = in && session_due(e, a.watermark);
+        const bool due = in && session_due(e, W);
         int32_t n_f;
         const int32_t fi = fd_block_scan<SW_TILE>(due ? 1 : 0, buf, &n_f);  // (barriers: the chunk is in registers)
         const int32_t n_in = ns - c0 < SW_TILE ? ns - c0 : SW_TILE;
@@ -628,6 +646,15 @@ __global__ __launch_bounds__(SW_TILE) void k_sw_advance(SwAdvArgs a) {
     if (t == 0) {
         a.n_s[blockIdx.x] = kept;
         a.min_end[blockIdx.x] = mn[0];
+    }
+}
+
+// Ctrl::cur = max(Ctrl::cur, the proposed watermark): *d_w if given, else w.  One thread, a launch of
+// its own in front of k_sw_advance<NW, true>, so no launch both reads and writes the word.
+__global__ void k_sw_raise(Ctrl* ctrl, const int64_t* d_w, int64_t w) {
+    if (blockIdx.x == 0 && threadIdx.x == 0) {
+        const int64_t v = d_w ? *d_w : w;
+        if (v > ctrl->cur) ctrl->cur = v;
     }
 }
 
@@ -852,17 +879,25 @@ void sw_free(SessionOp* op) {
     hipFree(op->side);
 }
 
-// the kernels' instance of a handle: NW = sw_round_nw(words of the plan)
-#define SW_LAUNCH_NW(kernel, nw_t, ...)                                            \
+// the kernels' instance of a handle: NW = sw_round_nw(words of the plan); `form` the template
+// arguments behind NW (SW_HOST: none, the host-watermark instances)
+#define SW_HOST(nw) <nw>
+#define SW_DEV_FOLD(nw) <nw, false, true>
+#define SW_DEV_ADV(nw) <nw, true>
+#define SW_LAUNCH_NW(kernel, form, nw_t, ...)                                      \
     switch (nw_t) {                                                                \
-        case 1: hipLaunchKernelGGL(kernel<1>, __VA_ARGS__); break;                 \
-        case 2: hipLaunchKernelGGL(kernel<2>, __VA_ARGS__); break;                 \
-        case 4: hipLaunchKernelGGL(kernel<4>, __VA_ARGS__); break;                 \
-        default: hipLaunchKernelGGL(kernel<8>, __VA_ARGS__); break;                \
+        case 1: hipLaunchKernelGGL((kernel form(1)), __VA_ARGS__); break;          \
+        case 2: hipLaunchKernelGGL((kernel form(2)), __VA_ARGS__); break;          \
+        case 4: hipLaunchKernelGGL((kernel form(4)), __VA_ARGS__); break;          \
+        default: hipLaunchKernelGGL((kernel form(8)), __VA_ARGS__); break;         \
     }
 
-int sw_push(SessionOp* op, int64_t watermark, int64_t n, const int64_t* d_key, const int64_t* d_ts, const int32_t* d_khash,
-            const void* const* d_vals, const uint8_t* const* d_nulls) {
+// the folds of one call: n rows at d_key[i * stride] ..., split into launches of part.cap_rows rows by
+// position.  d_seg_counts: the rows are a padded buffer of segments of seg_len rows (the device form);
+// dev: the device form of the fold (strided reads, the watermark from Ctrl::cur, `watermark` unread)
+static int sw_fold_call(SessionOp* op, bool dev, int64_t watermark, int64_t n, const int64_t* d_key, const int64_t* d_ts,
+                        int32_t stride, const int32_t* d_khash, const void* const* d_vals, const uint8_t* const* d_nulls,
+                        const int64_t* d_seg_counts, int64_t seg_len) {
     if (n >= (1ll << 32) || op->push_seq >= (1ll << 30))
         return set_error(FW_E_INVALID, "arrival ordinals need < 2^32 rows per call and < 2^30 calls");
     hipStream_t s = op->stream;
@@ -870,17 +905,19 @@ int sw_push(SessionOp* op, int64_t watermark, int64_t n, const int64_t* d_key, c
     const int64_t cap_rows = op->part.cap_rows;
     for (int64_t o = 0; o < n; o += cap_rows) {
         const int64_t m = std::min(cap_rows, n - o);
-        const int rc = fd_partition(op->part, op->ks, op->ctrl, s, m, d_key + o, d_khash ? d_khash + o : nullptr);
+        const int rc = d_seg_counts ? fd_partition_segments(op->part, op->ks, op->ctrl, s, m, d_key + o * stride, stride,
+                                                            d_khash ? d_khash + o : nullptr, d_seg_counts, seg_len, o)
+                                    : fd_partition(op->part, op->ks, op->ctrl, s, m, d_key + o, d_khash ? d_khash + o : nullptr);
         if (rc) return rc;
         SwFoldArgs fa{};
-        fa.key = d_key + o;
-        fa.ts = d_ts + o;
+        fa.key = d_key + o * stride;
+        fa.ts = d_ts + o * stride;
         for (int w = 0; w < op->d.nw; w++) {  // the columns the words name
             const int32_t col = op->d.col[w], gate = op->d.gate[w];
-            if (col >= 0) fa.vals[col] = (const uint64_t*)d_vals[col] + o;
+            if (col >= 0) fa.vals[col] = (const uint64_t*)d_vals[col] + o * stride;
             if (gate >= 0) fa.nulls[gate] = d_nulls[gate] + o;
         }
-        if (op->dyn) fa.vals[1] = (const uint64_t*)d_vals[1] + o;  // the gap column
+        if (op->dyn) fa.vals[1] = (const uint64_t*)d_vals[1] + o * stride;  // the gap column
         fa.perm = op->part.perm;
         fa.seg = op->part.seg;
         fa.d = op->d;
@@ -896,10 +933,17 @@ int sw_push(SessionOp* op, int64_t watermark, int64_t n, const int64_t* d_key, c
         fa.side = op->side;
         fa.side_cap = op->side_cap;
         fa.ord_base = (op->push_seq << 32) + o;
-        if (op->dyn) {
+        fa.stride = stride;
+        if (dev) {
+            if (op->dyn) {
+                hipLaunchKernelGGL((k_sw_fold<1, true, true>), dim3(n_sb), dim3(SW_TILE), 0, s, fa);
+            } else {
+                SW_LAUNCH_NW(k_sw_fold, SW_DEV_FOLD, op->nw_t, dim3(n_sb), dim3(SW_TILE), 0, s, fa);
+            }
+        } else if (op->dyn) {
             hipLaunchKernelGGL((k_sw_fold<1, true>), dim3(n_sb), dim3(SW_TILE), 0, s, fa);
         } else {
-            SW_LAUNCH_NW(k_sw_fold, op->nw_t, dim3(n_sb), dim3(SW_TILE), 0, s, fa);
+            SW_LAUNCH_NW(k_sw_fold, SW_HOST, op->nw_t, dim3(n_sb), dim3(SW_TILE), 0, s, fa);
         }
         FD_TRY(hipGetLastError());
     }
@@ -907,8 +951,18 @@ int sw_push(SessionOp* op, int64_t watermark, int64_t n, const int64_t* d_key, c
     return FW_OK;
 }
 
-// (a dynamic-gap handle runs the NW = 1 instance too: sessions carry their ends, no gap is read)
-int sw_advance(SessionOp* op, int64_t watermark) {
+int sw_push(SessionOp* op, int64_t watermark, int64_t n, const int64_t* d_key, const int64_t* d_ts, const int32_t* d_khash,
+            const void* const* d_vals, const uint8_t* const* d_nulls) {
+    return sw_fold_call(op, op->wm_dev, watermark, n, d_key, d_ts, 1, d_khash, d_vals, d_nulls, nullptr, 0);
+}
+
+int sw_push_segments(SessionOp* op, int32_t n_segs, int64_t seg_len, const int64_t* d_seg_counts, const int64_t* d_key,
+                     const int64_t* d_ts, int32_t stride, const int32_t* d_khash, const void* const* d_vals,
+                     const uint8_t* const* d_nulls) {
+    return sw_fold_call(op, true, 0, (int64_t)n_segs * seg_len, d_key, d_ts, stride, d_khash, d_vals, d_nulls, d_seg_counts, seg_len);
+}
+
+static SwAdvArgs sw_adv_args(SessionOp* op, int64_t watermark) {
     SwAdvArgs a{};
     a.d = op->d;
     a.watermark = watermark;
@@ -924,8 +978,29 @@ int sw_advance(SessionOp* op, int64_t watermark) {
     for (int g = 0; g < op->n_out; g++) a.out_val[g] = op->out_val[g];
     a.out_null = op->out_null;
     a.out_cap = op->out_cap;
-    SW_LAUNCH_NW(k_sw_advance, op->nw_t, dim3(op->ks.n_sb), dim3(SW_TILE), 0, op->stream, a);
+    return a;
+}
+
+// (a dynamic-gap handle runs the NW = 1 instance too: sessions carry their ends, no gap is read)
+int sw_advance(SessionOp* op, int64_t watermark) {
+    const SwAdvArgs a = sw_adv_args(op, watermark);
+    SW_LAUNCH_NW(k_sw_advance, SW_HOST, op->nw_t, dim3(op->ks.n_sb), dim3(SW_TILE), 0, op->stream, a);
     FD_TRY(hipGetLastError());
+    return FW_OK;
+}
+
+int sw_advance_device(SessionOp* op, const int64_t* d_watermark, int64_t watermark) {
+    op->wm_dev = true;
+    hipLaunchKernelGGL(k_sw_raise, dim3(1), dim3(1), 0, op->stream, op->ctrl, d_watermark, watermark);
+    const SwAdvArgs a = sw_adv_args(op, 0);
+    SW_LAUNCH_NW(k_sw_advance, SW_DEV_ADV, op->nw_t, dim3(op->ks.n_sb), dim3(SW_TILE), 0, op->stream, a);
+    FD_TRY(hipGetLastError());
+    return FW_OK;
+}
+
+int sw_read_watermark(SessionOp* op, int64_t* watermark) {
+    FD_TRY(hipMemcpyAsync(watermark, &op->ctrl->cur, sizeof(int64_t), hipMemcpyDeviceToHost, op->stream));
+    FD_TRY(hipStreamSynchronize(op->stream));
     return FW_OK;
 }
 

@@ -10,3 +10,4 @@ from .session_window_operator import SessionWindowOperator  # noqa: F401
 from .session_window_operator import is_gpu_eligible as is_session_window_gpu_eligible  # noqa: F401
 from .dynamic_session_window_operator import DynamicSessionWindowOperator  # noqa: F401
 from .dynamic_session_window_operator import is_gpu_eligible as is_dynamic_session_window_gpu_eligible  # noqa: F401
+from .session_exchange import SessionExchangeStep  # noqa: F401

@@ -97,12 +97,36 @@ class SessionWindowOperator:
             raise ValueError("a STRING-keyed operator interns its keys on the host (process_batch)")
         self.handle.push_device(keys, timestamps, [values], key_hashes)
 
+    # ---- behind the N > 1 keyBy exchange (parallelism > 1; a subtask of parallelism 1 has no exchange
+    # in front of it and its handle refuses these)
+    def process_segments_device(self, seg_counts, keys, timestamps, values, key_hashes=None):
+        """A padded exchange receive buffer of SoA columns (KeyByExchange.exchange_padded): segment s
+        holds its first min(seg_counts[s], segment length) rows; arrival order is buffer position
+        order.  A late record's ``row`` is its position in the buffer."""
+        if self.key_type == "STRING":
+            raise ValueError("a STRING-keyed operator interns its keys on the host (process_batch)")
+        self.handle.push_device_segments(seg_counts, keys, timestamps, [values], key_hashes)
+
+    def process_packed_segments_device(self, seg_counts, rows, row_words):
+        """A packed padded exchange receive buffer (KeyByExchange.exchange_packed_async): rows of
+        (key, ts, value) words."""
+        self.handle.push_device_packed_segments(seg_counts, rows, row_words)
+
+    def process_watermark_device(self, wm_tensor):
+        """process_watermark with the watermark in device memory (the exchange's device valve): the
+        handle takes max(its watermark, wm_tensor[0]) with no host wait; collecting the rows waits."""
+        self.handle.advance_device(wm_tensor)
+        return self._fired()
+
     def _key_objects(self, ids):
         return self._keys.objects(ids) if self.key_type == "STRING" else ids
 
     def process_watermark(self, watermark):
         """The sessions the watermark fires, sorted by (timestamp, key, window_start)."""
         self.handle.advance(watermark)
+        return self._fired()
+
+    def _fired(self):
         r = self.handle.results(reset=True)
         ts = r["window_end"] - 1
         order = np.lexsort((r["window_start"], r["key"], ts))

@@ -116,6 +116,30 @@ class SessionWindowAggOperator:
             return None
         return self.handle.results(reset=True)
 
+    # ---- behind the N > 1 keyBy exchange (parallelism > 1; a subtask of parallelism 1 has no exchange
+    # in front of it and its handle refuses these)
+    def process_segments_device(self, seg_counts, keys, rowtimes, values=(), key_hashes=None, nulls=None):
+        """A padded exchange receive buffer of SoA columns (KeyByExchange.exchange_padded): segment s
+        holds its first min(seg_counts[s], segment length) rows; arrival order is buffer position
+        order."""
+        self.handle.push_device_segments(seg_counts, keys, rowtimes, values, key_hashes, nulls=nulls)
+
+    def process_packed_segments_device(self, seg_counts, rows, row_words):
+        """A packed padded exchange receive buffer (KeyByExchange.exchange_packed_async): rows of
+        (key, rowtime, value words); NOT NULL columns and device-hashable keys only."""
+        self.handle.push_device_packed_segments(seg_counts, rows, row_words)
+
+    def process_watermark_device(self, wm_tensor, collect=True):
+        """processWatermark with the watermark in device memory (the exchange's device valve): the
+        handle takes max(its watermark, wm_tensor[0]) with no host wait.  current_watermark follows
+        at the next collect or state call."""
+        self.handle.advance_device(wm_tensor)
+        if not collect:
+            return None
+        res = self.handle.results(reset=True)
+        self.current_watermark = max(self.current_watermark, self.handle.stats()["current_watermark"])
+        return res
+
     def prepare_snapshot_pre_barrier(self, checkpoint_id=0):
         self.handle.flush()  # (nothing is buffered: every push is folded when it is pushed)
 

@@ -124,6 +124,10 @@ typedef enum {
        calls, the segment and key-row pushes, fw_advance_device, fw_first_element_events, the
        heap-format and fw_ds_* key-group calls and the profiling calls return FW_E_INVALID on a
        session handle.  A full session list raises FW_ERRF_STATE and drops the tile's rows.
+       Behind the N > 1 keyBy exchange: a session handle whose configuration has parallelism > 1 --
+       the only kind with an exchange in front of it -- accepts fw_push_device_segments,
+       fw_push_device_packed_segments and fw_advance_device (see there; previously refused calls,
+       so additive).  One of parallelism 1 refuses them as above, with the same code and message.
 
        v11 (additive), with api == FW_API_SQL: the SESSION window TVF aggregate,
        SESSION(TABLE t PARTITION BY k, DESCRIPTOR(rowtime), gap) grouped by (k, window_start,
@@ -402,7 +406,16 @@ int fw_push_device_key_rows(fw_handle* h, int64_t n, const int64_t* d_key_row_of
 /* The receive buffer of a padded all-to-all (the keyBy exchange without a host round trip for
    the row counts): n_segs segments of seg_len rows, one per sending subtask; segment s holds
    d_seg_counts[s] valid rows (device int64, e.g. the counts all-to-all's result), the rest is
-   padding and is never read.  Otherwise as fw_push_device. */
+   padding and is never read.  Otherwise as fw_push_device.
+   A session handle (FW_WIN_SESSION, FW_WIN_SESSION_DYNAMIC, either API) takes the call iff its
+   configuration has parallelism > 1; one of parallelism 1 and every count handle return
+   FW_E_INVALID.  The rows are folded when they are pushed, in buffer position order, under the
+   handle's watermark at that point of the stream; a count above seg_len is clamped (the overflow
+   went to the sender's spill); a padding row is never read, whatever it holds, so it raises
+   neither FW_ERRF_KEYGROUP nor FW_ERRF_GAP, while a live row of a foreign key group is dropped and
+   raises FW_ERRF_KEYGROUP.  The row of a late side-output record (fw_late_records) is the row's
+   position in the pushed buffer, segment * seg_len + index; push_seq counts the call like any
+   other push. */
 int fw_push_device_segments(fw_handle* h, int32_t n_segs, int64_t seg_len, const int64_t* d_seg_counts,
                             const int64_t* d_key, const int64_t* d_ts, const int32_t* d_key_hash,
                             const void* const* d_values, const uint8_t* const* d_nulls);
@@ -411,7 +424,10 @@ int fw_push_device_segments(fw_handle* h, int32_t n_segs, int64_t seg_len, const
    seg_len rows of row_words = 2 + n_value_cols int64 words each (key, ts, value columns in
    config order); segment s holds d_seg_counts[s] valid rows.  One buffer, one all-to-all per
    batch instead of one per column.  Not for FW_KEYHASH_PRECOMPUTED or NULL-able configurations
-   (their extra columns travel with fw_push_device_segments). */
+   (their extra columns travel with fw_push_device_segments).
+   Session handles: as fw_push_device_segments -- parallelism > 1 only, folded in buffer position
+   order, late side-output rows numbered by buffer position.  A dynamic-gap handle's rows are
+   (key, ts, field, gap). */
 int fw_push_device_packed_segments(fw_handle* h, int32_t n_segs, int64_t seg_len, const int64_t* d_seg_counts,
                                    const int64_t* d_rows, int32_t row_words);
 
@@ -459,7 +475,17 @@ int fw_advance(fw_handle* h, int64_t watermark);
    all-reduce on the device, and a step enqueues ingest and advance without waiting for its own GPU
    work.  The caller orders the handle's stream after the producer of d_watermark.  The host cannot
    skip watermarks that cross no slice end here (it does not know the value): the launch finds out on
-   the device. */
+   the device.
+   A session handle takes the call iff its configuration has parallelism > 1 (one of parallelism 1
+   returns FW_E_INVALID: its folds take the watermark from the host).  From the first call on the
+   handle's watermark of record lives in device memory: the call sets it to
+   W' = max(current, d_watermark[0]) and fires every session with end - 1 <= W', stream-ordered and
+   without a host wait; every later push through any entry point (fw_commit included) folds under
+   the device value as it stands at that point of the stream; fw_advance(h, w) launches too and the
+   device takes the maximum, so a lower w changes nothing; fw_get_stats().current_watermark and
+   the snapshot blobs report the device value after their synchronisation; fw_restore and
+   fw_initialize_watermark set it.  A count handle records the watermark on the device and fires
+   nothing, as ever. */
 int fw_advance_device(fw_handle* h, const int64_t* d_watermark);
 int fw_flush(fw_handle* h);
 /* copy_to_host != 0: host arrays owned by the handle, valid until the next call;
