@@ -205,16 +205,12 @@ __global__ __launch_bounds__(MG_BLOCK, 4) void k_merge_hopb(MergeArgs a) {
     Ctrl* c = a.ctrl;
     const WinDesc& win = a.win;
     const int64_t W = merge_watermark(a);
-    const int64_t cur = __hip_atomic_load(&c->cur, __ATOMIC_RELAXED, DEV_SCOPE);
-    const int64_t pend = __hip_atomic_load(&c->pending_pushes, __ATOMIC_RELAXED, DEV_SCOPE);
-    const int64_t ntp = __hip_atomic_load(&c->ntp, __ATOMIC_RELAXED, DEV_SCOPE);
-    const int64_t minp = __hip_atomic_load(&c->min_pending, __ATOMIC_RELAXED, DEV_SCOPE);
-    const bool adv = !a.force_flush && W > cur;
-    const bool do_flush = pend > 0 && (a.force_flush || (adv && (W >= ntp && win_fired(win, minp, W))));
-    const bool do_fire = adv;
-    const int64_t w_old = cur;
-    const int64_t w_new = adv ? W : cur;  // the watermark after this launch (slice expiry)
-    // late-record timer requests (n_treq) need no work here: their windows fire by holding data
+    // control decisions, in the form of SQL HOP (merge_decide: no always_flush; late-record timer
+    // requests need no work here: their windows fire by holding data)
+    const MergeDecision d = merge_decide<KIND_HOPB>(a, W);
+    const int64_t pend = d.pend, w_old = d.cur;
+    const bool do_flush = d.do_flush, do_fire = d.do_fire;
+    const int64_t w_new = d.adv ? W : d.cur;  // the watermark after this launch (slice expiry)
 
     const bool xq = a.n_sb % 8 == 0 && gridDim.x % 8 == 0;
     const int nq = xq ? a.n_sb / 8 : a.n_sb;
@@ -474,7 +470,7 @@ __global__ __launch_bounds__(MG_BLOCK, 4) void k_merge_hopb(MergeArgs a) {
         }
         __syncthreads();
     }
-    merge_ticket(a, W);
+    merge_ticket<KIND_HOPB>(a, W);
 }
 
 template <int NWP, int GF>

@@ -741,20 +741,46 @@ __device__ __forceinline__ int64_t merge_watermark(const MergeArgs& a) {
     return a.wm_dev ? __hip_atomic_load(a.wm_dev, __ATOMIC_RELAXED, DEV_SCOPE) : a.wm;
 }
 
-// the last workgroup of a k_merge_fire launch applies the launch's control decisions (every
-// workgroup read the old values at its start): advanceProgress bookkeeping of the processor
-// (AbstractSliceSyncStateWindowAggProcessor.java:139-153), the buffer reset after a flush, the
-// consumed timer requests, and the overflow-counter switch of a result reset.
+// The control decisions of a launch, read from the control block: every workgroup of the merge
+// kernels takes them for itself at its start, and the launch's last workgroup applies them to the
+// control block (merge_finalize, which still reads the old values: nothing writes them before it).
+// KIND: the kernel's window kind.  KIND_HOPB (k_merge_hopb) is reached by SQL HOP alone
+// (WinDesc::hopb), so its form leaves out what only DataStream handles or timers have: always_flush
+// is 0 there, and late-record timer requests need no work (their windows fire by holding data).
+struct MergeDecision {
+    int64_t cur, pend, ntreq, nlf, ntp, minp;
+    bool adv, do_flush, do_fire;
+};
+template <int KIND>
+__device__ __forceinline__ MergeDecision merge_decide(const MergeArgs& a, int64_t W) {
+    Ctrl* c = a.ctrl;
+    MergeDecision d;
+    d.cur = __hip_atomic_load(&c->cur, __ATOMIC_RELAXED, DEV_SCOPE);
+    d.pend = __hip_atomic_load(&c->pending_pushes, __ATOMIC_RELAXED, DEV_SCOPE);
+    // the ingest counts on past the cap (ERR_TREQ)
+    d.ntreq = KIND == KIND_HOPB ? 0 : min(__hip_atomic_load(&c->n_treq, __ATOMIC_RELAXED, DEV_SCOPE), a.treq_cap);
+    d.nlf = KIND == KIND_DSWIN ? min(__hip_atomic_load(&c->n_lfire, __ATOMIC_RELAXED, DEV_SCOPE), a.lfire_cap) : 0;
+    d.ntp = __hip_atomic_load(&c->ntp, __ATOMIC_RELAXED, DEV_SCOPE);
+    d.minp = __hip_atomic_load(&c->min_pending, __ATOMIC_RELAXED, DEV_SCOPE);
+    d.adv = !a.force_flush && W > d.cur;
+    d.do_flush = d.pend > 0 && (a.force_flush || (d.adv && ((KIND != KIND_HOPB && a.always_flush) ||
+                                                            (W >= d.ntp && win_fired(a.win, d.minp, W)))));
+    d.do_fire = d.adv;
+    return d;
+}
+
+// the last workgroup of a launch applies the launch's control decisions: advanceProgress
+// bookkeeping of the processor (AbstractSliceSyncStateWindowAggProcessor.java:139-153), the buffer
+// reset after a flush, the consumed timer requests, and the overflow-counter switch of a result reset.
+template <int KIND>
 __device__ void merge_finalize(const MergeArgs& a, int64_t W) {
     Ctrl* c = a.ctrl;
-    const int64_t cur = c->cur, pend = c->pending_pushes, ntp = c->ntp;
-    const bool adv = !a.force_flush && W > cur;
-    const bool do_flush = pend > 0 && (a.force_flush || (adv && (a.always_flush || (W >= ntp && win_fired(a.win, c->min_pending, W)))));
-    if (adv) {
+    const MergeDecision d = merge_decide<KIND>(a, W);
+    if (d.adv) {
         c->cur = W;
-        if (W >= ntp) c->ntp = tz_next_trigger_watermark(a.win.tz, W, a.win.slice_div);
+        if (W >= d.ntp) c->ntp = tz_next_trigger_watermark(a.win.tz, W, a.win.slice_div);
     }
-    if (do_flush) {
+    if (d.do_flush) {
         c->pending_pushes = 0;
         c->min_pending = INT64_MAX;
         c->pending_rows = 0;
@@ -771,15 +797,16 @@ __device__ void merge_finalize(const MergeArgs& a, int64_t W) {
     // the overflow region's rows, beside the slab counts (fw_results_device_segments)
     a.sb_out[a.n_sb] = (int32_t)min((int64_t)__hip_atomic_load(&c->out_count[sel], __ATOMIC_RELAXED, DEV_SCOPE), a.out_cap);
     if (a.host_mirror)  // vector store to host-mapped memory (system scope)
-        __hip_atomic_store(a.host_mirror, (unsigned long long)((a.merge_seq << 8) | (uint64_t)(do_flush ? 0 : pend)),
+        __hip_atomic_store(a.host_mirror, (unsigned long long)((a.merge_seq << 8) | (uint64_t)(d.do_flush ? 0 : d.pend)),
                            __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
 }
 
+template <int KIND>
 __device__ __forceinline__ void merge_ticket(const MergeArgs& a, int64_t W) {
     if (threadIdx.x != 0) return;
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     if (grid_last_wg(a.tickets->c[1])) {
-        merge_finalize(a, W);
+        merge_finalize<KIND>(a, W);
         kt_end(a.kt);
     }
 }
@@ -1478,17 +1505,9 @@ __global__ __launch_bounds__(MG_BLOCK, 4) void k_merge_fire(MergeArgs a) {
     Ctrl* c = a.ctrl;
     const int64_t W = merge_watermark(a);
     // control decisions; the launch's last workgroup applies them to the control block (merge_finalize)
-    const int64_t cur = __hip_atomic_load(&c->cur, __ATOMIC_RELAXED, DEV_SCOPE);
-    const int64_t pend = __hip_atomic_load(&c->pending_pushes, __ATOMIC_RELAXED, DEV_SCOPE);
-    const int64_t ntreq = min(__hip_atomic_load(&c->n_treq, __ATOMIC_RELAXED, DEV_SCOPE), a.treq_cap);  // the ingest counts on past the cap (ERR_TREQ)
-    const int64_t nlf = KIND == KIND_DSWIN ? min(__hip_atomic_load(&c->n_lfire, __ATOMIC_RELAXED, DEV_SCOPE), a.lfire_cap) : 0;
-    const int64_t ntp = __hip_atomic_load(&c->ntp, __ATOMIC_RELAXED, DEV_SCOPE);
-    const int64_t minp = __hip_atomic_load(&c->min_pending, __ATOMIC_RELAXED, DEV_SCOPE);
-    const bool adv = !a.force_flush && W > cur;
-    const bool do_flush = pend > 0 &&
-                          (a.force_flush || (adv && (a.always_flush || (W >= ntp && win_fired(a.win, minp, W)))));
-    const bool do_fire = adv;
-    const int64_t w_old = cur;
+    const MergeDecision d = merge_decide<KIND>(a, W);
+    const int64_t pend = d.pend, ntreq = d.ntreq, nlf = d.nlf, w_old = d.cur;
+    const bool do_flush = d.do_flush, do_fire = d.do_fire;
 
     Stamps stm;
     stm.init((FW_ABL(a) & AB_STAMPS) != 0);
@@ -2206,7 +2225,7 @@ __global__ __launch_bounds__(MG_BLOCK, 4) void k_merge_fire(MergeArgs a) {
         if (tid == 0 && n_by_path[1]) atomicAdd(&a.tickets->mg_path[1], (unsigned long long)n_by_path[1]);
     }
     stm.flush(a.stamps);
-    merge_ticket(a, W);
+    merge_ticket<KIND>(a, W);
 }
 
 // persistent grid of the merge kernel: one workgroup per CU, at most one per superbucket

@@ -40,7 +40,12 @@ def test_random_stream_matches_oracle(name):
 
 # Every accumulator layout with its own k_merge_fire variant (fw_merge_impl.h MergeLayouts: the
 # word ops as compile-time constants), under each SQL window kind, against the oracle.  HOP needs
-# a COUNT(*), so it runs the layouts that have one.
+# a COUNT(*), so it runs the layouts that have one.  "six_words" reads both value columns as BIGINT
+# (the second column's bit patterns) and plans six distinct accumulator words -- the planner keeps
+# one word per (op, column), so aggregates that share a word do not count -- which selects the
+# eight-word OPS_ANY variant: one block of rows in flight, the plain cell loop.  "ds_sliding" is the
+# DataStream sliding window (KIND_DSWIN), whose rows reach the same folds through
+# ds_add_to_windows -- FW_RUNS=1 through the runs gather.
 LAYOUT_AGGS = {
     "cnt": [(abi.AGG_COUNT_STAR, 0, I64)],
     "max": [(abi.AGG_MAX, 0, I64)],
@@ -52,14 +57,22 @@ LAYOUT_AGGS = {
     "cnt_min": [(abi.AGG_COUNT_STAR, 0, I64), (abi.AGG_MIN, 0, I64)],
     "cnt_sum_min_max": [(abi.AGG_COUNT_STAR, 0, I64), (abi.AGG_SUM, 0, I64), (abi.AGG_MIN, 0, I64),
                         (abi.AGG_MAX, 0, I64)],
+    "six_words": [(abi.AGG_COUNT_STAR, 0, I64), (abi.AGG_SUM, 0, I64), (abi.AGG_MIN, 0, I64),
+                  (abi.AGG_MAX, 0, I64), (abi.AGG_MIN, 1, I64), (abi.AGG_MAX, 1, I64)],
 }
-LAYOUT_WINDOWS = {
+SQL_LAYOUT_WINDOWS = {
     "tumble": dict(window_kind=abi.WIN_TUMBLE, size_ms=6000),
     "hop": dict(window_kind=abi.WIN_HOP, size_ms=6000, slide_ms=2000),
     "cumulate": dict(window_kind=abi.WIN_CUMULATE, size_ms=8000, slide_ms=2000),
 }
-LAYOUT_CASES = [(w, a) for w in LAYOUT_WINDOWS for a in LAYOUT_AGGS
-                if w != "hop" or LAYOUT_AGGS[a][0][0] == abi.AGG_COUNT_STAR]
+LAYOUT_WINDOWS = dict(SQL_LAYOUT_WINDOWS,
+                      ds_sliding=dict(api=abi.API_DATASTREAM, window_kind=abi.WIN_HOP, size_ms=6000, slide_ms=2000))
+LAYOUT_CASES = [(w, a) for w in SQL_LAYOUT_WINDOWS for a in LAYOUT_AGGS
+                if w != "hop" or LAYOUT_AGGS[a][0][0] == abi.AGG_COUNT_STAR] + [("ds_sliding", "max")]
+# superbucket capacity of a handle that plans more than four accumulator words (fw_internal.h
+# mg_entries(8, kind); up to four words: 2048 or more), which the merge launch checks against the
+# variant it starts: the sign that the eight-word kernels ran
+CAP_E_EIGHT_WORDS = 1024
 
 
 # The rows where the merge wrote them (fw_results_device_segments: per-superbucket slabs and the
@@ -87,8 +100,12 @@ def test_compiled_accumulator_layouts_match_oracle(win, aggs, layout, monkeypatc
     kw = dict(LAYOUT_WINDOWS[win], aggs=LAYOUT_AGGS[aggs])
     if kw["aggs"][0][0] == abi.AGG_COUNT_STAR:
         kw["count_star_index"] = 0
+    if aggs == "six_words":
+        kw["value_col_types"] = [I64, I64]
+    st = {}
     _run_both(_cfg(kw), _stream(zlib.crc32(f"{win}{aggs}".encode()) % 1000, 20000, 300, ooo=2 * kw["size_ms"],
-                                step_ms=4500, n_wm=20), _double_cols(kw))  # 2-3 slides per watermark: HOP chains
+                                step_ms=4500, n_wm=20), _double_cols(kw), stats=st)  # 2-3 slides per watermark: HOP chains
+    assert (st["superbucket_capacity"] == CAP_E_EIGHT_WORDS) == (aggs == "six_words"), st
 
 
 # TIMESTAMP_LTZ windows across daylight-saving changes: slices on the zone's wall clock, timers at

@@ -1,6 +1,7 @@
 #!/bin/bash
 # Register / spill report of the kernel translation units (host-side compile only):
 #   tools/regs.sh [k_ingest_nv1 k_merge_nw1 ...]
+# per kernel VGPRs, VGPR and SGPR spills, scratch bytes per lane, occupancy (waves per SIMD) and LDS bytes.
 # Instruction mix of their kernels, from the same compile with -S:
 #   tools/regs.sh --mix [k_ingest_pack ...]
 # per kernel the instruction count, the counts by class (v_*, s_*, ds_*, global_*) and of the
@@ -69,12 +70,12 @@ for line in sys.stdin:
     m = re.search(r"Name: (\S+)", line)
     if m:
         cur = {"name": m.group(1)}; rows.append(cur); continue
-    m = re.search(r"(VGPRs|AGPRs|ScratchSize \[bytes/lane\]|SGPRs Spill|VGPRs Spill|Occupancy \[waves/SIMD\]): (\d+)", line)
+    m = re.search(r"(VGPRs|AGPRs|ScratchSize \[bytes/lane\]|SGPRs Spill|VGPRs Spill|Occupancy \[waves/SIMD\]|LDS Size \[bytes/block\]): (\d+)", line)
     if m and cur is not None: cur[m.group(1)] = int(m.group(2))
 names = subprocess.run(["c++filt"], input="\n".join(r["name"] for r in rows), capture_output=True, text=True).stdout.split("\n")
 for r, n in zip(rows, names):
     n = re.sub(r"fw::|\(fw::\w+\)|void ", "", n)
     g = lambda k: r.get(k, 0)
-    print("%-70s vgpr %4d vspill %4d sspill %4d scratch %d" % (n, g("VGPRs"), g("VGPRs Spill"), g("SGPRs Spill"), g("ScratchSize [bytes/lane]")))
+    print("%-70s vgpr %4d vspill %4d sspill %4d scratch %d occ %d lds %d" % (n, g("VGPRs"), g("VGPRs Spill"), g("SGPRs Spill"), g("ScratchSize [bytes/lane]"), g("Occupancy [waves/SIMD]"), g("LDS Size [bytes/block]")))
 '
   done
