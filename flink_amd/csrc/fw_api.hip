@@ -538,7 +538,8 @@ int validate_and_plan(fw_handle* h) {
         h->stage_cap = c.max_batch_rows;
         return FW_OK;
     }
-    if (c.window_kind == FW_WIN_SESSION || c.window_kind == FW_WIN_SESSION_DYNAMIC) {  // session windows: a plan of their own (fw_session.hip)
+    if (c.window_kind == FW_WIN_SESSION || c.window_kind == FW_WIN_SESSION_DYNAMIC ||
+        c.window_kind == FW_WIN_SESSION_LATENESS) {  // session windows: a plan of their own (fw_session.hip)
         int rc = sw_plan(c, &h->sw);
         if (rc) return rc;
         h->ks = h->sw.ks;
@@ -1768,9 +1769,10 @@ int fw_advance(fw_handle* h, int64_t watermark) {
         // device takes the maximum
         if (h->sw.wm_dev) return sw_advance_device(&h->sw, nullptr, watermark);
         if (watermark <= h->host_cur) return FW_OK;
+        const int64_t prev = h->host_cur;  // (lateness: the sessions with a timer at or below it have fired)
         h->host_cur = watermark;
         HIP_TRY(hipMemcpyAsync(&h->ctrl->cur, &h->host_cur, sizeof(int64_t), hipMemcpyHostToDevice, h->stream));
-        return sw_advance(&h->sw, watermark);
+        return sw_advance(&h->sw, watermark, prev);
     }
     ar_kick(h);
     // A SQL watermark below the next trigger watermark crosses no slice end: no window fires, no
@@ -2810,7 +2812,12 @@ int fw_snapshot_key_group(fw_handle* h, int32_t key_group, void* buf, int64_t ca
 int fw_restore_key_group(fw_handle* h, const void* buf, int64_t size) {
     if (!h || !buf) return fail(FW_E_INVALID, "null argument");
     if (h->cw.on) return cw_restore(&h->cw, true, buf, size);
-    if (h->sw.on) return sw_restore(&h->sw, true, buf, size, &h->host_cur);
+    if (h->sw.on) {
+        // (lateness: the blob's watermark must be the handle's, which is Ctrl::cur once advanced from the device)
+        int rc_wm = 0;
+        if (h->sw.late && h->sw.wm_dev && (rc_wm = sw_read_watermark(&h->sw, &h->host_cur))) return rc_wm;
+        return sw_restore(&h->sw, true, buf, size, &h->host_cur);
+    }
     KgHeader hd;
     if (size < (int64_t)sizeof hd) return fail(FW_E_INVALID, "key-group snapshot truncated");
     memcpy(&hd, buf, sizeof hd);
@@ -3610,6 +3617,30 @@ int fw_host_session_add(const fw_config* cfg, int64_t watermark, int64_t ts, int
     for (int32_t i = 0; i < *n; i++) accs[i] = (int64_t)session_result(d, (uint64_t)accs[i]);
     if (r < 0) return fail(FW_E_CAPACITY, "the session list is full (%d sessions)", capacity);
     *outcome = r;
+    return FW_OK;
+}
+
+int fw_host_session_add_late(const fw_config* cfg, int64_t watermark, int64_t ts, int64_t value, int64_t* starts, int64_t* ends,
+                             int64_t* accs, int32_t* n, int32_t capacity, int32_t* outcome, int32_t* fired_index) {
+    if (!cfg || !n || !outcome || !fired_index || (capacity > 0 && (!starts || !ends || !accs))) return fail(FW_E_INVALID, "null argument");
+    if (cfg->window_kind != FW_WIN_SESSION_LATENESS)
+        return fail(FW_E_INVALID, "fw_host_session_add_late needs a FW_WIN_SESSION_LATENESS configuration");
+    fw_handle h;
+    h.cfg = *cfg;
+    const int rc = validate_and_plan(&h);
+    if (rc) return rc;
+    if (*n < 0 || *n > capacity) return fail(FW_E_INVALID, "bad session count %d (capacity %d)", *n, capacity);
+    const SessionDesc& d = h.sw.d;
+    for (int32_t i = 0; i < *n; i++) accs[i] = (int64_t)session_word_of_result(d, (uint64_t)accs[i]);
+    const uint64_t word = session_word(d, (uint64_t)value);
+    int32_t at = -1;
+    const int r = session_add<1, true>(d.gap, d.ops, watermark, ts, &word, 1, starts, ends, (uint64_t*)accs, 1, 1, n, capacity,
+                                       h.sw.lateness, &at);
+    for (int32_t i = 0; i < *n; i++) accs[i] = (int64_t)session_result(d, (uint64_t)accs[i]);
+    if (r < 0) return fail(FW_E_CAPACITY, "the session list is full (%d sessions)", capacity);
+    *outcome = r;
+    // EventTimeTrigger.onElement: the session the element produced fires at once if its timer has passed
+    *fired_index = r == 1 && session_due(ends[at], watermark) ? at : -1;
     return FW_OK;
 }
 

@@ -65,6 +65,18 @@ FW_HD void session_cover(int64_t* start, int64_t* end, int64_t b_start, int64_t 
 FW_HD bool session_late(int64_t ts, int64_t gap, int64_t watermark) { return ts + gap - 1 <= watermark; }
 // EventTimeTrigger: the window's timer at maxTimestamp = end - 1 fires once the watermark reaches it
 FW_HD bool session_due(int64_t end, int64_t watermark) { return end - 1 <= watermark; }
+// The same with allowedLateness = L > 0 (FW_WIN_SESSION_LATENESS; recalled, parity unpinned:
+// WindowOperator.isWindowLate / cleanupTime, EventTimeTrigger.onElement).  A window is late once its
+// cleanup time maxTimestamp + L has passed; a session is held until then and fires when the
+// watermark first reaches end - 1, so a held session with end - 1 <= W has fired with exactly its
+// contents and the watermark alone tells which sessions have (no per-session bit).
+FW_HD bool session_late_l(int64_t ts, int64_t gap, int64_t lateness, int64_t watermark) {
+    return ts + gap - 1 + lateness <= watermark;
+}
+// the session's timer fires in an advance of the watermark from w0 to w1 > w0
+FW_HD bool session_fires(int64_t end, int64_t w0, int64_t w1) { return w0 < end - 1 && end - 1 <= w1; }
+// the session's cleanup timer at end - 1 + L has run at `watermark`: the session is removed
+FW_HD bool session_cleaned(int64_t end, int64_t lateness, int64_t watermark) { return end - 1 + lateness <= watermark; }
 
 // an element's value as an accumulator word, and a fired accumulator as the result value
 FW_HD uint64_t session_word(const SessionDesc& d, uint64_t v) {
@@ -109,9 +121,14 @@ FW_HD int32_t session_op_of_word(int32_t wop) {
 // and is late is dropped and leaves the list untouched.  `gap` is the element's own: the handle's for
 // a static-gap session, the row's for a dynamic-gap one.
 // Returns 1 merged or added, 0 dropped as late, -1 the list is full (capacity sessions).
-template <int NW>
+// LATE: the form with an allowed lateness.  The drop test is the window's cleanup time
+// (session_late_l) and *at is the list index of the session the element produced, so that the caller
+// can apply EventTimeTrigger.onElement: a resulting session with end - 1 <= watermark fires at once.
+// The form without LATE reads neither `lateness` nor `at`.
+template <int NW, bool LATE = false>
 FW_HD int session_add(int64_t gap, const int32_t* ops, int64_t watermark, int64_t ts, const uint64_t* words, int wstride,
-                      int64_t* start, int64_t* end, uint64_t* acc, int stride, int astride, int32_t* n, int32_t capacity) {
+                      int64_t* start, int64_t* end, uint64_t* acc, int stride, int astride, int32_t* n, int32_t capacity,
+                      int64_t lateness = 0, int32_t* at = nullptr) {
     const int32_t m = *n;
     const int64_t we = ts + gap;
     int32_t i = 0;
@@ -121,7 +138,7 @@ FW_HD int session_add(int64_t gap, const int32_t* ops, int64_t watermark, int64_
     int32_t j = i;
     while (j < m && session_intersects(ts, we, start[(size_t)j * stride], end[(size_t)j * stride])) j++;
     if (i == j) {
-        if (session_late(ts, gap, watermark)) return 0;
+        if (LATE ? session_late_l(ts, gap, lateness, watermark) : session_late(ts, gap, watermark)) return 0;
         if (m >= capacity) return -1;
         for (int32_t k = m; k > i; k--) {
             start[(size_t)k * stride] = start[(size_t)(k - 1) * stride];
@@ -132,8 +149,10 @@ FW_HD int session_add(int64_t gap, const int32_t* ops, int64_t watermark, int64_
         end[(size_t)i * stride] = we;
         for (int w = 0; w < NW; w++) acc[(size_t)i * astride + w] = words[(size_t)w * wstride];
         *n = m + 1;
+        if (LATE) *at = i;
         return 1;
     }
+    if (LATE) *at = i;
     int64_t s = ts, e = we;
     for (int32_t k = i; k < j; k++) {
         session_cover(&s, &e, start[(size_t)k * stride], end[(size_t)k * stride]);
@@ -169,6 +188,10 @@ struct SessionOp {
     // advanced from the device, sw_advance_device): every fold and advance reads it there, and the
     // host's mirror (fw_handle::host_cur) is only a lower bound until a reader synchronises
     bool wm_dev = false;
+    // FW_WIN_SESSION_LATENESS: sessions are held until end - 1 + lateness, late elements into a held
+    // session re-fire it (DESIGN.md "Session windows", Lateness)
+    bool late = false;
+    int64_t lateness = 0;
     SessionDesc d{};
     AggDesc ad{};             // SQL: the aggregates over the words (sql_agg_result)
     KeySpace ks{};
@@ -188,6 +211,10 @@ struct SessionOp {
     uint64_t* scratch = nullptr;   // [n_sb][cap_s + SW_TILE] sessions: the merged list of one tile's fold
     int32_t* n_s = nullptr;        // [n_sb] sessions held
     int64_t* min_end = nullptr;    // [n_sb] a lower bound of the superbucket's smallest session end
+    // (late) min_end bounds every held session's end, so min_end - 1 + lateness the smallest cleanup
+    // time; min_fire bounds the smallest end of a session that has not fired
+    int64_t* min_fire = nullptr;   // [n_sb]
+    int64_t* prev_wm = nullptr;    // (late) Ctrl::cur as it stood in front of the last device advance
     FoldedPart part{};             // the superbucket partition's buffers
     // result rows and the late side output
     int64_t* out_key = nullptr;
@@ -221,7 +248,9 @@ int sw_push_segments(SessionOp* op, int32_t n_segs, int64_t seg_len, const int64
                      const int64_t* d_ts, int32_t stride, const int32_t* d_khash, const void* const* d_vals,
                      const uint8_t* const* d_nulls);
 // fires every session with end - 1 <= watermark and compacts the rest (stream-ordered, asynchronous)
-int sw_advance(SessionOp* op, int64_t watermark);
+// (lateness: the sessions with prev_watermark < end - 1 <= watermark fire, the ones with
+// end - 1 + lateness <= watermark leave; the other kinds do not read prev_watermark)
+int sw_advance(SessionOp* op, int64_t watermark, int64_t prev_watermark = 0);
 // Ctrl::cur = W' = max(Ctrl::cur, *d_watermark or, with d_watermark NULL, watermark), then every session
 // with end - 1 <= W' fires: two stream-ordered launches, no host wait.  Sets op->wm_dev.
 int sw_advance_device(SessionOp* op, const int64_t* d_watermark, int64_t watermark);

@@ -16,6 +16,12 @@
 // live rows fd_partition_segments selected, and the watermark from Ctrl::cur; k_sw_advance<NW, true>
 // reads Ctrl::cur behind the one-thread k_sw_raise.  The instances above are unchanged and are what a
 // direct push of a host-watermark handle launches.
+// An allowed lateness (FW_WIN_SESSION_LATENESS) is a last template argument of both kernels, NW = 1 and
+// a static gap only: k_sw_fold<1, false, DEV, true> re-fires a retained session from the arrival-order
+// walk of a late-candidate run, k_sw_advance<1, DEV, true> fires the sessions whose timer lies between
+// the previous watermark and the new one and removes the ones past their cleanup time (in the device
+// form behind k_sw_raise_late, which keeps the previous watermark).  Every lateness line sits behind
+// that argument; the instances above compile to what they compiled to without it.
 // No workgroup waits on another: the only cross-workgroup traffic is counters (atomic adds).
 #include <hip/hip_runtime.h>
 
@@ -102,6 +108,14 @@ struct SwFoldArgs {
     int64_t side_cap;
     int64_t ord_base;  // push_seq << 32 | row offset of this launch within its call
     int32_t stride;    // the device form (DEV): key, ts and value words of row r at col[r * stride]
+    // the lateness form (LATE) alone reads what follows: rows that fire at once go to the result buffer
+    int64_t lateness;
+    int64_t* min_fire;
+    int64_t* out_key;
+    int64_t* out_ws;
+    int64_t* out_we;
+    uint64_t* out_val;
+    int64_t out_cap;
 };
 
 // first index in [lo, hi) of the sorted session list whose (key, start) is not below (k, s)
@@ -145,9 +159,17 @@ __device__ __forceinline__ void sw_row_words(const SwFoldArgs& a, uint32_t row, 
 // over rows + 0, 1, 2 + c a packed one -- and the watermark from a.ctrl->cur, a word no workgroup of
 // a fold launch writes.  Everything else is the one body.  The instances without DEV are the ones a
 // direct push of a host-watermark handle launches; they read neither a.stride nor Ctrl::cur.
-template <int NW, bool DYN = false, bool DEV = false>
+// LATE (NW = 1, static gap): the form with an allowed lateness (FW_WIN_SESSION_LATENESS).  The state
+// then also holds sessions that have fired (end - 1 <= W) until their cleanup time.  A late candidate
+// is the same row as ever, ts + gap - 1 <= W, and its key run takes the same arrival-order walk, where
+// the drop test is the cleanup time and a row whose resulting session has end - 1 <= W emits that
+// session at once (EventTimeTrigger.onElement: FIRE, no purge).  A run without a candidate holds only
+// rows with ts + gap - 1 > W: whatever they merge with, fired sessions included, ends behind the
+// watermark, nothing fires and nothing is dropped, so the result is the union of intervals as before.
+template <int NW, bool DYN = false, bool DEV = false, bool LATE = false>
 __global__ __launch_bounds__(SW_TILE) void k_sw_fold(SwFoldArgs a) {
     static_assert(!DYN || NW == 1, "the dynamic-gap fold is a DataStream instance");
+    static_assert(!LATE || (NW == 1 && !DYN), "the lateness fold is the static-gap DataStream instance");
     constexpr int SWS = sw_stride(NW);   // words per session
     __shared__ uint64_t sk[SW_TILE];     // sorted keys; then the coalesce chunk's keys
     __shared__ int64_t sts[SW_TILE];     // their timestamps; then the chunk's ends
@@ -180,6 +202,7 @@ __global__ __launch_bounds__(SW_TILE) void k_sw_fold(SwFoldArgs a) {
     int ns = a.n_s[blockIdx.x];
     const int ns_at_entry = ns;
     int64_t tile_min_end = INT64_MAX;
+    int64_t tile_min_fire = INT64_MAX;  // (LATE) over the rows that are no late candidates
 
     for (int64_t base = seg0; base < seg1; base += SW_TILE) {
         const int nrows = (int)(seg1 - base < SW_TILE ? seg1 - base : SW_TILE);
@@ -258,6 +281,7 @@ __global__ __launch_bounds__(SW_TILE) void k_sw_fold(SwFoldArgs a) {
         const bool shead = valid && !slow && (rank == 0 || (DYN ? myts > pmax : myts - sts[t - 1] > gap));
         const bool stail = valid && !slow && (runtail || (DYN ? sts[t + 1] > imax : sts[t + 1] - myts > gap));
         tile_min_end = valid && SW_END < tile_min_end ? SW_END : tile_min_end;
+        if (LATE && valid && !session_late(myts, gap, W) && SW_END < tile_min_fire) tile_min_fire = SW_END;
         // the sessions the tile can add at most; if they might not fit, the coalesce pass below runs
         // once more in front, only counting (uniform)
         const int may_add = __syncthreads_count(shead || slow);
@@ -355,8 +379,22 @@ __global__ __launch_bounds__(SW_TILE) void k_sw_fold(SwFoldArgs a) {
                 // the row's words: a late-candidate run's rows are segments of their own in the scan
                 // above, so sa[.][u] still holds the words of the row at sorted index u (and se[u] its
                 // own end: a dynamic gap travels like the word)
-                const int rc = session_add<NW>(DYN ? se[u] - ts : gap, ops, W, ts, &sa[0][u], SW_TILE, (int64_t*)reg + 1,
-                                               (int64_t*)reg + 2, reg + 3, SWS, SWS, &n, room);
+                int32_t at = 0;
+                const int rc = session_add<NW, LATE>(DYN ? se[u] - ts : gap, ops, W, ts, &sa[0][u], SW_TILE, (int64_t*)reg + 1,
+                                                     (int64_t*)reg + 2, reg + 3, SWS, SWS, &n, room, LATE ? a.lateness : 0, &at);
+                if (LATE && rc == 1 && session_due((int64_t)reg[(size_t)at * SWS + 2], W)) {
+                    // the session the row produced has fired before: it fires again, with the row
+                    const unsigned long long o = atomicAdd((unsigned long long*)&a.ctrl->out_count[0], 1ull);
+                    atomicAdd((unsigned long long*)&a.ctrl->fired, 1ull);
+                    if (o < (unsigned long long)a.out_cap) {
+                        a.out_key[o] = (int64_t)mykey;
+                        a.out_ws[o] = (int64_t)reg[(size_t)at * SWS + 1];
+                        a.out_we[o] = (int64_t)reg[(size_t)at * SWS + 2];
+                        a.out_val[o] = session_result(a.d, reg[(size_t)at * SWS + 3]);
+                    } else {
+                        atomicOr(&a.ctrl->error, ERR_OUTPUT);
+                    }
+                }
                 if (rc == 0) {  // dropped: counted (SQL has no side output: late_side is 0)
                     atomicAdd(&n_drop, 1u);
                     if (NW == 1 && a.late_side) {
@@ -527,6 +565,18 @@ __global__ __launch_bounds__(SW_TILE) void k_sw_fold(SwFoldArgs a) {
         __syncthreads();
     }
     if (t == 0 && sts[0] < a.min_end[blockIdx.x]) a.min_end[blockIdx.x] = sts[0];
+    if (LATE) {
+        // a session that has not fired ends where a held one did or where a row that is no late
+        // candidate does: a candidate's own window ends at or before W + 1
+        __syncthreads();
+        sts[t] = tile_min_fire;
+        __syncthreads();
+        for (int dd = SW_TILE >> 1; dd > 0; dd >>= 1) {
+            if (t < dd && sts[t + dd] < sts[t]) sts[t] = sts[t + dd];
+            __syncthreads();
+        }
+        if (t == 0 && sts[0] < a.min_fire[blockIdx.x]) a.min_fire[blockIdx.x] = sts[0];
+    }
 #undef SW_OP
 #undef SW_IDN
 #undef SW_END
@@ -549,24 +599,40 @@ struct SwAdvArgs {
     uint64_t* out_val[FW_MAX_AGGS];
     uint32_t* out_null;
     int64_t out_cap;
+    // the lateness form (LATE) alone reads what follows
+    int64_t lateness;
+    int64_t prev_watermark;     // host form: the watermark in front of this advance
+    const int64_t* prev_wm;     // device form: the same, as k_sw_raise_late left it
+    int64_t* min_fire;
 };
 
 // DEV: the watermark is Ctrl::cur, which k_sw_raise set in a launch of its own in front (no
 // workgroup of this launch writes it)
-template <int NW, bool DEV = false>
+// LATE: an advance from W0 to W emits the sessions whose timer lies in (W0, W] -- the ones at or below
+// W0 have fired -- and removes the ones whose cleanup time end - 1 + L has passed, emitted or not.
+// min_fire and min_end are exact behind it, so an advance that neither fires nor cleans returns
+// without reading the list.
+template <int NW, bool DEV = false, bool LATE = false>
 __global__ __launch_bounds__(SW_TILE) void k_sw_advance(SwAdvArgs a) {
+    static_assert(!LATE || NW == 1, "the lateness advance is the DataStream instance");
     constexpr int SWS = sw_stride(NW);
     const int64_t W = DEV ? a.ctrl->cur : a.watermark;
+    const int64_t W0 = !LATE ? 0 : DEV ? *a.prev_wm : a.prev_watermark;
+    const int64_t Lt = LATE ? a.lateness : 0;
     __shared__ int32_t buf[SW_TILE];
     __shared__ int64_t mn[SW_TILE];
     __shared__ unsigned long long out_base;
     const int t = threadIdx.x;
     const int ns = a.n_s[blockIdx.x];
-    if (ns == 0 || !session_due(a.min_end[blockIdx.x], W)) return;  // nothing is due (uniform)
+    if (!LATE && (ns == 0 || !session_due(a.min_end[blockIdx.x], W))) return;  // nothing is due (uniform)
+    if (LATE && (ns == 0 || W <= W0 || (!session_due(a.min_fire[blockIdx.x], W) && !session_cleaned(a.min_end[blockIdx.x], Lt, W))))
+        return;  // no timer of either kind is due (uniform)
     uint64_t* st = a.state + (size_t)blockIdx.x * a.cap_s * SWS;
     // the due sessions, counted first: one device atomic per workgroup claims their output rows
     int32_t mine = 0;
-    for (int i = t; i < ns; i += SW_TILE) mine += session_due((int64_t)st[(size_t)i * SWS + 2], W) ? 1 : 0;
+#define SW_DUE(e) (LATE ? session_fires((e), W0, W) : session_due((e), W))
+#define SW_GONE(e) (LATE ? session_cleaned((e), Lt, W) : session_due((e), W))
+    for (int i = t; i < ns; i += SW_TILE) mine += SW_DUE((int64_t)st[(size_t)i * SWS + 2]) ? 1 : 0;
     int32_t n_due;
     fd_block_scan<SW_TILE>(mine, buf, &n_due);
     if (t == 0) {
@@ -574,14 +640,14 @@ __global__ __launch_bounds__(SW_TILE) void k_sw_advance(SwAdvArgs a) {
         if (n_due) {
             out_base = atomicAdd((unsigned long long*)&a.ctrl->out_count[0], (unsigned long long)n_due);
             atomicAdd((unsigned long long*)&a.ctrl->fired, (unsigned long long)n_due);
-            atomicAdd((unsigned long long*)&a.ctrl->live_entries, (unsigned long long)(long long)(-n_due));
+            if (!LATE) atomicAdd((unsigned long long*)&a.ctrl->live_entries, (unsigned long long)(long long)(-n_due));
             if (out_base + (unsigned long long)n_due > (unsigned long long)a.out_cap) atomicOr(&a.ctrl->error, ERR_OUTPUT);
         }
     }
     __syncthreads();
     const bool sql = a.d.sql != 0;  // (uniform)
     int32_t fired = 0, kept = 0;
-    int64_t min_end = INT64_MAX;
+    int64_t min_end = INT64_MAX, min_fire = INT64_MAX;
     for (int c0 = 0; c0 < ns; c0 += SW_TILE) {
         const int i = c0 + t;
         const bool in = i < ns;
@@ -596,9 +662,9 @@ __global__ __launch_bounds__(SW_TILE) void k_sw_advance(SwAdvArgs a) {
 #pragma unroll
             for (int w = 0; w < NW; w++) acc[w] = st[(size_t)i * SWS + 3 + w];
         }
-        const bool due = in && session_due(e, W);
+        const bool due = in && SW_DUE(e);
         int32_t n_f;
-        const int32_t fi = fd_block_scan<SW_TILE>(due ? 1 : 0, buf, &n_f);  // (barriers: the chunk is in registers)
+        int32_t fi = fd_block_scan<SW_TILE>(due ? 1 : 0, buf, &n_f);  // (barriers: the chunk is in registers)
         const int32_t n_in = ns - c0 < SW_TILE ? ns - c0 : SW_TILE;
         if (due) {
             const unsigned long long o = out_base + (unsigned long long)(fired + fi - 1);
@@ -623,7 +689,13 @@ __global__ __launch_bounds__(SW_TILE) void k_sw_advance(SwAdvArgs a) {
             }
         }
         if (sql) __syncthreads();
-        if (in && !due) {  // stable compaction: the slot is at or before the session's own
+        bool gone = due;
+        if (LATE) {  // what leaves the list is what is cleaned, a set of its own: counted again
+            gone = in && SW_GONE(e);
+            fired += n_f;  // (the output rows claimed so far)
+            fi = fd_block_scan<SW_TILE>(gone ? 1 : 0, buf, &n_f);
+        }
+        if (in && !gone) {  // stable compaction: the slot is at or before the session's own
             uint64_t* dst = st + (size_t)(kept + (t + 1 - fi) - 1) * SWS;
             dst[0] = k;
             dst[1] = (uint64_t)s;
@@ -631,8 +703,9 @@ __global__ __launch_bounds__(SW_TILE) void k_sw_advance(SwAdvArgs a) {
 #pragma unroll
             for (int w = 0; w < NW; w++) dst[3 + w] = acc[w];
             if (e < min_end) min_end = e;
+            if (LATE && !session_due(e, W) && e < min_fire) min_fire = e;
         }
-        fired += n_f;
+        if (!LATE) fired += n_f;
         kept += n_in - n_f;
         __threadfence_block();
         __syncthreads();
@@ -646,6 +719,31 @@ __global__ __launch_bounds__(SW_TILE) void k_sw_advance(SwAdvArgs a) {
     if (t == 0) {
         a.n_s[blockIdx.x] = kept;
         a.min_end[blockIdx.x] = mn[0];
+        if (LATE && kept != ns)
+            atomicAdd((unsigned long long*)&a.ctrl->live_entries, (unsigned long long)(long long)(kept - ns));
+    }
+    if (LATE) {
+        __syncthreads();
+        mn[t] = min_fire;
+        __syncthreads();
+        for (int dd = SW_TILE >> 1; dd > 0; dd >>= 1) {
+            if (t < dd && mn[t + dd] < mn[t]) mn[t] = mn[t + dd];
+            __syncthreads();
+        }
+        if (t == 0) a.min_fire[blockIdx.x] = mn[0];
+    }
+#undef SW_DUE
+#undef SW_GONE
+}
+
+// k_sw_raise for a lateness handle: the watermark in front of the raise goes to *prev, a word of the
+// session operator that only k_sw_advance<1, true, true> reads, in the launch behind this one
+__global__ void k_sw_raise_late(Ctrl* ctrl, const int64_t* d_w, int64_t w, int64_t* prev) {
+    if (blockIdx.x == 0 && threadIdx.x == 0) {
+        const int64_t v = d_w ? *d_w : w;
+        const int64_t c = ctrl->cur;
+        *prev = c;
+        if (v > c) ctrl->cur = v;
     }
 }
 
@@ -800,9 +898,29 @@ static int sw_plan_dyn(const fw_config& c, SessionOp* op) {
     return FW_OK;
 }
 
+// the lateness form: EventTimeSessionWindows.withGap with allowedLateness >= 0.  Everything
+// sw_plan_ds refuses, with its messages, but for the lateness, which has a range of its own
+static int sw_plan_late(const fw_config& c, SessionOp* op) {
+    if (c.api != FW_API_DATASTREAM)
+        return set_error(FW_E_INVALID, "FW_WIN_SESSION_LATENESS (EventTimeSessionWindows with allowedLateness) is a DataStream window: "
+                                       "api must be FW_API_DATASTREAM");
+    if (c.allowed_lateness_ms < 0 || c.allowed_lateness_ms > SW_MAX_GAP)
+        return set_error(FW_E_INVALID, "session windows: allowed_lateness_ms must be in [0, 2^40]");
+    fw_config c0 = c;
+    c0.allowed_lateness_ms = 0;
+    const int rc = sw_plan_ds(c0, op);
+    if (rc) return rc;
+    op->late = true;
+    op->lateness = c.allowed_lateness_ms;
+    return FW_OK;
+}
+
 int sw_plan(const fw_config& c, SessionOp* op) {
     const bool dyn = c.window_kind == FW_WIN_SESSION_DYNAMIC;
-    const int prc = dyn ? sw_plan_dyn(c, op) : c.api == FW_API_SQL ? sw_plan_sql(c, op) : sw_plan_ds(c, op);
+    const int prc = c.window_kind == FW_WIN_SESSION_LATENESS ? sw_plan_late(c, op)
+                    : dyn                                    ? sw_plan_dyn(c, op)
+                    : c.api == FW_API_SQL                    ? sw_plan_sql(c, op)
+                                                             : sw_plan_ds(c, op);
     if (prc) return prc;
     const SessionDesc& d = op->d;
 
@@ -827,6 +945,12 @@ int sw_plan(const fw_config& c, SessionOp* op) {
         for (int64_t v : {(int64_t)c.api, (int64_t)(op->dyn ? FW_WIN_SESSION_DYNAMIC : FW_WIN_SESSION), d.gap, (int64_t)d.op,
                           (int64_t)d.vtype, (int64_t)d.is_count, (int64_t)ks.hash_kind, (int64_t)ks.max_p})
             mix(v);
+        if (op->late) {  // a kind and a lateness of its own: the fired sessions of a blob are read off its watermark
+            x = 0xcbf29ce484222325ull;
+            for (int64_t v : {(int64_t)c.api, (int64_t)FW_WIN_SESSION_LATENESS, d.gap, op->lateness, (int64_t)d.op, (int64_t)d.vtype,
+                              (int64_t)d.is_count, (int64_t)ks.hash_kind, (int64_t)ks.max_p})
+                mix(v);
+        }
     } else {  // the API, every aggregate, the NULL-able columns, key hash, gap, max parallelism
         for (int64_t v : {(int64_t)c.api, (int64_t)FW_WIN_SESSION, d.gap, (int64_t)c.n_aggs, (int64_t)c.nullable_cols,
                           (int64_t)ks.hash_kind, (int64_t)ks.max_p})
@@ -851,6 +975,12 @@ int sw_allocate(SessionOp* op, hipStream_t stream, Ctrl* ctrl) {
     FD_TRY(hipMemsetAsync(op->n_s, 0, (size_t)n_sb * 4, stream));
     if ((rc = fd_dalloc(&op->min_end, (size_t)n_sb))) return rc;
     hipLaunchKernelGGL(k_sw_fill, dim3((n_sb + 255) / 256), dim3(256), 0, stream, op->min_end, INT64_MAX, n_sb);
+    if (op->late) {
+        if ((rc = fd_dalloc(&op->min_fire, (size_t)n_sb))) return rc;
+        hipLaunchKernelGGL(k_sw_fill, dim3((n_sb + 255) / 256), dim3(256), 0, stream, op->min_fire, INT64_MAX, n_sb);
+        if ((rc = fd_dalloc(&op->prev_wm, 1))) return rc;
+        hipLaunchKernelGGL(k_sw_fill, dim3(1), dim3(256), 0, stream, op->prev_wm, INT64_MIN, 1);
+    }
     if ((rc = fd_allocate(&op->part, op->ks))) return rc;
     const size_t oc = (size_t)op->out_cap;
     if ((rc = fd_dalloc(&op->out_key, oc))) return rc;
@@ -870,6 +1000,8 @@ void sw_free(SessionOp* op) {
     hipFree(op->scratch);
     hipFree(op->n_s);
     hipFree(op->min_end);
+    hipFree(op->min_fire);
+    hipFree(op->prev_wm);
     fd_free(&op->part);
     hipFree(op->out_key);
     hipFree(op->out_ws);
@@ -934,7 +1066,17 @@ static int sw_fold_call(SessionOp* op, bool dev, int64_t watermark, int64_t n, c
         fa.side_cap = op->side_cap;
         fa.ord_base = (op->push_seq << 32) + o;
         fa.stride = stride;
-        if (dev) {
+        if (op->late) {
+            fa.lateness = op->lateness;
+            fa.min_fire = op->min_fire;
+            fa.out_key = op->out_key;
+            fa.out_ws = op->out_ws;
+            fa.out_we = op->out_we;
+            fa.out_val = op->out_val[0];
+            fa.out_cap = op->out_cap;
+            if (dev) hipLaunchKernelGGL((k_sw_fold<1, false, true, true>), dim3(n_sb), dim3(SW_TILE), 0, s, fa);
+            else hipLaunchKernelGGL((k_sw_fold<1, false, false, true>), dim3(n_sb), dim3(SW_TILE), 0, s, fa);
+        } else if (dev) {
             if (op->dyn) {
                 hipLaunchKernelGGL((k_sw_fold<1, true, true>), dim3(n_sb), dim3(SW_TILE), 0, s, fa);
             } else {
@@ -978,12 +1120,21 @@ static SwAdvArgs sw_adv_args(SessionOp* op, int64_t watermark) {
     for (int g = 0; g < op->n_out; g++) a.out_val[g] = op->out_val[g];
     a.out_null = op->out_null;
     a.out_cap = op->out_cap;
+    a.lateness = op->lateness;
+    a.prev_wm = op->prev_wm;
+    a.min_fire = op->min_fire;
     return a;
 }
 
 // (a dynamic-gap handle runs the NW = 1 instance too: sessions carry their ends, no gap is read)
-int sw_advance(SessionOp* op, int64_t watermark) {
-    const SwAdvArgs a = sw_adv_args(op, watermark);
+int sw_advance(SessionOp* op, int64_t watermark, int64_t prev_watermark) {
+    SwAdvArgs a = sw_adv_args(op, watermark);
+    if (op->late) {
+        a.prev_watermark = prev_watermark;
+        hipLaunchKernelGGL((k_sw_advance<1, false, true>), dim3(op->ks.n_sb), dim3(SW_TILE), 0, op->stream, a);
+        FD_TRY(hipGetLastError());
+        return FW_OK;
+    }
     SW_LAUNCH_NW(k_sw_advance, SW_HOST, op->nw_t, dim3(op->ks.n_sb), dim3(SW_TILE), 0, op->stream, a);
     FD_TRY(hipGetLastError());
     return FW_OK;
@@ -991,8 +1142,14 @@ int sw_advance(SessionOp* op, int64_t watermark) {
 
 int sw_advance_device(SessionOp* op, const int64_t* d_watermark, int64_t watermark) {
     op->wm_dev = true;
-    hipLaunchKernelGGL(k_sw_raise, dim3(1), dim3(1), 0, op->stream, op->ctrl, d_watermark, watermark);
     const SwAdvArgs a = sw_adv_args(op, 0);
+    if (op->late) {
+        hipLaunchKernelGGL(k_sw_raise_late, dim3(1), dim3(1), 0, op->stream, op->ctrl, d_watermark, watermark, op->prev_wm);
+        hipLaunchKernelGGL((k_sw_advance<1, true, true>), dim3(op->ks.n_sb), dim3(SW_TILE), 0, op->stream, a);
+        FD_TRY(hipGetLastError());
+        return FW_OK;
+    }
+    hipLaunchKernelGGL(k_sw_raise, dim3(1), dim3(1), 0, op->stream, op->ctrl, d_watermark, watermark);
     SW_LAUNCH_NW(k_sw_advance, SW_DEV_ADV, op->nw_t, dim3(op->ks.n_sb), dim3(SW_TILE), 0, op->stream, a);
     FD_TRY(hipGetLastError());
     return FW_OK;
@@ -1065,6 +1222,12 @@ int sw_restore(SessionOp* op, bool key_group, const void* buf, int64_t size, int
     if (hd.magic != (key_group ? SW_KG_MAGIC : SW_MAGIC))
         return set_error(FW_E_INVALID, "not a session-window %ssnapshot", key_group ? "key-group " : "");
     if (hd.fingerprint != op->fingerprint) return set_error(FW_E_INVALID, "session-window snapshot of a different operator configuration");
+    // lateness: which of a blob's sessions have fired is read off its watermark, so a key group joins
+    // only a handle that stands at that watermark (fw_initialize_watermark sets it for a rescaled restore)
+    if (op->late && key_group && hd.watermark != *watermark)
+        return set_error(FW_E_STATE, "session windows with lateness: key group %d was snapshotted at watermark %lld, this subtask "
+                                     "stands at %lld (fw_initialize_watermark before the first key group)",
+                         hd.key_group, (long long)hd.watermark, (long long)*watermark);
     if (hd.n < 0 || size < (int64_t)sizeof hd + hd.n * SW_BLOB_WORDS * 8) return set_error(FW_E_INVALID, "session-window snapshot truncated");
     if (ks.hash_kind == KH_PRE && L > hd.sb_log2)
         return set_error(FW_E_INVALID, "precomputed-hash keys cannot be split finer than the snapshot's sub-buckets");
@@ -1094,7 +1257,7 @@ int sw_restore(SessionOp* op, bool key_group, const void* buf, int64_t size, int
         per[sb - sb0].push_back(en);
     }
     std::vector<uint64_t> tmp;
-    std::vector<int64_t> mins(sb1 - sb0, INT64_MAX);
+    std::vector<int64_t> mins(sb1 - sb0, INT64_MAX), minf(sb1 - sb0, INT64_MAX);
     for (int sb = sb0; sb < sb1; sb++) {
         std::vector<Ent>& v = per[sb - sb0];
         if ((int64_t)v.size() > op->cap_s)
@@ -1107,6 +1270,7 @@ int sw_restore(SessionOp* op, bool key_group, const void* buf, int64_t size, int
             tmp.push_back((uint64_t)x.end);
             for (int w = 0; w < NW; w++) tmp.push_back(x.acc[w]);
             mins[sb - sb0] = std::min(mins[sb - sb0], x.end);
+            if (!session_due(x.end, hd.watermark)) minf[sb - sb0] = std::min(minf[sb - sb0], x.end);
         }
         cnt[sb - sb0] = (int32_t)v.size();
         if (!tmp.empty())
@@ -1114,6 +1278,7 @@ int sw_restore(SessionOp* op, bool key_group, const void* buf, int64_t size, int
     }
     FD_TRY(hipMemcpy(op->n_s + sb0, cnt.data(), cnt.size() * 4, hipMemcpyHostToDevice));
     FD_TRY(hipMemcpy(op->min_end + sb0, mins.data(), mins.size() * 8, hipMemcpyHostToDevice));
+    if (op->late) FD_TRY(hipMemcpy(op->min_fire + sb0, minf.data(), minf.size() * 8, hipMemcpyHostToDevice));
     Ctrl c;
     if ((rc = fd_restored_ctrl(op->ctrl, key_group, hd.n, hd.watermark, &c))) return rc;
     op->push_seq = key_group ? std::max(op->push_seq, hd.push_seq) : hd.push_seq;

@@ -1,0 +1,85 @@
+"""GPU-backed drop-in for keyBy(...).window(EventTimeSessionWindows.withGap(gap)).allowedLateness(L)
+on its eligible subset.
+
+WindowOperatorBuilder would return this operator iff the assigner is EventTimeSessionWindows with a
+static gap, the trigger the default EventTimeTrigger, no evictor, allowedLateness >= 0, and the
+function a built-in field aggregation sum / min / max or a count on a LONG / INT / DOUBLE field of
+(key, field) tuples.  Dynamic gaps and the SQL SESSION TVF with a lateness stay on the reference
+operator.
+
+Semantics (WindowOperator.processElement's merging branch, EventTimeTrigger.onElement, cleanupTime;
+recalled, parity unpinned).  Gap g, lateness L, watermark W:
+  * an element's window [ts, ts + g) and every session of its key that it intersects -- touching
+    counts -- become one session;
+  * an element that intersects nothing and has ts + g - 1 + L <= W is dropped (or goes to the late
+    side output);
+  * any other element is kept, and if the session it produced has end - 1 <= W that session is
+    emitted at once with the element in it.  Nothing is purged: two late elements into one fired
+    session emit two rows, in arrival order;
+  * a watermark W' > W emits every session with W < end - 1 <= W' and removes every session with
+    end - 1 + L <= W'.  Which held sessions have fired is read off the watermark.
+``collect()`` returns the rows late elements fired since the last collection; ``process_watermark``
+returns those and the timer rows.
+"""
+from .. import abi
+from .session_window_operator import _AGG, _KEY, _TYPE, MAX_GAP, SessionWindowOperator
+from .count_window_operator import StringKeyTable
+from .windowing import EventTimeSessionWindows, EventTimeTrigger
+from ..runtime.options import gpu_enabled
+
+MAX_LATENESS = 1 << 40
+
+
+def is_gpu_eligible(assigner, trigger, aggregation, *, evictor=None, allowed_lateness=0, conf=None):
+    """WindowOperatorBuilder's seam for session windows with an allowed lateness.  ``conf``: the job
+    configuration (``gpu.window-agg.enabled``); None = the GPU operator was chosen."""
+    if conf is not None and not gpu_enabled(conf):
+        return False, "gpu.window-agg.enabled is false"
+    if not isinstance(assigner, EventTimeSessionWindows):
+        return False, "assigner is not EventTimeSessionWindows with a static gap (dynamic gaps with allowedLateness stay on the reference operator)"
+    if not isinstance(trigger, EventTimeTrigger):
+        return False, "trigger is not EventTimeTrigger"
+    if evictor is not None:
+        return False, "session windows with an evictor stay on the reference operator"
+    if allowed_lateness < 0 or allowed_lateness > MAX_LATENESS:
+        return False, "allowedLateness must be in [0, 2^40]"
+    if assigner.gap <= 0 or assigner.gap > MAX_GAP:
+        return False, "session gap must be in (0, 2^40]"
+    if len(aggregation) != 2 or aggregation[0] not in _AGG:
+        return False, "not sum / min / max / count (minBy / maxBy stay on the reference operator)"
+    if aggregation[1] not in _TYPE:
+        return False, f"field type {aggregation[1]} is not LONG / INT / DOUBLE"
+    return True, ""
+
+
+class LateSessionWindowOperator(SessionWindowOperator):
+    """SessionWindowOperator's methods (the segment and device-watermark ones included) over a
+    FW_WIN_SESSION_LATENESS handle, and collect()."""
+
+    def __init__(self, gap_ms, allowed_lateness_ms, aggregation=("sum", "LONG"), key_type="LONG", late_side_output=False,
+                 max_parallelism=128, parallelism=1, subtask_index=0, device=0, state_capacity=1 << 16,
+                 max_batch_rows=1 << 20, output_capacity=1 << 20):
+        ok, why = is_gpu_eligible(EventTimeSessionWindows.with_gap(gap_ms), EventTimeTrigger.create(), aggregation,
+                                  allowed_lateness=allowed_lateness_ms)
+        if not ok:
+            raise ValueError(f"not eligible for the GPU late-session-window operator: {why}")
+        fn, ftype = aggregation
+        t = _TYPE[ftype]
+        self.gap = gap_ms
+        self.allowed_lateness = allowed_lateness_ms
+        self.aggregation = aggregation
+        self.key_type = key_type
+        self.cfg = abi.make_config(
+            api=abi.API_DATASTREAM, window_kind=abi.WIN_SESSION_LATENESS, size_ms=gap_ms, allowed_lateness_ms=allowed_lateness_ms,
+            aggs=[(_AGG[fn], 0, t)], count_star_index=-1, value_col_types=[t], key_hash=_KEY[key_type],
+            late_side_output=late_side_output, max_parallelism=max_parallelism, parallelism=parallelism,
+            subtask_index=subtask_index, device=device, state_capacity=state_capacity, max_batch_rows=max_batch_rows,
+            output_capacity=output_capacity)
+        self.handle = None
+        self._keys = StringKeyTable()
+
+    def collect(self):
+        """The rows in the result buffer, without advancing: after a push, the sessions its late
+        elements fired at once, sorted by (timestamp, key, window_start) -- rows of one session differ
+        in their value."""
+        return self._fired()

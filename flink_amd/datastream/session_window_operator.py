@@ -4,9 +4,10 @@ subset.
 WindowOperatorBuilder would return this operator iff the assigner is EventTimeSessionWindows with a
 static gap, the trigger the default EventTimeTrigger, no evictor, allowedLateness 0, and the
 function a built-in field aggregation sum / min / max (SumAggregator / ComparableAggregator) or a
-count on a LONG / INT / DOUBLE field of (key, field) tuples.  Lateness > 0, other triggers, evictors
-and minBy / maxBy stay on the reference operator; dynamic gaps have an operator of their own
-(dynamic_session_window_operator.DynamicSessionWindowOperator).
+count on a LONG / INT / DOUBLE field of (key, field) tuples.  Other triggers, evictors and minBy /
+maxBy stay on the reference operator; dynamic gaps and an allowed lateness have operators of their
+own (dynamic_session_window_operator.DynamicSessionWindowOperator,
+late_session_window_operator.LateSessionWindowOperator).
 
 Semantics (WindowOperator.processElement's merging branch, MergingWindowSet.addWindow,
 TimeWindow.intersects / mergeWindows, EventTimeTrigger): an element's window [ts, ts + gap) and
@@ -45,7 +46,7 @@ def is_gpu_eligible(assigner, trigger, aggregation, *, evictor=None, allowed_lat
     if evictor is not None:
         return False, "session windows with an evictor stay on the reference operator"
     if allowed_lateness != 0:
-        return False, "allowedLateness > 0 needs late re-fires of merged windows (stays on the reference operator)"
+        return False, "allowedLateness > 0 needs late re-fires of merged windows (late_session_window_operator.LateSessionWindowOperator)"
     if assigner.gap <= 0 or assigner.gap > MAX_GAP:
         return False, "session gap must be in (0, 2^40]"
     if len(aggregation) != 2 or aggregation[0] not in _AGG:

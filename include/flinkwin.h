@@ -164,7 +164,25 @@ typedef enum {
        refused.  Snapshot blobs have the entry format of FW_WIN_SESSION (a session stores start and
        end) and a fingerprint of their own: they restore only into a dynamic-gap handle of the same
        size_ms. */
-    FW_WIN_SESSION_DYNAMIC = 5
+    FW_WIN_SESSION_DYNAMIC = 5,
+    /* v11 (additive), DataStream only: EventTimeSessionWindows.withGap(gap) with allowedLateness
+       >= 0, EventTimeTrigger, no evictor (WindowOperator.processElement's merging branch,
+       EventTimeTrigger.onElement, cleanupTime: recalled, parity unpinned).  size_ms is the gap, in
+       (0, 2^40]; allowed_lateness_ms is in [0, 2^40]; everything else is validated as for
+       FW_WIN_SESSION.  A session handle: everything above holds, with these differences.  A session
+       is held until the watermark reaches end - 1 + allowed_lateness_ms; it fires when the watermark
+       first reaches end - 1 and is then retained.  An element that intersects no held session and
+       whose own window has ts + size_ms - 1 + allowed_lateness_ms <= watermark is dropped (counted,
+       and written to the late side output if configured).  Any other element is kept, and if the
+       session it produced has end - 1 <= watermark that session is emitted at once, with the
+       element: the row is in the result buffer as soon as the push's fold has run, nothing is
+       purged, and two late elements into one fired session emit two rows in arrival order.
+       num_fired_windows counts every emitted row; live_state_entries counts held sessions, fired
+       ones included.  Which held sessions have fired is read off the watermark, so snapshot blobs
+       keep the FW_WIN_SESSION entry format; their fingerprint mixes the kind and the lateness.
+       fw_restore_key_group returns FW_E_STATE unless the blob's watermark equals the handle's
+       current watermark (fw_initialize_watermark before the first key group sets it). */
+    FW_WIN_SESSION_LATENESS = 6
 } fw_window_kind;
 
 typedef enum {
@@ -407,7 +425,7 @@ int fw_push_device_key_rows(fw_handle* h, int64_t n, const int64_t* d_key_row_of
    the row counts): n_segs segments of seg_len rows, one per sending subtask; segment s holds
    d_seg_counts[s] valid rows (device int64, e.g. the counts all-to-all's result), the rest is
    padding and is never read.  Otherwise as fw_push_device.
-   A session handle (FW_WIN_SESSION, FW_WIN_SESSION_DYNAMIC, either API) takes the call iff its
+   A session handle (FW_WIN_SESSION, FW_WIN_SESSION_DYNAMIC, FW_WIN_SESSION_LATENESS, either API) takes the call iff its
    configuration has parallelism > 1; one of parallelism 1 and every count handle return
    FW_E_INVALID.  The rows are folded when they are pushed, in buffer position order, under the
    handle's watermark at that point of the stream; a count above seg_len is clamped (the overflow
@@ -857,6 +875,14 @@ int fw_host_count_step(const fw_config* cfg, int64_t index, int64_t* slice, int3
    configuration fw_create would reject, FW_E_CAPACITY when a new session does not fit. */
 int fw_host_session_add(const fw_config* cfg, int64_t watermark, int64_t ts, int64_t value, int64_t* starts, int64_t* ends,
                         int64_t* accs, int32_t* n, int32_t capacity, int32_t* outcome);
+/* v11 (additive): the same for a FW_WIN_SESSION_LATENESS configuration.  The drop test is the
+   window's cleanup time (ts + size_ms - 1 + allowed_lateness_ms <= watermark, for an element that
+   intersects nothing).  *outcome = 1 kept, 0 dropped; *fired_index is the list index of the session
+   the element produced if that session has end - 1 <= watermark -- the caller emits it at once --
+   and -1 otherwise.  FW_E_INVALID for a configuration of another window kind.  It runs the routine
+   the device code calls. */
+int fw_host_session_add_late(const fw_config* cfg, int64_t watermark, int64_t ts, int64_t value, int64_t* starts, int64_t* ends,
+                             int64_t* accs, int32_t* n, int32_t capacity, int32_t* outcome, int32_t* fired_index);
 /* v11 (additive): the same for a FW_WIN_SESSION_DYNAMIC configuration: the element's window is
    [ts, ts + gap) with its own gap.  Same lists, outcomes and capacity behaviour; FW_E_INVALID also
    for a gap outside (0, size_ms] and for a configuration of another window kind.  It runs the

@@ -9,7 +9,8 @@ tile).  Push s carries event times in [10 s * s, 10 s * (s + 1)) and is followed
 the advance and the (stream-ordered) result reset; it is timed on the host around a handle sync.
 Prints one JSON line per stream.
 
-    python tools/session_window_bench.py [--rows N] [--warmup 5] [--steps 20] [--streams uniform,zipf,hot] [--sql AGGS | --dynamic-gap]
+    python tools/session_window_bench.py [--rows N] [--warmup 5] [--steps 20] [--streams uniform,zipf,hot]
+                                         [--sql AGGS | --dynamic-gap | --lateness MS [--late-share F]]
 
 --sql AGGS runs the same streams through a SQL session handle (the SESSION window TVF aggregate,
 BINROW_BIGINT keys) instead: AGGS is a comma-separated aggregate list over two value columns, a
@@ -23,6 +24,14 @@ which the eight-word kernels carry.
 a dynamic-gap handle (EventTimeSessionWindows.withDynamicGap, max gap 3 s) whose gap column is the
 constant 3 s, and through one whose gaps are drawn from 0.5 / 1 / 2 / 3 s.  The dynamic fold reads
 8 B more per event (the gap column); the lines carry "gaps": "static" / "constant" / "mixed".
+
+--lateness MS runs the streams through a handle with that allowed lateness (FW_WIN_SESSION_LATENESS;
+0 is allowed) and makes a share --late-share (default 1/6) of every push's rows late candidates:
+their event times lie 3 to 8 s behind the push's span, behind the watermark of the push before.  A
+candidate's key run leaves the parallel path for the arrival-order walk of one lane; with a lateness
+that reaches back (10 s: every candidate is kept) most of them fire a retained session again, with
+0 the ones that touch no open session are dropped.  The lines carry "lateness_ms", "late_share" and
+the rows dropped.
 """
 import argparse
 import json
@@ -58,11 +67,12 @@ _SQL_AGGS = {"COUNT(*)": ("COUNT_STAR", 0, "BIGINT"), "COUNT(b)": ("COUNT", 1, "
              "SUM(b)": ("SUM", 1, "DOUBLE"), "AVG(b)": ("AVG", 1, "DOUBLE")}
 
 
-def run(kind, rows, warmup, steps, n_keys=10**6, sql=None, gaps=None):
-    """``gaps``: None = the static handle; "constant" / "mixed" = a dynamic-gap handle"""
+def run(kind, rows, warmup, steps, n_keys=10**6, sql=None, gaps=None, lateness=None, late_share=0.0):
+    """``gaps``: None = the static handle; "constant" / "mixed" = a dynamic-gap handle;
+    ``lateness``: not None = a handle with that allowed lateness and ``late_share`` late candidates"""
     import torch
     from flink_amd import abi
-    from flink_amd.datastream import DynamicSessionWindowOperator, SessionWindowOperator
+    from flink_amd.datastream import DynamicSessionWindowOperator, LateSessionWindowOperator, SessionWindowOperator
     from flink_amd.table import SessionWindowAggOperator
     dev = torch.device("cuda", 0)
     if kind == "hot":  # a step of the hot key takes far longer than the others: fewer of them
@@ -73,6 +83,9 @@ def run(kind, rows, warmup, steps, n_keys=10**6, sql=None, gaps=None):
     elif gaps:
         op = DynamicSessionWindowOperator(GAP_MS, ("sum", "LONG"), state_capacity=1 << 21, max_batch_rows=rows,
                                           output_capacity=1 << 22).open()
+    elif lateness is not None:
+        op = LateSessionWindowOperator(GAP_MS, lateness, ("sum", "LONG"), state_capacity=1 << 21, max_batch_rows=rows,
+                                       output_capacity=1 << 23).open()
     else:
         op = SessionWindowOperator(GAP_MS, ("sum", "LONG"), state_capacity=1 << 21, max_batch_rows=rows,
                                    output_capacity=1 << 22).open()
@@ -92,6 +105,11 @@ def run(kind, rows, warmup, steps, n_keys=10**6, sql=None, gaps=None):
             gcol = torch.tensor(MIXED_GAPS_MS, dtype=torch.int64, device=dev)[
                 torch.randint(0, len(MIXED_GAPS_MS), (rows,), generator=g, device=dev)]
         offs = torch.randint(0, SPAN_MS, (rows,), device=dev, dtype=torch.int64)
+        if lateness is not None and late_share > 0:  # late candidates: 3 to 8 s behind the push's span
+            g = torch.Generator(device=dev)
+            g.manual_seed(5)
+            back = torch.rand(rows, generator=g, device=dev) < late_share
+            offs = torch.where(back, -GAP_MS - offs % 5000, offs)
         torch.cuda.synchronize()
         ms = []
         for s in range(warmup + steps):
@@ -119,6 +137,9 @@ def run(kind, rows, warmup, steps, n_keys=10**6, sql=None, gaps=None):
         elif gaps:
             window = "EventTimeSessionWindows.withDynamicGap(<= 3s).sum LONG"
             extra = {"gaps": gaps}
+        elif lateness is not None:
+            window = "EventTimeSessionWindows.withGap(3s).allowedLateness.sum LONG"
+            extra = {"lateness_ms": lateness, "late_share": round(late_share, 4)}
         return {"tool": "session_window_bench", "stream": kind, "window": window, **extra,
                 "rows_per_push": rows, "keys": 1 if kind == "hot" else n_keys, "warmup": warmup, "steps": steps,
                 "ms_per_push_median": round(float(np.median(ms)), 4), "ms_per_push_min": round(float(ms.min()), 4),
@@ -137,14 +158,18 @@ def main():
     ap.add_argument("--streams", default="uniform,zipf,hot")
     ap.add_argument("--sql", default=None, metavar="AGGS", help="run a SQL session handle with this aggregate list")
     ap.add_argument("--dynamic-gap", action="store_true", help="static, constant-gap dynamic and mixed-gap dynamic handles in turn")
+    ap.add_argument("--lateness", type=int, default=None, metavar="MS", help="run a handle with this allowed lateness")
+    ap.add_argument("--late-share", type=float, default=1.0 / 6, help="with --lateness: the share of late candidates per push")
     a = ap.parse_args()
     if a.sql and a.dynamic_gap:
         ap.error("--dynamic-gap is a DataStream run (no --sql)")
+    if a.lateness is not None and (a.sql or a.dynamic_gap):
+        ap.error("--lateness is a static-gap DataStream run (no --sql, no --dynamic-gap)")
     if a.sql and any(x not in _SQL_AGGS for x in a.sql.split(",")):
         ap.error("--sql takes a comma-separated list out of " + ", ".join(_SQL_AGGS))
     for kind in a.streams.split(","):
         if not a.dynamic_gap:
-            print(json.dumps(run(kind, a.rows, a.warmup, a.steps, sql=a.sql)), flush=True)
+            print(json.dumps(run(kind, a.rows, a.warmup, a.steps, sql=a.sql, lateness=a.lateness, late_share=a.late_share)), flush=True)
             continue
         for _ in range(2):      # alternating: static, constant, mixed, twice
             for gaps in (None, "constant", "mixed"):
