@@ -1757,6 +1757,45 @@ int fw_push_device_packed_segments(fw_handle* h, int32_t n_segs, int64_t seg_len
     return push(h, n, d_rows, d_rows + 1, nullptr, vals, nullptr, d_seg_counts, seg_len, row_words);
 }
 
+// The count handle's own segment pushes: count rows have no timestamp, so the two entries above keep
+// refusing them.  Only a count handle of parallelism > 1 has an exchange in front of it.
+#define CW_ONLY_EXCHANGE(h, name)                                                                                  \
+    if ((h)->sw.on) return fail(FW_E_INVALID, name ": not for session windows (count windows only)");              \
+    if (!(h)->cw.on) return fail(FW_E_INVALID, name ": not for time windows (count windows only)");                \
+    if ((h)->cfg.parallelism <= 1)                                                                                 \
+        return fail(FW_E_INVALID, name ": a count handle of parallelism 1 has no keyBy exchange in front of it")
+
+int fw_push_device_count_segments(fw_handle* h, int32_t n_segs, int64_t seg_len, const int64_t* d_seg_counts,
+                                  const int64_t* d_key, const int32_t* d_key_hash, const void* d_value) {
+    if (!h) return fail(FW_E_INVALID, "null handle");
+    CW_ONLY_EXCHANGE(h, "fw_push_device_count_segments");
+    if (n_segs < 0 || seg_len < 1 || (n_segs > 0 && !d_seg_counts)) return fail(FW_E_INVALID, "bad segments");
+    if (seg_len >= (1ll << 32) || (int64_t)n_segs * seg_len >= (1ll << 32))
+        return fail(FW_E_INVALID, "arrival ordinals need n_segs * seg_len < 2^32 rows per call");
+    if (n_segs == 0) return FW_OK;
+    if (!d_key) return fail(FW_E_INVALID, "null key column");
+    if (h->cfg.key_hash == FW_KEYHASH_PRECOMPUTED && !d_key_hash) return fail(FW_E_INVALID, "key_hash column required");
+    if (h->nv > 0 && !d_value) return fail(FW_E_INVALID, "value column %d is NULL", h->slot_col[0]);
+    return cw_push_segments(&h->cw, n_segs, seg_len, d_seg_counts, d_key,
+                            h->cfg.key_hash == FW_KEYHASH_PRECOMPUTED ? d_key_hash : nullptr,
+                            h->nv > 0 ? (const uint64_t*)d_value : nullptr, 1);
+}
+
+int fw_push_device_count_packed_segments(fw_handle* h, int32_t n_segs, int64_t seg_len, const int64_t* d_seg_counts,
+                                         const int64_t* d_rows, int32_t row_words) {
+    if (!h) return fail(FW_E_INVALID, "null handle");
+    CW_ONLY_EXCHANGE(h, "fw_push_device_count_packed_segments");
+    if (n_segs < 0 || seg_len < 1 || (n_segs > 0 && !d_seg_counts)) return fail(FW_E_INVALID, "bad segments");
+    if (row_words != 2 + h->cfg.n_value_cols) return fail(FW_E_INVALID, "row_words %d != 2 + value columns", row_words);
+    if (h->cfg.key_hash == FW_KEYHASH_PRECOMPUTED) return fail(FW_E_INVALID, "packed rows carry no key-hash column");
+    if (seg_len >= (1ll << 32) || (int64_t)n_segs * seg_len >= (1ll << 32))
+        return fail(FW_E_INVALID, "arrival ordinals need n_segs * seg_len < 2^32 rows per call");
+    if (n_segs == 0) return FW_OK;
+    if (!d_rows) return fail(FW_E_INVALID, "null rows");
+    // (key, ts, value): word 1 is not read; a count aggregate reads no value word either
+    return cw_push_segments(&h->cw, n_segs, seg_len, d_seg_counts, d_rows, nullptr, (const uint64_t*)d_rows + 2, row_words);
+}
+
 int fw_advance(fw_handle* h, int64_t watermark) {
     if (!h) return fail(FW_E_INVALID, "null handle");
     if (h->cw.on) {  // CountTrigger.onEventTime: CONTINUE -- the watermark is recorded, nothing fires

@@ -104,6 +104,13 @@ int cw_allocate(CountOp* op, hipStream_t stream, Ctrl* ctrl);
 void cw_free(CountOp* op);
 // folds n rows into the state and appends the fired rows (stream-ordered, asynchronous)
 int cw_push(CountOp* op, int64_t n, const int64_t* d_key, const int32_t* d_khash, const uint64_t* d_val);
+// The same over a padded exchange receive buffer (the device form, behind the N > 1 keyBy exchange):
+// n_segs segments of seg_len rows, segment s holding min(d_seg_counts[s], seg_len) live rows in front
+// of its padding; row i has its key at d_key[i * stride], its value at d_val[i * stride] (1: columns,
+// row_words: packed rows) and its hash at d_khash[i].  Arrival order is buffer position order; a
+// fired row's ordinal is push_seq << 32 | the triggering element's position in the buffer.
+int cw_push_segments(CountOp* op, int32_t n_segs, int64_t seg_len, const int64_t* d_seg_counts, const int64_t* d_key,
+                     const int32_t* d_khash, const uint64_t* d_val, int32_t stride);
 int cw_snapshot(CountOp* op, int32_t key_group, void* buf, int64_t capacity, int64_t* size);
 int cw_restore(CountOp* op, bool key_group, const void* buf, int64_t size);
 

@@ -4,6 +4,9 @@
 // partition (fd_partition, fw_folded.hip: four stream-ordered launches), then
 //   k_cw_fold     one workgroup per superbucket walks its segment in arrival order, a tile at a time
 // No workgroup waits on another: the only cross-workgroup traffic is counters (atomic adds).
+// Behind the N > 1 keyBy exchange (cw_push_segments) the partition is fd_partition_segments over the
+// padded receive buffer and the fold the strided instance k_cw_fold<true>; buffer position order is
+// the arrival order.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -31,8 +34,15 @@ struct CwFoldArgs {
     int64_t* out_ord;
     int64_t out_cap;
     int64_t ord_base;  // push_seq << 32 | row offset of this launch within its call
+    int32_t stride;    // the device form (DEV): key and value word of row r at key[r * stride], val[r * stride]
 };
 
+// DEV: the device form, behind the N > 1 keyBy exchange (cw_push_segments): perm / seg name the live
+// rows fd_partition_segments selected from a padded receive buffer -- a padding row is in no segment,
+// so it is never read -- and a row's words are strided (1: columns, row_words: packed rows).  Everything
+// else is the one body; the instance without DEV is the one a direct push launches.
+#define CW_AT(row) (DEV ? (size_t)(row) * (size_t)a.stride : (row))
+template <bool DEV>
 __global__ __launch_bounds__(CW_TILE) void k_cw_fold(CwFoldArgs a) {
     __shared__ uint64_t sk[CW_TILE];     // sorted keys
     __shared__ uint32_t sp[CW_TILE];     // their positions in the tile (arrival order)
@@ -64,9 +74,9 @@ __global__ __launch_bounds__(CW_TILE) void k_cw_fold(CwFoldArgs a) {
         }
         if (t < nt) {
             const uint32_t row = a.perm[base + t];
-            uint64_t v = a.is_count ? 1ull : a.val[row];
+            uint64_t v = a.is_count ? 1ull : a.val[CW_AT(row)];
             if (dbl_cmp) v = (uint64_t)dkey(v);
-            sk[t] = (uint64_t)a.key[row];
+            sk[t] = (uint64_t)a.key[CW_AT(row)];
             sp[t] = (uint32_t)t;
             pv[t] = v;
             prow[t] = row;
@@ -329,18 +339,24 @@ void cw_free(CountOp* op) {
     hipFree(op->out_null);
 }
 
-int cw_push(CountOp* op, int64_t n, const int64_t* d_key, const int32_t* d_khash, const uint64_t* d_val) {
+// the folds of one call: n rows at d_key[i * stride], d_val[i * stride], split into launches of
+// part.cap_rows rows by position.  d_seg_counts: the rows are a padded buffer of segments of seg_len
+// rows and the fold is the device form; else a direct push (stride 1)
+static int cw_fold_call(CountOp* op, int64_t n, const int64_t* d_key, const int32_t* d_khash, const uint64_t* d_val, int32_t stride,
+                        const int64_t* d_seg_counts, int64_t seg_len) {
     if (n >= (1ll << 32) || op->push_seq >= (1ll << 30))
         return set_error(FW_E_INVALID, "arrival ordinals need < 2^32 rows per call and < 2^30 calls");
     hipStream_t s = op->stream;
     const int64_t cap_rows = op->part.cap_rows;
     for (int64_t o = 0; o < n; o += cap_rows) {
         const int64_t m = std::min(cap_rows, n - o);
-        const int rc = fd_partition(op->part, op->ks, op->ctrl, s, m, d_key + o, d_khash ? d_khash + o : nullptr);
+        const int rc = d_seg_counts ? fd_partition_segments(op->part, op->ks, op->ctrl, s, m, d_key + o * stride, stride,
+                                                            d_khash ? d_khash + o : nullptr, d_seg_counts, seg_len, o)
+                                    : fd_partition(op->part, op->ks, op->ctrl, s, m, d_key + o, d_khash ? d_khash + o : nullptr);
         if (rc) return rc;
         CwFoldArgs fa{};
-        fa.key = d_key + o;
-        fa.val = op->is_count ? nullptr : d_val + o;
+        fa.key = d_key + o * stride;
+        fa.val = op->is_count ? nullptr : d_val + o * stride;
         fa.perm = op->part.perm;
         fa.seg = op->part.seg;
         fa.d = op->d;
@@ -357,11 +373,22 @@ int cw_push(CountOp* op, int64_t n, const int64_t* d_key, const int32_t* d_khash
         fa.out_ord = op->out_ord;
         fa.out_cap = op->out_cap;
         fa.ord_base = (op->push_seq << 32) + o;
-        hipLaunchKernelGGL(k_cw_fold, dim3(op->ks.n_sb), dim3(CW_TILE), 0, s, fa);
+        fa.stride = stride;
+        if (d_seg_counts) hipLaunchKernelGGL(k_cw_fold<true>, dim3(op->ks.n_sb), dim3(CW_TILE), 0, s, fa);
+        else hipLaunchKernelGGL(k_cw_fold<false>, dim3(op->ks.n_sb), dim3(CW_TILE), 0, s, fa);
         FD_TRY(hipGetLastError());
     }
     op->push_seq++;
     return FW_OK;
+}
+
+int cw_push(CountOp* op, int64_t n, const int64_t* d_key, const int32_t* d_khash, const uint64_t* d_val) {
+    return cw_fold_call(op, n, d_key, d_khash, d_val, 1, nullptr, 0);
+}
+
+int cw_push_segments(CountOp* op, int32_t n_segs, int64_t seg_len, const int64_t* d_seg_counts, const int64_t* d_key,
+                     const int32_t* d_khash, const uint64_t* d_val, int32_t stride) {
+    return cw_fold_call(op, (int64_t)n_segs * seg_len, d_key, d_khash, d_val, stride, d_seg_counts, seg_len);
 }
 
 // ---- checkpoint: the library's own blob.  Entries are (key, count, key group << 32 | sub-bucket,
@@ -390,6 +417,10 @@ int cw_snapshot(CountOp* op, int32_t key_group, void* buf, int64_t capacity, int
     const size_t words = (size_t)(sb1 - sb0) * op->cap_e * pwe;
     std::vector<uint64_t> tab(words);
     FD_TRY(hipMemcpy(tab.data(), op->table + (size_t)sb0 * op->cap_e * pwe, words * 8, hipMemcpyDeviceToHost));
+    // the watermark of record: fw_advance_device leaves it in Ctrl::cur only, fw_advance in the host mirror only
+    int64_t dev_wm = INT64_MIN;
+    FD_TRY(hipMemcpy(&dev_wm, &op->ctrl->cur, sizeof dev_wm, hipMemcpyDeviceToHost));
+    const int64_t watermark = std::max(op->watermark, dev_wm);
     std::vector<uint64_t> ent;
     int64_t n = 0;
     for (int sb = sb0; sb < sb1; sb++)
@@ -406,7 +437,7 @@ int cw_snapshot(CountOp* op, int32_t key_group, void* buf, int64_t capacity, int
     *size = need;
     if (!buf) return FW_OK;
     if (capacity < need) return set_error(FW_E_INVALID, "snapshot buffer too small (%lld < %lld)", (long long)capacity, (long long)need);
-    CwHeader hd{key_group >= 0 ? CW_KG_MAGIC : CW_MAGIC, op->push_seq, op->watermark, op->d.size, op->d.slide, op->d.op, op->vtype,
+    CwHeader hd{key_group >= 0 ? CW_KG_MAGIC : CW_MAGIC, op->push_seq, watermark, op->d.size, op->d.slide, op->d.op, op->vtype,
                 ks.hash_kind, ks.max_p, op->d.R, key_group, L, 0, n};
     memcpy(buf, &hd, sizeof hd);
     if (!ent.empty()) memcpy((char*)buf + sizeof hd, ent.data(), ent.size() * 8);

@@ -13,3 +13,4 @@ from .dynamic_session_window_operator import is_gpu_eligible as is_dynamic_sessi
 from .late_session_window_operator import LateSessionWindowOperator  # noqa: F401
 from .late_session_window_operator import is_gpu_eligible as is_late_session_window_gpu_eligible  # noqa: F401
 from .session_exchange import SessionExchangeStep  # noqa: F401
+from .count_exchange import CountExchangeStep  # noqa: F401

@@ -153,6 +153,20 @@ class CountWindowOperator:
             raise ValueError("a STRING-keyed operator interns its keys on the host (process_batch)")
         self.handle.push_device(keys, None, [values], key_hashes)
 
+    def process_segments_device(self, seg_counts, keys, values, key_hashes=None):
+        """Behind the N > 1 keyBy exchange: a padded receive buffer as columns, len(seg_counts)
+        segments, segment s holding seg_counts[s] live rows in front of its padding.  The elements
+        arrive in buffer position order; ``values`` may be None for a count."""
+        if self.key_type == "STRING":
+            raise ValueError("a STRING-keyed operator interns its keys on the host (process_batch)")
+        self.handle.push_device_count_segments(seg_counts, keys, values, key_hashes)
+
+    def process_packed_segments_device(self, seg_counts, rows, row_words):
+        """The same over the exchange's packed rows (key, ts, value); the ts word is not read."""
+        if self.key_type == "STRING":
+            raise ValueError("a STRING-keyed operator interns its keys on the host (process_batch)")
+        self.handle.push_device_count_packed_segments(seg_counts, rows, row_words)
+
     def collect(self):
         """The rows fired since the last call, in the reference's emission order."""
         r = self.handle.results(reset=True)
@@ -166,6 +180,15 @@ class CountWindowOperator:
     def process_watermark(self, watermark):
         """CountTrigger.onEventTime returns CONTINUE: the watermark is recorded and nothing fires."""
         self.handle.advance(watermark)
+        return self._no_rows()
+
+    def process_watermark_device(self, wm_tensor):
+        """The watermark in device memory (the exchange's device valve): recorded on the device,
+        nothing fires, no host wait."""
+        self.handle.advance_device(wm_tensor)
+        return self._no_rows()
+
+    def _no_rows(self):
         e = np.empty(0, np.int64)
         return {"key": np.empty(0, object) if self.key_type == "STRING" else e, "value": e, "timestamp": e,
                 "window_start": e, "window_end": e, "trigger_ord": e}

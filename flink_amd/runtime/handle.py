@@ -232,6 +232,34 @@ class WindowAggHandle:
         self.push_seq += 1
         self._end_read(cur)
 
+    def push_device_count_segments(self, seg_counts, keys, values=None, key_hashes=None):
+        """A count-window handle of parallelism > 1: a padded exchange receive buffer as columns,
+        len(seg_counts) segments of keys.numel() // len(seg_counts) rows; segment s holds
+        seg_counts[s] live rows (a device int64 tensor) in front of its padding.  ``values``: the one
+        value column (None for a count aggregate).  Arrival order is buffer position order."""
+        p = seg_counts.numel()
+        n = keys.numel()
+        if p == 0 or n == 0:
+            return
+        cur = self._begin_read(keys.device)
+        check(lib().fw_push_device_count_segments(self._h, p, n // p, seg_counts.data_ptr(), keys.data_ptr(),
+                                                  key_hashes.data_ptr() if key_hashes is not None else None,
+                                                  values.data_ptr() if values is not None else None))
+        self.push_seq += 1
+        self._end_read(cur)
+
+    def push_device_count_packed_segments(self, seg_counts, rows, row_words):
+        """A count-window handle of parallelism > 1: the packed padded exchange receive buffer,
+        rows of (key, ts, value) words -- the ts word is not read."""
+        p = seg_counts.numel()
+        if p == 0 or rows.numel() == 0:
+            return
+        cur = self._begin_read(rows.device)
+        check(lib().fw_push_device_count_packed_segments(self._h, p, rows.numel() // (p * row_words), seg_counts.data_ptr(),
+                                                         rows.data_ptr(), int(row_words)))
+        self.push_seq += 1
+        self._end_read(cur)
+
     # ---- progress / output
     def advance(self, wm):
         check(lib().fw_advance(self._h, int(wm)))

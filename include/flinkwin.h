@@ -103,7 +103,9 @@ typedef enum {
        max(0, c - size), window_end = c, the key's element count at the fire, and first_ord (below).
        The async / device / segment result calls, the segment and key-row pushes, fw_late_records,
        fw_first_element_events, the heap-format and fw_ds_* key-group calls and the profiling calls
-       return FW_E_INVALID on a count handle.  A full key table raises FW_ERRF_STATE. */
+       return FW_E_INVALID on a count handle.  A full key table raises FW_ERRF_STATE.
+       Behind the N > 1 keyBy exchange a count handle of parallelism > 1 has segment pushes of its
+       own, fw_push_device_count_segments and fw_push_device_count_packed_segments (new symbols). */
     FW_WIN_COUNT = 3,
     /* v11 (additive), DataStream only: EventTimeSessionWindows.withGap(gap) with EventTimeTrigger, no
        evictor, allowedLateness 0.  size_ms carries the gap (0 < gap <= 2^40); slide_ms, offset_ms and
@@ -427,7 +429,8 @@ int fw_push_device_key_rows(fw_handle* h, int64_t n, const int64_t* d_key_row_of
    padding and is never read.  Otherwise as fw_push_device.
    A session handle (FW_WIN_SESSION, FW_WIN_SESSION_DYNAMIC, FW_WIN_SESSION_LATENESS, either API) takes the call iff its
    configuration has parallelism > 1; one of parallelism 1 and every count handle return
-   FW_E_INVALID.  The rows are folded when they are pushed, in buffer position order, under the
+   FW_E_INVALID (a count handle's segment pushes are fw_push_device_count_segments and
+   fw_push_device_count_packed_segments, below).  The rows are folded when they are pushed, in buffer position order, under the
    handle's watermark at that point of the stream; a count above seg_len is clamped (the overflow
    went to the sender's spill); a padding row is never read, whatever it holds, so it raises
    neither FW_ERRF_KEYGROUP nor FW_ERRF_GAP, while a live row of a foreign key group is dropped and
@@ -448,6 +451,27 @@ int fw_push_device_segments(fw_handle* h, int32_t n_segs, int64_t seg_len, const
    (key, ts, field, gap). */
 int fw_push_device_packed_segments(fw_handle* h, int32_t n_segs, int64_t seg_len, const int64_t* d_seg_counts,
                                    const int64_t* d_rows, int32_t row_words);
+
+/* v11 (additive: new symbols), count windows behind the N > 1 keyBy exchange.  A count handle
+   (FW_WIN_COUNT) keeps refusing the two entries above -- its rows have no timestamp -- and has these
+   instead, iff its configuration has parallelism > 1 (only such a handle has an exchange in front of
+   it); a count handle of parallelism 1 and every other kind of handle return FW_E_INVALID.
+   The buffer is the padded receive buffer of the exchange: n_segs segments of seg_len rows, segment
+   s holding min(d_seg_counts[s], seg_len) live rows in front of its padding (device int64).
+   fw_push_device_count_segments takes columns: d_key, d_key_hash (FW_KEYHASH_PRECOMPUTED only, else
+   NULL) and the one value column d_value of n_segs * seg_len 8-byte words (NULL for COUNT_STAR).
+   fw_push_device_count_packed_segments takes the exchange's packed rows (key, ts, value):
+   row_words must be 2 + n_value_cols = 3, word 1 is not read; not for FW_KEYHASH_PRECOMPUTED.
+   Arrival order is the buffer's position order: segment by segment (sender by sender), each in
+   its own order.  A padding row is never read, whatever it holds: it counts for no key and raises
+   nothing; a live row of a foreign key group is dropped and raises FW_ERRF_KEYGROUP.  push_seq counts
+   the call like any other push, and a fired row's first_ord is push_seq << 32 | the position of the
+   triggering element in the pushed buffer, segment * seg_len + index; n_segs * seg_len must be below
+   2^32.  FW_ERRF_STATE and FW_ERRF_OUTPUT as on fw_push_device. */
+int fw_push_device_count_segments(fw_handle* h, int32_t n_segs, int64_t seg_len, const int64_t* d_seg_counts,
+                                  const int64_t* d_key, const int32_t* d_key_hash, const void* d_value);
+int fw_push_device_count_packed_segments(fw_handle* h, int32_t n_segs, int64_t seg_len, const int64_t* d_seg_counts,
+                                         const int64_t* d_rows, int32_t row_words);
 
 /* ---- progress / output --------------------------------------------------------------- */
 /* Late side output of a DataStream operator with late_side_output (WindowOperator.sideOutput,
