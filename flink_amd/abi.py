@@ -28,6 +28,7 @@ WIN_COUNT = 3  # DataStream countWindow: size_ms / slide_ms carry element counts
 WIN_SESSION = 4  # DataStream EventTimeSessionWindows.withGap: size_ms carries the gap
 WIN_SESSION_DYNAMIC = 5  # ... withDynamicGap: value column 1 carries each element's gap, size_ms the largest allowed
 WIN_SESSION_LATENESS = 6  # ... withGap and allowedLateness >= 0: fired sessions are retained and re-fire on late elements
+WIN_SESSION_DYNAMIC_LATENESS = 7  # ... withDynamicGap and allowedLateness >= 0: both of the above
 # fw_agg_kind
 AGG_COUNT_STAR = 0
 AGG_COUNT = 1

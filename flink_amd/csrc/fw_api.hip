@@ -538,8 +538,8 @@ int validate_and_plan(fw_handle* h) {
         h->stage_cap = c.max_batch_rows;
         return FW_OK;
     }
-    if (c.window_kind == FW_WIN_SESSION || c.window_kind == FW_WIN_SESSION_DYNAMIC ||
-        c.window_kind == FW_WIN_SESSION_LATENESS) {  // session windows: a plan of their own (fw_session.hip)
+    if (c.window_kind == FW_WIN_SESSION || c.window_kind == FW_WIN_SESSION_DYNAMIC || c.window_kind == FW_WIN_SESSION_LATENESS ||
+        c.window_kind == FW_WIN_SESSION_DYNAMIC_LATENESS) {  // session windows: a plan of their own (fw_session.hip)
         int rc = sw_plan(c, &h->sw);
         if (rc) return rc;
         h->ks = h->sw.ks;
@@ -3702,6 +3702,33 @@ int fw_host_session_add_gap(const fw_config* cfg, int64_t watermark, int64_t ts,
     for (int32_t i = 0; i < *n; i++) accs[i] = (int64_t)session_result(d, (uint64_t)accs[i]);
     if (r < 0) return fail(FW_E_CAPACITY, "the session list is full (%d sessions)", capacity);
     *outcome = r;
+    return FW_OK;
+}
+
+int fw_host_session_add_gap_late(const fw_config* cfg, int64_t watermark, int64_t ts, int64_t gap, int64_t value, int64_t* starts,
+                                 int64_t* ends, int64_t* accs, int32_t* n, int32_t capacity, int32_t* outcome,
+                                 int32_t* fired_index) {
+    if (!cfg || !n || !outcome || !fired_index || (capacity > 0 && (!starts || !ends || !accs))) return fail(FW_E_INVALID, "null argument");
+    if (cfg->window_kind != FW_WIN_SESSION_DYNAMIC_LATENESS)
+        return fail(FW_E_INVALID, "fw_host_session_add_gap_late needs a FW_WIN_SESSION_DYNAMIC_LATENESS configuration");
+    fw_handle h;
+    h.cfg = *cfg;
+    const int rc = validate_and_plan(&h);
+    if (rc) return rc;
+    const SessionDesc& d = h.sw.d;
+    if (gap < 1 || gap > d.gap)
+        return fail(FW_E_INVALID, "session gap %lld is outside (0, size_ms = %lld]", (long long)gap, (long long)d.gap);
+    if (*n < 0 || *n > capacity) return fail(FW_E_INVALID, "bad session count %d (capacity %d)", *n, capacity);
+    for (int32_t i = 0; i < *n; i++) accs[i] = (int64_t)session_word_of_result(d, (uint64_t)accs[i]);
+    const uint64_t word = session_word(d, (uint64_t)value);
+    int32_t at = -1;
+    const int r = session_add<1, true>(gap, d.ops, watermark, ts, &word, 1, starts, ends, (uint64_t*)accs, 1, 1, n, capacity,
+                                       h.sw.lateness, &at);
+    for (int32_t i = 0; i < *n; i++) accs[i] = (int64_t)session_result(d, (uint64_t)accs[i]);
+    if (r < 0) return fail(FW_E_CAPACITY, "the session list is full (%d sessions)", capacity);
+    *outcome = r;
+    // EventTimeTrigger.onElement (recalled, parity unpinned): the session the element produced fires at once if its timer has passed
+    *fired_index = r == 1 && session_due(ends[at], watermark) ? at : -1;
     return FW_OK;
 }
 

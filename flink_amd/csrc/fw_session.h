@@ -21,6 +21,8 @@
 // unpinned: DynamicEventTimeSessionWindows.assignWindows) differs only in the element's window,
 // [ts, ts + g) with g = extractor.extract(element) > 0: the gap arrives as a value column.  Window
 // ends are then no longer ordered like the starts -- a window may lie inside an earlier, longer one.
+// With an allowed lateness on top (FW_WIN_SESSION_DYNAMIC_LATENESS; recalled, parity unpinned) the
+// lateness rules below hold with g in place of the gap wherever the element's own window is named.
 //
 // This header holds the interval arithmetic the kernels and fw_host_session_add share (FW_HD), the
 // per-handle state of a session operator (SessionOp) and the entry points fw_api.hip dispatches to.
@@ -184,6 +186,7 @@ constexpr int64_t SW_SIDE_WORDS = 4;               // late side-output row: key,
 struct SessionOp {
     bool on = false;
     bool dyn = false;         // FW_WIN_SESSION_DYNAMIC: value column 1 is the row's gap, d.gap the largest allowed
+    // (FW_WIN_SESSION_DYNAMIC_LATENESS sets both dyn and late)
     // Ctrl::cur in device memory is the watermark of record (a handle of parallelism > 1 that was
     // advanced from the device, sw_advance_device): every fold and advance reads it there, and the
     // host's mirror (fw_handle::host_cur) is only a lower bound until a reader synchronises

@@ -16,12 +16,14 @@
 // live rows fd_partition_segments selected, and the watermark from Ctrl::cur; k_sw_advance<NW, true>
 // reads Ctrl::cur behind the one-thread k_sw_raise.  The instances above are unchanged and are what a
 // direct push of a host-watermark handle launches.
-// An allowed lateness (FW_WIN_SESSION_LATENESS) is a last template argument of both kernels, NW = 1 and
-// a static gap only: k_sw_fold<1, false, DEV, true> re-fires a retained session from the arrival-order
+// An allowed lateness (FW_WIN_SESSION_LATENESS) is a last template argument of both kernels, NW = 1
+// only: k_sw_fold<1, false, DEV, true> re-fires a retained session from the arrival-order
 // walk of a late-candidate run, k_sw_advance<1, DEV, true> fires the sessions whose timer lies between
 // the previous watermark and the new one and removes the ones past their cleanup time (in the device
 // form behind k_sw_raise_late, which keeps the previous watermark).  Every lateness line sits behind
 // that argument; the instances above compile to what they compiled to without it.
+// Both together (FW_WIN_SESSION_DYNAMIC_LATENESS) are k_sw_fold<1, true, DEV, true>: the late-candidate
+// tests take the row's own gap, and the advance is the lateness one, which reads no gap.
 // No workgroup waits on another: the only cross-workgroup traffic is counters (atomic adds).
 #include <hip/hip_runtime.h>
 
@@ -159,17 +161,29 @@ __device__ __forceinline__ void sw_row_words(const SwFoldArgs& a, uint32_t row, 
 // over rows + 0, 1, 2 + c a packed one -- and the watermark from a.ctrl->cur, a word no workgroup of
 // a fold launch writes.  Everything else is the one body.  The instances without DEV are the ones a
 // direct push of a host-watermark handle launches; they read neither a.stride nor Ctrl::cur.
-// LATE (NW = 1, static gap): the form with an allowed lateness (FW_WIN_SESSION_LATENESS).  The state
+// LATE (NW = 1): the form with an allowed lateness (FW_WIN_SESSION_LATENESS).  The state
 // then also holds sessions that have fired (end - 1 <= W) until their cleanup time.  A late candidate
 // is the same row as ever, ts + gap - 1 <= W, and its key run takes the same arrival-order walk, where
 // the drop test is the cleanup time and a row whose resulting session has end - 1 <= W emits that
 // session at once (EventTimeTrigger.onElement: FIRE, no purge).  A run without a candidate holds only
 // rows with ts + gap - 1 > W: whatever they merge with, fired sessions included, ends behind the
 // watermark, nothing fires and nothing is dropped, so the result is the union of intervals as before.
+// DYN && LATE (FW_WIN_SESSION_DYNAMIC_LATENESS): every late-candidate test takes the row's own gap g.
+// A run without a candidate then holds only rows with ts + g - 1 > W, so the same holds: whatever they
+// merge with, retained fired sessions included, ends behind the watermark, nothing fires at once and
+// nothing is dropped, and the run keeps the parallel path with the dynamic form's running-maximum cut
+// unchanged.  Ends are not ordered like starts here, so the bounds are kept per row, not per run:
+//   min_fire[sb] is a lower bound of the smallest end among the sessions that have not fired,
+//   min_end[sb]  a lower bound of the smallest end of any held session.
+// A bound that is too high lets k_sw_advance return early past a due timer; too low is only slower.
+// A session that has not fired (end - 1 > W) took its end from a held session that had not fired
+// (>= the old min_fire) or from a row with ts + g - 1 > W, which is no candidate by its own gap and
+// feeds tile_min_fire with its own end ts + g -- a short row inside a long run included, although the
+// run's largest gap would put its timer much later.  Every row feeds tile_min_end with ts + g.
 template <int NW, bool DYN = false, bool DEV = false, bool LATE = false>
 __global__ __launch_bounds__(SW_TILE) void k_sw_fold(SwFoldArgs a) {
     static_assert(!DYN || NW == 1, "the dynamic-gap fold is a DataStream instance");
-    static_assert(!LATE || (NW == 1 && !DYN), "the lateness fold is the static-gap DataStream instance");
+    static_assert(!LATE || NW == 1, "the lateness fold is a DataStream instance");
     constexpr int SWS = sw_stride(NW);   // words per session
     __shared__ uint64_t sk[SW_TILE];     // sorted keys; then the coalesce chunk's keys
     __shared__ int64_t sts[SW_TILE];     // their timestamps; then the chunk's ends
@@ -281,7 +295,7 @@ __global__ __launch_bounds__(SW_TILE) void k_sw_fold(SwFoldArgs a) {
         const bool shead = valid && !slow && (rank == 0 || (DYN ? myts > pmax : myts - sts[t - 1] > gap));
         const bool stail = valid && !slow && (runtail || (DYN ? sts[t + 1] > imax : sts[t + 1] - myts > gap));
         tile_min_end = valid && SW_END < tile_min_end ? SW_END : tile_min_end;
-        if (LATE && valid && !session_late(myts, gap, W) && SW_END < tile_min_fire) tile_min_fire = SW_END;
+        if (LATE && valid && !session_late(myts, DYN ? mygap : gap, W) && SW_END < tile_min_fire) tile_min_fire = SW_END;
         // the sessions the tile can add at most; if they might not fit, the coalesce pass below runs
         // once more in front, only counting (uniform)
         const int may_add = __syncthreads_count(shead || slow);
@@ -567,7 +581,7 @@ __global__ __launch_bounds__(SW_TILE) void k_sw_fold(SwFoldArgs a) {
     if (t == 0 && sts[0] < a.min_end[blockIdx.x]) a.min_end[blockIdx.x] = sts[0];
     if (LATE) {
         // a session that has not fired ends where a held one did or where a row that is no late
-        // candidate does: a candidate's own window ends at or before W + 1
+        // candidate (by its own gap) does: a candidate's own window ends at or before W + 1
         __syncthreads();
         sts[t] = tile_min_fire;
         __syncthreads();
@@ -915,9 +929,24 @@ static int sw_plan_late(const fw_config& c, SessionOp* op) {
     return FW_OK;
 }
 
+// both: EventTimeSessionWindows.withDynamicGap with allowedLateness >= 0.  Everything sw_plan_dyn
+// refuses, with its messages, and the lateness range of sw_plan_late
+static int sw_plan_dyn_late(const fw_config& c, SessionOp* op) {
+    fw_config c0 = c;
+    c0.allowed_lateness_ms = 0;
+    const int rc = sw_plan_dyn(c0, op);
+    if (rc) return rc;
+    if (c.allowed_lateness_ms < 0 || c.allowed_lateness_ms > SW_MAX_GAP)
+        return set_error(FW_E_INVALID, "session windows: allowed_lateness_ms must be in [0, 2^40]");
+    op->late = true;
+    op->lateness = c.allowed_lateness_ms;
+    return FW_OK;
+}
+
 int sw_plan(const fw_config& c, SessionOp* op) {
     const bool dyn = c.window_kind == FW_WIN_SESSION_DYNAMIC;
-    const int prc = c.window_kind == FW_WIN_SESSION_LATENESS ? sw_plan_late(c, op)
+    const int prc = c.window_kind == FW_WIN_SESSION_DYNAMIC_LATENESS ? sw_plan_dyn_late(c, op)
+                    : c.window_kind == FW_WIN_SESSION_LATENESS ? sw_plan_late(c, op)
                     : dyn                                    ? sw_plan_dyn(c, op)
                     : c.api == FW_API_SQL                    ? sw_plan_sql(c, op)
                                                              : sw_plan_ds(c, op);
@@ -947,7 +976,9 @@ int sw_plan(const fw_config& c, SessionOp* op) {
             mix(v);
         if (op->late) {  // a kind and a lateness of its own: the fired sessions of a blob are read off its watermark
             x = 0xcbf29ce484222325ull;
-            for (int64_t v : {(int64_t)c.api, (int64_t)FW_WIN_SESSION_LATENESS, d.gap, op->lateness, (int64_t)d.op, (int64_t)d.vtype,
+            // (with dynamic gaps a kind of its own again: d.gap is then the largest gap)
+            for (int64_t v : {(int64_t)c.api, (int64_t)(op->dyn ? FW_WIN_SESSION_DYNAMIC_LATENESS : FW_WIN_SESSION_LATENESS), d.gap,
+                              op->lateness, (int64_t)d.op, (int64_t)d.vtype,
                               (int64_t)d.is_count, (int64_t)ks.hash_kind, (int64_t)ks.max_p})
                 mix(v);
         }
@@ -1074,8 +1105,14 @@ static int sw_fold_call(SessionOp* op, bool dev, int64_t watermark, int64_t n, c
             fa.out_we = op->out_we;
             fa.out_val = op->out_val[0];
             fa.out_cap = op->out_cap;
-            if (dev) hipLaunchKernelGGL((k_sw_fold<1, false, true, true>), dim3(n_sb), dim3(SW_TILE), 0, s, fa);
-            else hipLaunchKernelGGL((k_sw_fold<1, false, false, true>), dim3(n_sb), dim3(SW_TILE), 0, s, fa);
+            if (op->dyn) {  // (fa.vals[1], the gap column, is filled above)
+                if (dev) hipLaunchKernelGGL((k_sw_fold<1, true, true, true>), dim3(n_sb), dim3(SW_TILE), 0, s, fa);
+                else hipLaunchKernelGGL((k_sw_fold<1, true, false, true>), dim3(n_sb), dim3(SW_TILE), 0, s, fa);
+            } else if (dev) {
+                hipLaunchKernelGGL((k_sw_fold<1, false, true, true>), dim3(n_sb), dim3(SW_TILE), 0, s, fa);
+            } else {
+                hipLaunchKernelGGL((k_sw_fold<1, false, false, true>), dim3(n_sb), dim3(SW_TILE), 0, s, fa);
+            }
         } else if (dev) {
             if (op->dyn) {
                 hipLaunchKernelGGL((k_sw_fold<1, true, true>), dim3(n_sb), dim3(SW_TILE), 0, s, fa);

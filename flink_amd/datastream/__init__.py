@@ -1,5 +1,5 @@
 """DataStream window operators on MI355X: event-time windows (tumbling / sliding + built-in
-sum/min/max), count windows (countWindow) and event-time session windows (static gap, dynamic gap, allowed lateness)."""
+sum/min/max), count windows (countWindow) and event-time session windows (static gap, dynamic gap, allowed lateness, dynamic gap with allowed lateness)."""
 from .windowing import EventTimeTrigger, SlidingEventTimeWindows, TumblingEventTimeWindows  # noqa: F401
 from .windowing import CountEvictor, CountTrigger, GlobalWindows, PurgingTrigger  # noqa: F401
 from .windowing import DynamicEventTimeSessionWindows, EventTimeSessionWindows  # noqa: F401
@@ -12,5 +12,7 @@ from .dynamic_session_window_operator import DynamicSessionWindowOperator  # noq
 from .dynamic_session_window_operator import is_gpu_eligible as is_dynamic_session_window_gpu_eligible  # noqa: F401
 from .late_session_window_operator import LateSessionWindowOperator  # noqa: F401
 from .late_session_window_operator import is_gpu_eligible as is_late_session_window_gpu_eligible  # noqa: F401
+from .late_dynamic_session_window_operator import LateDynamicSessionWindowOperator  # noqa: F401
+from .late_dynamic_session_window_operator import is_gpu_eligible as is_late_dynamic_session_window_gpu_eligible  # noqa: F401
 from .session_exchange import SessionExchangeStep  # noqa: F401
 from .count_exchange import CountExchangeStep  # noqa: F401

@@ -6,7 +6,8 @@ the trigger the default EventTimeTrigger, no evictor, allowedLateness 0, and the
 field aggregation sum / min / max or a count on a LONG / INT / DOUBLE field of (key, field) tuples.
 The job names the largest gap its extractor can return (``max_gap_ms``, at most 2^40): the session
 gap extractor runs on the host, or in the producer of a device batch, and its result arrives as a
-column beside the field.
+column beside the field.  With allowedLateness > 0 the job takes
+late_dynamic_session_window_operator.LateDynamicSessionWindowOperator; this seam keeps refusing it.
 
 Semantics (DynamicEventTimeSessionWindows.assignWindows, then the static path's
 WindowOperator.processElement merging branch, MergingWindowSet.addWindow, TimeWindow.intersects /

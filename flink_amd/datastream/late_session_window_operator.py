@@ -4,8 +4,9 @@ on its eligible subset.
 WindowOperatorBuilder would return this operator iff the assigner is EventTimeSessionWindows with a
 static gap, the trigger the default EventTimeTrigger, no evictor, allowedLateness >= 0, and the
 function a built-in field aggregation sum / min / max or a count on a LONG / INT / DOUBLE field of
-(key, field) tuples.  Dynamic gaps and the SQL SESSION TVF with a lateness stay on the reference
-operator.
+(key, field) tuples.  Dynamic gaps with a lateness have an operator of their own
+(late_dynamic_session_window_operator.py: this seam refuses the assigner); the SQL SESSION TVF with a
+lateness stays on the reference operator.
 
 Semantics (WindowOperator.processElement's merging branch, EventTimeTrigger.onElement, cleanupTime;
 recalled, parity unpinned).  Gap g, lateness L, watermark W:

@@ -1,5 +1,6 @@
 """One subtask of a session-window operator of parallelism > 1 behind its keyBy exchange: the step
-driver of SessionWindowOperator, DynamicSessionWindowOperator and the SQL SessionWindowAggOperator,
+driver of SessionWindowOperator, DynamicSessionWindowOperator, their lateness forms
+(LateSessionWindowOperator, LateDynamicSessionWindowOperator) and the SQL SessionWindowAggOperator,
 as TwoPhaseWindowAgg is the two-phase plan's.
 
 A step is one watermark interval of the subtask's input: its rows are routed by key group

@@ -7,7 +7,8 @@ function a built-in field aggregation sum / min / max (SumAggregator / Comparabl
 count on a LONG / INT / DOUBLE field of (key, field) tuples.  Other triggers, evictors and minBy /
 maxBy stay on the reference operator; dynamic gaps and an allowed lateness have operators of their
 own (dynamic_session_window_operator.DynamicSessionWindowOperator,
-late_session_window_operator.LateSessionWindowOperator).
+late_session_window_operator.LateSessionWindowOperator, and for both together
+late_dynamic_session_window_operator.LateDynamicSessionWindowOperator).
 
 Semantics (WindowOperator.processElement's merging branch, MergingWindowSet.addWindow,
 TimeWindow.intersects / mergeWindows, EventTimeTrigger): an element's window [ts, ts + gap) and

@@ -184,7 +184,29 @@ typedef enum {
        keep the FW_WIN_SESSION entry format; their fingerprint mixes the kind and the lateness.
        fw_restore_key_group returns FW_E_STATE unless the blob's watermark equals the handle's
        current watermark (fw_initialize_watermark before the first key group sets it). */
-    FW_WIN_SESSION_LATENESS = 6
+    FW_WIN_SESSION_LATENESS = 6,
+    /* v11 (additive), DataStream only: EventTimeSessionWindows.withDynamicGap(extractor) with
+       allowedLateness >= 0, EventTimeTrigger, no evictor (DynamicEventTimeSessionWindows.assignWindows,
+       WindowOperator.processElement's merging branch, EventTimeTrigger.onElement, cleanupTime:
+       recalled, parity unpinned).  The product of the two kinds above; neither of them changes.  It
+       is validated as FW_WIN_SESSION_DYNAMIC is, with the same messages -- n_value_cols 2, value
+       column 1 the FW_T_I64 gap that no aggregate reads, size_ms the largest gap an element may
+       carry, in (0, 2^40] -- and takes allowed_lateness_ms in [0, 2^40].  An element's window is
+       [ts, ts + g) with its own gap g; merging follows FW_WIN_SESSION; drop, immediate fire,
+       retention and cleanup follow FW_WIN_SESSION_LATENESS with g in place of size_ms wherever the
+       element's own window is named.  A session is held until the watermark reaches end - 1 +
+       allowed_lateness_ms, fires when the watermark first reaches end - 1 and is then retained.  An
+       element that intersects no held session and has ts + g - 1 + allowed_lateness_ms <= watermark
+       is dropped (counted, and written to the late side output if configured, its gap column 0);
+       any other element is kept, and if the session it produced has end - 1 <= watermark that
+       session is emitted at once, with the element, in arrival order.  A row whose gap is outside
+       (0, size_ms] adds nothing and raises FW_ERRF_GAP.  Snapshot blobs keep the FW_WIN_SESSION
+       entry format; their fingerprint mixes this kind, size_ms and the lateness, so a blob crosses
+       neither into FW_WIN_SESSION_DYNAMIC nor into FW_WIN_SESSION_LATENESS nor into a handle of
+       another size_ms or lateness.  fw_restore_key_group returns FW_E_STATE unless the blob's
+       watermark equals the handle's current watermark (fw_initialize_watermark before the first
+       key group sets it). */
+    FW_WIN_SESSION_DYNAMIC_LATENESS = 7
 } fw_window_kind;
 
 typedef enum {
@@ -427,7 +449,8 @@ int fw_push_device_key_rows(fw_handle* h, int64_t n, const int64_t* d_key_row_of
    the row counts): n_segs segments of seg_len rows, one per sending subtask; segment s holds
    d_seg_counts[s] valid rows (device int64, e.g. the counts all-to-all's result), the rest is
    padding and is never read.  Otherwise as fw_push_device.
-   A session handle (FW_WIN_SESSION, FW_WIN_SESSION_DYNAMIC, FW_WIN_SESSION_LATENESS, either API) takes the call iff its
+   A session handle (FW_WIN_SESSION, FW_WIN_SESSION_DYNAMIC, FW_WIN_SESSION_LATENESS,
+   FW_WIN_SESSION_DYNAMIC_LATENESS, either API) takes the call iff its
    configuration has parallelism > 1; one of parallelism 1 and every count handle return
    FW_E_INVALID (a count handle's segment pushes are fw_push_device_count_segments and
    fw_push_device_count_packed_segments, below).  The rows are folded when they are pushed, in buffer position order, under the
@@ -596,7 +619,7 @@ int fw_results_device_segments(fw_handle* h, fw_result_segments* out);
 #define FW_ERRF_LATE 32       /* late-fire rows or late side-output rows over capacity     */
 #define FW_ERRF_ORDEV 64      /* first-element retain / release events over capacity       */
 #define FW_ERRF_KEYROW 128    /* key-row table full, or a key row over key_row_max_bytes   */
-#define FW_ERRF_GAP 256       /* FW_WIN_SESSION_DYNAMIC: a row's gap outside (0, size_ms]  */
+#define FW_ERRF_GAP 256       /* FW_WIN_SESSION_DYNAMIC(_LATENESS): a row's gap outside (0, size_ms] */
 int fw_get_stats(fw_handle* h, fw_stats* out);
 
 /* ---- per-kernel device timing (in-kernel clock stamps, or hipEvents around each launch) --- */
@@ -913,6 +936,15 @@ int fw_host_session_add_late(const fw_config* cfg, int64_t watermark, int64_t ts
    routine fw_host_session_add and the device code call. */
 int fw_host_session_add_gap(const fw_config* cfg, int64_t watermark, int64_t ts, int64_t gap, int64_t value, int64_t* starts,
                             int64_t* ends, int64_t* accs, int32_t* n, int32_t capacity, int32_t* outcome);
+/* v11 (additive): the same for a FW_WIN_SESSION_DYNAMIC_LATENESS configuration, the union of the two
+   above: the element's window is [ts, ts + gap) with its own gap, the drop test its cleanup time
+   (ts + gap - 1 + allowed_lateness_ms <= watermark, for an element that intersects nothing), and
+   *fired_index names the session to emit at once, or is -1.  FW_E_INVALID also for a gap outside
+   (0, size_ms] and for a configuration of another window kind.  It runs the routine the device code
+   calls. */
+int fw_host_session_add_gap_late(const fw_config* cfg, int64_t watermark, int64_t ts, int64_t gap, int64_t value, int64_t* starts,
+                                 int64_t* ends, int64_t* accs, int32_t* n, int32_t capacity, int32_t* outcome,
+                                 int32_t* fired_index);
 /* v11 (additive): the same for a SQL session configuration (FW_WIN_SESSION with FW_API_SQL), whose
    sessions carry the accumulator words of the aggregate list.  fw_host_sql_session_words returns
    the number of words nw the plan uses (1 .. 8; the device rounds it up to 1, 2, 4 or 8).

@@ -10,7 +10,8 @@ the advance and the (stream-ordered) result reset; it is timed on the host aroun
 Prints one JSON line per stream.
 
     python tools/session_window_bench.py [--rows N] [--warmup 5] [--steps 20] [--streams uniform,zipf,hot]
-                                         [--sql AGGS | --dynamic-gap | --lateness MS [--late-share F]]
+                                         [--sql AGGS | --dynamic-gap | --lateness MS [--late-share F] |
+                                          --dynamic-gap --lateness MS [--late-share F]]
 
 --sql AGGS runs the same streams through a SQL session handle (the SESSION window TVF aggregate,
 BINROW_BIGINT keys) instead: AGGS is a comma-separated aggregate list over two value columns, a
@@ -32,6 +33,12 @@ candidate's key run leaves the parallel path for the arrival-order walk of one l
 that reaches back (10 s: every candidate is kept) most of them fire a retained session again, with
 0 the ones that touch no open session are dropped.  The lines carry "lateness_ms", "late_share" and
 the rows dropped.
+
+--dynamic-gap --lateness MS runs the constant-gap and the mixed-gap dynamic handles with that allowed
+lateness (FW_WIN_SESSION_DYNAMIC_LATENESS) and the same late candidates, once each.  A candidate is
+placed by the 3 s gap; a mixed-gap row with a shorter gap that lies behind the watermark by its own
+gap is a candidate too.  The lines carry "kind", "gaps", "lateness_ms", "late_share" and the rows
+dropped.
 """
 import argparse
 import json
@@ -72,7 +79,8 @@ def run(kind, rows, warmup, steps, n_keys=10**6, sql=None, gaps=None, lateness=N
     ``lateness``: not None = a handle with that allowed lateness and ``late_share`` late candidates"""
     import torch
     from flink_amd import abi
-    from flink_amd.datastream import DynamicSessionWindowOperator, LateSessionWindowOperator, SessionWindowOperator
+    from flink_amd.datastream import (DynamicSessionWindowOperator, LateDynamicSessionWindowOperator, LateSessionWindowOperator,
+                                      SessionWindowOperator)
     from flink_amd.table import SessionWindowAggOperator
     dev = torch.device("cuda", 0)
     if kind == "hot":  # a step of the hot key takes far longer than the others: fewer of them
@@ -80,6 +88,10 @@ def run(kind, rows, warmup, steps, n_keys=10**6, sql=None, gaps=None, lateness=N
     if sql:
         op = SessionWindowAggOperator(GAP_MS, [_SQL_AGGS[a] for a in sql.split(",")], ["BIGINT", "DOUBLE"], nullable_cols=(1,),
                                       state_capacity=1 << 21, max_batch_rows=rows, output_capacity=1 << 22).open()
+    elif gaps and lateness is not None:
+        # (shorter gaps merge less: the mixed stream holds more sessions over the lateness than the static handle's list takes)
+        op = LateDynamicSessionWindowOperator(GAP_MS, lateness, ("sum", "LONG"), state_capacity=1 << 22, max_batch_rows=rows,
+                                              output_capacity=1 << 23).open()
     elif gaps:
         op = DynamicSessionWindowOperator(GAP_MS, ("sum", "LONG"), state_capacity=1 << 21, max_batch_rows=rows,
                                           output_capacity=1 << 22).open()
@@ -134,6 +146,9 @@ def run(kind, rows, warmup, steps, n_keys=10**6, sql=None, gaps=None, lateness=N
         if sql:
             window = "SQL SESSION(gap 3s) " + sql
             extra = {"accumulator_words": abi.host_sql_session_words(op.cfg)}
+        elif gaps and lateness is not None:
+            window = "EventTimeSessionWindows.withDynamicGap(<= 3s).allowedLateness.sum LONG"
+            extra = {"kind": "FW_WIN_SESSION_DYNAMIC_LATENESS", "gaps": gaps, "lateness_ms": lateness, "late_share": round(late_share, 4)}
         elif gaps:
             window = "EventTimeSessionWindows.withDynamicGap(<= 3s).sum LONG"
             extra = {"gaps": gaps}
@@ -163,13 +178,17 @@ def main():
     a = ap.parse_args()
     if a.sql and a.dynamic_gap:
         ap.error("--dynamic-gap is a DataStream run (no --sql)")
-    if a.lateness is not None and (a.sql or a.dynamic_gap):
-        ap.error("--lateness is a static-gap DataStream run (no --sql, no --dynamic-gap)")
+    if a.lateness is not None and a.sql:
+        ap.error("--lateness is a DataStream run (no --sql)")
     if a.sql and any(x not in _SQL_AGGS for x in a.sql.split(",")):
         ap.error("--sql takes a comma-separated list out of " + ", ".join(_SQL_AGGS))
     for kind in a.streams.split(","):
         if not a.dynamic_gap:
             print(json.dumps(run(kind, a.rows, a.warmup, a.steps, sql=a.sql, lateness=a.lateness, late_share=a.late_share)), flush=True)
+            continue
+        if a.lateness is not None:      # the dynamic-gap handles with a lateness: constant, mixed
+            for gaps in ("constant", "mixed"):
+                print(json.dumps(run(kind, a.rows, a.warmup, a.steps, gaps=gaps, lateness=a.lateness, late_share=a.late_share)), flush=True)
             continue
         for _ in range(2):      # alternating: static, constant, mixed, twice
             for gaps in (None, "constant", "mixed"):
