@@ -3639,97 +3639,65 @@ int fw_host_count_step(const fw_config* cfg, int64_t index, int64_t* slice, int3
     return FW_OK;
 }
 
-int fw_host_session_add(const fw_config* cfg, int64_t watermark, int64_t ts, int64_t value, int64_t* starts, int64_t* ends,
-                        int64_t* accs, int32_t* n, int32_t capacity, int32_t* outcome) {
+// One session list, one element: the body of the four fw_host_session_add* entry points.  `kind` is the
+// window kind the entry point accepts (kind_name in the messages) and `name` its own name; `gap` is the
+// caller's gap (the dynamic kinds) or null for the configuration's; `fired_index` is given by the
+// lateness kinds, which run session_add<1, true>.  (Only FW_WIN_SESSION plans a SQL configuration.)
+static int host_session_add(int32_t kind, const char* kind_name, const char* name, const fw_config* cfg, int64_t watermark, int64_t ts,
+                            const int64_t* gap, int64_t value, int64_t* starts, int64_t* ends, int64_t* accs, int32_t* n,
+                            int32_t capacity, int32_t* outcome, int32_t* fired_index) {
     if (!cfg || !n || !outcome || (capacity > 0 && (!starts || !ends || !accs))) return fail(FW_E_INVALID, "null argument");
-    if (cfg->window_kind != FW_WIN_SESSION) return fail(FW_E_INVALID, "fw_host_session_add needs a FW_WIN_SESSION configuration");
+    if (cfg->window_kind != kind) return fail(FW_E_INVALID, "%s needs a %s configuration", name, kind_name);
     fw_handle h;
     h.cfg = *cfg;
     const int rc = validate_and_plan(&h);
     if (rc) return rc;
-    if (h.sw.d.sql) return fail(FW_E_INVALID, "fw_host_session_add needs a DataStream session configuration (SQL: fw_host_sql_session_add)");
-    if (*n < 0 || *n > capacity) return fail(FW_E_INVALID, "bad session count %d (capacity %d)", *n, capacity);
     const SessionDesc& d = h.sw.d;
+    if (d.sql) return fail(FW_E_INVALID, "%s needs a DataStream session configuration (SQL: fw_host_sql_session_add)", name);
+    if (gap && (*gap < 1 || *gap > d.gap))
+        return fail(FW_E_INVALID, "session gap %lld is outside (0, size_ms = %lld]", (long long)*gap, (long long)d.gap);
+    if (*n < 0 || *n > capacity) return fail(FW_E_INVALID, "bad session count %d (capacity %d)", *n, capacity);
     for (int32_t i = 0; i < *n; i++) accs[i] = (int64_t)session_word_of_result(d, (uint64_t)accs[i]);
     const uint64_t word = session_word(d, (uint64_t)value);
-    const int r = session_add<1>(d.gap, d.ops, watermark, ts, &word, 1, starts, ends, (uint64_t*)accs, 1, 1, n, capacity);
-    for (int32_t i = 0; i < *n; i++) accs[i] = (int64_t)session_result(d, (uint64_t)accs[i]);
-    if (r < 0) return fail(FW_E_CAPACITY, "the session list is full (%d sessions)", capacity);
-    *outcome = r;
-    return FW_OK;
-}
-
-int fw_host_session_add_late(const fw_config* cfg, int64_t watermark, int64_t ts, int64_t value, int64_t* starts, int64_t* ends,
-                             int64_t* accs, int32_t* n, int32_t capacity, int32_t* outcome, int32_t* fired_index) {
-    if (!cfg || !n || !outcome || !fired_index || (capacity > 0 && (!starts || !ends || !accs))) return fail(FW_E_INVALID, "null argument");
-    if (cfg->window_kind != FW_WIN_SESSION_LATENESS)
-        return fail(FW_E_INVALID, "fw_host_session_add_late needs a FW_WIN_SESSION_LATENESS configuration");
-    fw_handle h;
-    h.cfg = *cfg;
-    const int rc = validate_and_plan(&h);
-    if (rc) return rc;
-    if (*n < 0 || *n > capacity) return fail(FW_E_INVALID, "bad session count %d (capacity %d)", *n, capacity);
-    const SessionDesc& d = h.sw.d;
-    for (int32_t i = 0; i < *n; i++) accs[i] = (int64_t)session_word_of_result(d, (uint64_t)accs[i]);
-    const uint64_t word = session_word(d, (uint64_t)value);
+    const int64_t g = gap ? *gap : d.gap;
     int32_t at = -1;
-    const int r = session_add<1, true>(d.gap, d.ops, watermark, ts, &word, 1, starts, ends, (uint64_t*)accs, 1, 1, n, capacity,
-                                       h.sw.lateness, &at);
+    const int r = fired_index ? session_add<1, true>(g, d.ops, watermark, ts, &word, 1, starts, ends, (uint64_t*)accs, 1, 1, n, capacity,
+                                                     h.sw.lateness, &at)
+                              : session_add<1>(g, d.ops, watermark, ts, &word, 1, starts, ends, (uint64_t*)accs, 1, 1, n, capacity);
     for (int32_t i = 0; i < *n; i++) accs[i] = (int64_t)session_result(d, (uint64_t)accs[i]);
     if (r < 0) return fail(FW_E_CAPACITY, "the session list is full (%d sessions)", capacity);
     *outcome = r;
     // EventTimeTrigger.onElement: the session the element produced fires at once if its timer has passed
-    *fired_index = r == 1 && session_due(ends[at], watermark) ? at : -1;
+    // (with a dynamic gap: recalled, parity unpinned)
+    if (fired_index) *fired_index = r == 1 && session_due(ends[at], watermark) ? at : -1;
     return FW_OK;
+}
+
+int fw_host_session_add(const fw_config* cfg, int64_t watermark, int64_t ts, int64_t value, int64_t* starts, int64_t* ends,
+                        int64_t* accs, int32_t* n, int32_t capacity, int32_t* outcome) {
+    return host_session_add(FW_WIN_SESSION, "FW_WIN_SESSION", "fw_host_session_add", cfg, watermark, ts, nullptr, value, starts, ends,
+                            accs, n, capacity, outcome, nullptr);
+}
+
+int fw_host_session_add_late(const fw_config* cfg, int64_t watermark, int64_t ts, int64_t value, int64_t* starts, int64_t* ends,
+                             int64_t* accs, int32_t* n, int32_t capacity, int32_t* outcome, int32_t* fired_index) {
+    if (!fired_index) return fail(FW_E_INVALID, "null argument");
+    return host_session_add(FW_WIN_SESSION_LATENESS, "FW_WIN_SESSION_LATENESS", "fw_host_session_add_late", cfg, watermark, ts, nullptr,
+                            value, starts, ends, accs, n, capacity, outcome, fired_index);
 }
 
 int fw_host_session_add_gap(const fw_config* cfg, int64_t watermark, int64_t ts, int64_t gap, int64_t value, int64_t* starts,
                             int64_t* ends, int64_t* accs, int32_t* n, int32_t capacity, int32_t* outcome) {
-    if (!cfg || !n || !outcome || (capacity > 0 && (!starts || !ends || !accs))) return fail(FW_E_INVALID, "null argument");
-    if (cfg->window_kind != FW_WIN_SESSION_DYNAMIC)
-        return fail(FW_E_INVALID, "fw_host_session_add_gap needs a FW_WIN_SESSION_DYNAMIC configuration");
-    fw_handle h;
-    h.cfg = *cfg;
-    const int rc = validate_and_plan(&h);
-    if (rc) return rc;
-    const SessionDesc& d = h.sw.d;
-    if (gap < 1 || gap > d.gap)
-        return fail(FW_E_INVALID, "session gap %lld is outside (0, size_ms = %lld]", (long long)gap, (long long)d.gap);
-    if (*n < 0 || *n > capacity) return fail(FW_E_INVALID, "bad session count %d (capacity %d)", *n, capacity);
-    for (int32_t i = 0; i < *n; i++) accs[i] = (int64_t)session_word_of_result(d, (uint64_t)accs[i]);
-    const uint64_t word = session_word(d, (uint64_t)value);
-    const int r = session_add<1>(gap, d.ops, watermark, ts, &word, 1, starts, ends, (uint64_t*)accs, 1, 1, n, capacity);
-    for (int32_t i = 0; i < *n; i++) accs[i] = (int64_t)session_result(d, (uint64_t)accs[i]);
-    if (r < 0) return fail(FW_E_CAPACITY, "the session list is full (%d sessions)", capacity);
-    *outcome = r;
-    return FW_OK;
+    return host_session_add(FW_WIN_SESSION_DYNAMIC, "FW_WIN_SESSION_DYNAMIC", "fw_host_session_add_gap", cfg, watermark, ts, &gap, value,
+                            starts, ends, accs, n, capacity, outcome, nullptr);
 }
 
 int fw_host_session_add_gap_late(const fw_config* cfg, int64_t watermark, int64_t ts, int64_t gap, int64_t value, int64_t* starts,
                                  int64_t* ends, int64_t* accs, int32_t* n, int32_t capacity, int32_t* outcome,
                                  int32_t* fired_index) {
-    if (!cfg || !n || !outcome || !fired_index || (capacity > 0 && (!starts || !ends || !accs))) return fail(FW_E_INVALID, "null argument");
-    if (cfg->window_kind != FW_WIN_SESSION_DYNAMIC_LATENESS)
-        return fail(FW_E_INVALID, "fw_host_session_add_gap_late needs a FW_WIN_SESSION_DYNAMIC_LATENESS configuration");
-    fw_handle h;
-    h.cfg = *cfg;
-    const int rc = validate_and_plan(&h);
-    if (rc) return rc;
-    const SessionDesc& d = h.sw.d;
-    if (gap < 1 || gap > d.gap)
-        return fail(FW_E_INVALID, "session gap %lld is outside (0, size_ms = %lld]", (long long)gap, (long long)d.gap);
-    if (*n < 0 || *n > capacity) return fail(FW_E_INVALID, "bad session count %d (capacity %d)", *n, capacity);
-    for (int32_t i = 0; i < *n; i++) accs[i] = (int64_t)session_word_of_result(d, (uint64_t)accs[i]);
-    const uint64_t word = session_word(d, (uint64_t)value);
-    int32_t at = -1;
-    const int r = session_add<1, true>(gap, d.ops, watermark, ts, &word, 1, starts, ends, (uint64_t*)accs, 1, 1, n, capacity,
-                                       h.sw.lateness, &at);
-    for (int32_t i = 0; i < *n; i++) accs[i] = (int64_t)session_result(d, (uint64_t)accs[i]);
-    if (r < 0) return fail(FW_E_CAPACITY, "the session list is full (%d sessions)", capacity);
-    *outcome = r;
-    // EventTimeTrigger.onElement (recalled, parity unpinned): the session the element produced fires at once if its timer has passed
-    *fired_index = r == 1 && session_due(ends[at], watermark) ? at : -1;
-    return FW_OK;
+    if (!fired_index) return fail(FW_E_INVALID, "null argument");
+    return host_session_add(FW_WIN_SESSION_DYNAMIC_LATENESS, "FW_WIN_SESSION_DYNAMIC_LATENESS", "fw_host_session_add_gap_late", cfg,
+                            watermark, ts, &gap, value, starts, ends, accs, n, capacity, outcome, fired_index);
 }
 
 // the plan of a SQL session configuration, as fw_create makes it

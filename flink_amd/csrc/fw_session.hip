@@ -836,10 +836,20 @@ static int sw_plan_sql(const fw_config& c, SessionOp* op) {
     return FW_OK;
 }
 
-// the DataStream form: EventTimeSessionWindows.withGap with one built-in aggregation
-static int sw_plan_ds(const fw_config& c, SessionOp* op) {
+// the DataStream forms: EventTimeSessionWindows.withGap with one built-in aggregation; dyn:
+// withDynamicGap (FW_WIN_SESSION_DYNAMIC); late: with allowedLateness >= 0 (FW_WIN_SESSION_LATENESS); both:
+// FW_WIN_SESSION_DYNAMIC_LATENESS.  The kinds share every message.  They differ in where the lateness is
+// checked -- the static and dynamic kinds refuse any, the lateness kind checks its range behind the API,
+// the dynamic lateness kind last -- and the lateness kind alone names itself when the API is wrong.
+static int sw_plan_ds(const fw_config& c, SessionOp* op, bool dyn, bool late) {
+    const bool bad_lateness = c.allowed_lateness_ms < 0 || c.allowed_lateness_ms > SW_MAX_GAP;
+    const char* const lateness_range = "session windows: allowed_lateness_ms must be in [0, 2^40]";
     if (c.api != FW_API_DATASTREAM)
-        return set_error(FW_E_INVALID, "FW_WIN_SESSION (EventTimeSessionWindows) is a DataStream window: api must be FW_API_DATASTREAM");
+        return late && !dyn ? set_error(FW_E_INVALID, "FW_WIN_SESSION_LATENESS (EventTimeSessionWindows with allowedLateness) is a "
+                                                      "DataStream window: api must be FW_API_DATASTREAM")
+                            : set_error(FW_E_INVALID, "FW_WIN_SESSION (EventTimeSessionWindows) is a DataStream window: api must be "
+                                                      "FW_API_DATASTREAM");
+    if (late && !dyn && bad_lateness) return set_error(FW_E_INVALID, "%s", lateness_range);
     if (c.n_aggs != 1) return set_error(FW_E_INVALID, "session windows take one aggregation (n_aggs == 1), got %d", c.n_aggs);
     const fw_agg_desc& g = c.aggs[0];
     if (g.kind == FW_AGG_MINBY || g.kind == FW_AGG_MAXBY)
@@ -859,7 +869,7 @@ static int sw_plan_ds(const fw_config& c, SessionOp* op) {
     if (c.size_ms > SW_MAX_GAP) return set_error(FW_E_INVALID, "session gap (size_ms) must be <= 2^40");
     if (c.slide_ms != 0) return set_error(FW_E_INVALID, "session windows have no slide (slide_ms must be 0)");
     if (c.offset_ms != 0) return set_error(FW_E_INVALID, "session windows have no offset (offset_ms must be 0)");
-    if (c.allowed_lateness_ms != 0)
+    if (!late && c.allowed_lateness_ms != 0)
         return set_error(FW_E_INVALID, "session windows with allowed lateness run on the reference operator (allowed_lateness_ms must be 0)");
     if (c.late_side_output != 0 && c.late_side_output != 1) return set_error(FW_E_INVALID, "late_side_output must be 0 or 1");
     if (c.ds_first_ordinals) return set_error(FW_E_INVALID, "session windows are (key, aggregate) shaped (ds_first_ordinals must be 0)");
@@ -892,64 +902,27 @@ static int sw_plan_ds(const fw_config& c, SessionOp* op) {
     op->n_out = 1;
     op->val_col = is_count ? 0 : g.input_col;
     op->late_side = c.late_side_output;
-    return FW_OK;
-}
-
-// the dynamic-gap form: EventTimeSessionWindows.withDynamicGap.  Everything sw_plan_ds refuses, with
-// its messages; value column 1 carries the element's gap and size_ms (d.gap) the largest one
-static int sw_plan_dyn(const fw_config& c, SessionOp* op) {
-    const int rc = sw_plan_ds(c, op);
-    if (rc) return rc;
-    if (c.n_value_cols != 2)
-        return set_error(FW_E_INVALID, "dynamic-gap session windows take two value columns, the aggregated field and the gap "
-                                       "(n_value_cols == 2), got %d", c.n_value_cols);
-    if (c.value_col_types[1] != FW_T_I64)
-        return set_error(FW_E_INVALID, "dynamic-gap session windows: the gap column (value column 1) must be FW_T_I64");
-    if (!op->d.is_count && c.aggs[0].input_col != 0)
-        return set_error(FW_E_INVALID, "dynamic-gap session windows: the aggregate reads value column 0 (input_col %d: column 1 is the gap)",
-                         c.aggs[0].input_col);
-    op->dyn = true;
-    return FW_OK;
-}
-
-// the lateness form: EventTimeSessionWindows.withGap with allowedLateness >= 0.  Everything
-// sw_plan_ds refuses, with its messages, but for the lateness, which has a range of its own
-static int sw_plan_late(const fw_config& c, SessionOp* op) {
-    if (c.api != FW_API_DATASTREAM)
-        return set_error(FW_E_INVALID, "FW_WIN_SESSION_LATENESS (EventTimeSessionWindows with allowedLateness) is a DataStream window: "
-                                       "api must be FW_API_DATASTREAM");
-    if (c.allowed_lateness_ms < 0 || c.allowed_lateness_ms > SW_MAX_GAP)
-        return set_error(FW_E_INVALID, "session windows: allowed_lateness_ms must be in [0, 2^40]");
-    fw_config c0 = c;
-    c0.allowed_lateness_ms = 0;
-    const int rc = sw_plan_ds(c0, op);
-    if (rc) return rc;
-    op->late = true;
-    op->lateness = c.allowed_lateness_ms;
-    return FW_OK;
-}
-
-// both: EventTimeSessionWindows.withDynamicGap with allowedLateness >= 0.  Everything sw_plan_dyn
-// refuses, with its messages, and the lateness range of sw_plan_late
-static int sw_plan_dyn_late(const fw_config& c, SessionOp* op) {
-    fw_config c0 = c;
-    c0.allowed_lateness_ms = 0;
-    const int rc = sw_plan_dyn(c0, op);
-    if (rc) return rc;
-    if (c.allowed_lateness_ms < 0 || c.allowed_lateness_ms > SW_MAX_GAP)
-        return set_error(FW_E_INVALID, "session windows: allowed_lateness_ms must be in [0, 2^40]");
-    op->late = true;
-    op->lateness = c.allowed_lateness_ms;
+    if (dyn) {  // value column 1 carries the element's gap and size_ms (d.gap) the largest one
+        if (c.n_value_cols != 2)
+            return set_error(FW_E_INVALID, "dynamic-gap session windows take two value columns, the aggregated field and the gap "
+                                           "(n_value_cols == 2), got %d", c.n_value_cols);
+        if (c.value_col_types[1] != FW_T_I64)
+            return set_error(FW_E_INVALID, "dynamic-gap session windows: the gap column (value column 1) must be FW_T_I64");
+        if (!is_count && g.input_col != 0)
+            return set_error(FW_E_INVALID, "dynamic-gap session windows: the aggregate reads value column 0 (input_col %d: column 1 is the gap)",
+                             g.input_col);
+        if (late && bad_lateness) return set_error(FW_E_INVALID, "%s", lateness_range);
+    }
+    op->dyn = dyn;
+    op->late = late;
+    op->lateness = late ? c.allowed_lateness_ms : 0;
     return FW_OK;
 }
 
 int sw_plan(const fw_config& c, SessionOp* op) {
-    const bool dyn = c.window_kind == FW_WIN_SESSION_DYNAMIC;
-    const int prc = c.window_kind == FW_WIN_SESSION_DYNAMIC_LATENESS ? sw_plan_dyn_late(c, op)
-                    : c.window_kind == FW_WIN_SESSION_LATENESS ? sw_plan_late(c, op)
-                    : dyn                                    ? sw_plan_dyn(c, op)
-                    : c.api == FW_API_SQL                    ? sw_plan_sql(c, op)
-                                                             : sw_plan_ds(c, op);
+    const bool dyn = c.window_kind == FW_WIN_SESSION_DYNAMIC || c.window_kind == FW_WIN_SESSION_DYNAMIC_LATENESS;
+    const bool late = c.window_kind == FW_WIN_SESSION_LATENESS || c.window_kind == FW_WIN_SESSION_DYNAMIC_LATENESS;
+    const int prc = !dyn && !late && c.api == FW_API_SQL ? sw_plan_sql(c, op) : sw_plan_ds(c, op, dyn, late);
     if (prc) return prc;
     const SessionDesc& d = op->d;
 
@@ -963,32 +936,23 @@ int sw_plan(const fw_config& c, SessionOp* op) {
     op->cap_s = (int32_t)cs;
     op->out_cap = c.output_capacity;
     op->side_cap = c.late_side_output ? 2 * c.max_batch_rows : 0;
-    uint64_t x = 0xcbf29ce484222325ull;  // the semantics fingerprint of the blobs (FNV-1a, as the time windows')
-    auto mix = [&x](int64_t v) {
+    // the semantics fingerprint of the blobs (FNV-1a, as the time windows'), one value list per kind
+    std::vector<int64_t> fp{(int64_t)c.api, (int64_t)c.window_kind, d.gap};
+    if (!d.sql) {  // (the DataStream blobs' fingerprint since their first build; the other three kinds name themselves, and
+        // a lateness kind its lateness: the fired sessions of a blob are read off its watermark)
+        if (op->late) fp.push_back(op->lateness);
+        fp.insert(fp.end(), {(int64_t)d.op, (int64_t)d.vtype, (int64_t)d.is_count, (int64_t)ks.hash_kind, (int64_t)ks.max_p});
+    } else {  // every aggregate, the NULL-able columns, key hash, max parallelism
+        fp.insert(fp.end(), {(int64_t)c.n_aggs, (int64_t)c.nullable_cols, (int64_t)ks.hash_kind, (int64_t)ks.max_p});
+        for (int g = 0; g < c.n_aggs; g++)
+            fp.insert(fp.end(), {(int64_t)c.aggs[g].kind, (int64_t)c.aggs[g].type, (int64_t)c.aggs[g].input_col});
+    }
+    uint64_t x = 0xcbf29ce484222325ull;
+    for (int64_t v : fp)
         for (int b = 0; b < 8; b++) {
             x ^= (uint64_t)((v >> (8 * b)) & 0xff);
             x *= 0x100000001b3ull;
         }
-    };
-    if (!d.sql) {  // (the DataStream blobs' fingerprint since their first build; the dynamic form's names its kind)
-        for (int64_t v : {(int64_t)c.api, (int64_t)(op->dyn ? FW_WIN_SESSION_DYNAMIC : FW_WIN_SESSION), d.gap, (int64_t)d.op,
-                          (int64_t)d.vtype, (int64_t)d.is_count, (int64_t)ks.hash_kind, (int64_t)ks.max_p})
-            mix(v);
-        if (op->late) {  // a kind and a lateness of its own: the fired sessions of a blob are read off its watermark
-            x = 0xcbf29ce484222325ull;
-            // (with dynamic gaps a kind of its own again: d.gap is then the largest gap)
-            for (int64_t v : {(int64_t)c.api, (int64_t)(op->dyn ? FW_WIN_SESSION_DYNAMIC_LATENESS : FW_WIN_SESSION_LATENESS), d.gap,
-                              op->lateness, (int64_t)d.op, (int64_t)d.vtype,
-                              (int64_t)d.is_count, (int64_t)ks.hash_kind, (int64_t)ks.max_p})
-                mix(v);
-        }
-    } else {  // the API, every aggregate, the NULL-able columns, key hash, gap, max parallelism
-        for (int64_t v : {(int64_t)c.api, (int64_t)FW_WIN_SESSION, d.gap, (int64_t)c.n_aggs, (int64_t)c.nullable_cols,
-                          (int64_t)ks.hash_kind, (int64_t)ks.max_p})
-            mix(v);
-        for (int g = 0; g < c.n_aggs; g++)
-            for (int64_t v : {(int64_t)c.aggs[g].kind, (int64_t)c.aggs[g].type, (int64_t)c.aggs[g].input_col}) mix(v);
-    }
     op->fingerprint = x;
     op->on = true;
     return FW_OK;
@@ -1042,18 +1006,39 @@ void sw_free(SessionOp* op) {
     hipFree(op->side);
 }
 
-// the kernels' instance of a handle: NW = sw_round_nw(words of the plan); `form` the template
-// arguments behind NW (SW_HOST: none, the host-watermark instances)
-#define SW_HOST(nw) <nw>
-#define SW_DEV_FOLD(nw) <nw, false, true>
-#define SW_DEV_ADV(nw) <nw, true>
-#define SW_LAUNCH_NW(kernel, form, nw_t, ...)                                      \
-    switch (nw_t) {                                                                \
-        case 1: hipLaunchKernelGGL((kernel form(1)), __VA_ARGS__); break;          \
-        case 2: hipLaunchKernelGGL((kernel form(2)), __VA_ARGS__); break;          \
-        case 4: hipLaunchKernelGGL((kernel form(4)), __VA_ARGS__); break;          \
-        default: hipLaunchKernelGGL((kernel form(8)), __VA_ARGS__); break;         \
+// The kernels' instance of a handle, chosen in one place: calls launch(SwInstance<NW, DYN, DEV, LATE>{})
+// with NW = nw_t (sw_round_nw of the plan's words).  DYN and LATE exist with NW == 1 only (the DataStream
+// kinds), so a fold has 14 instances; an advance ignores DYN and has 10.
+template <int NW, bool DYN, bool DEV, bool LATE>
+struct SwInstance {
+    static constexpr int nw = NW;
+    static constexpr bool dyn = DYN, dev = DEV, late = LATE;
+};
+template <int NW, class F>
+static void sw_dispatch_sql(bool dev, F& launch) {
+    if (dev) launch(SwInstance<NW, false, true, false>{});
+    else launch(SwInstance<NW, false, false, false>{});
+}
+template <class F>
+static void sw_dispatch(int32_t nw_t, bool dyn, bool dev, bool late, F launch) {
+    switch (nw_t) {
+        case 1:
+            switch ((dyn ? 4 : 0) | (dev ? 2 : 0) | (late ? 1 : 0)) {
+                case 0: launch(SwInstance<1, false, false, false>{}); break;
+                case 1: launch(SwInstance<1, false, false, true>{}); break;
+                case 2: launch(SwInstance<1, false, true, false>{}); break;
+                case 3: launch(SwInstance<1, false, true, true>{}); break;
+                case 4: launch(SwInstance<1, true, false, false>{}); break;
+                case 5: launch(SwInstance<1, true, false, true>{}); break;
+                case 6: launch(SwInstance<1, true, true, false>{}); break;
+                default: launch(SwInstance<1, true, true, true>{}); break;
+            }
+            break;
+        case 2: sw_dispatch_sql<2>(dev, launch); break;
+        case 4: sw_dispatch_sql<4>(dev, launch); break;
+        default: sw_dispatch_sql<8>(dev, launch); break;
     }
+}
 
 // the folds of one call: n rows at d_key[i * stride] ..., split into launches of part.cap_rows rows by
 // position.  d_seg_counts: the rows are a padded buffer of segments of seg_len rows (the device form);
@@ -1105,25 +1090,11 @@ static int sw_fold_call(SessionOp* op, bool dev, int64_t watermark, int64_t n, c
             fa.out_we = op->out_we;
             fa.out_val = op->out_val[0];
             fa.out_cap = op->out_cap;
-            if (op->dyn) {  // (fa.vals[1], the gap column, is filled above)
-                if (dev) hipLaunchKernelGGL((k_sw_fold<1, true, true, true>), dim3(n_sb), dim3(SW_TILE), 0, s, fa);
-                else hipLaunchKernelGGL((k_sw_fold<1, true, false, true>), dim3(n_sb), dim3(SW_TILE), 0, s, fa);
-            } else if (dev) {
-                hipLaunchKernelGGL((k_sw_fold<1, false, true, true>), dim3(n_sb), dim3(SW_TILE), 0, s, fa);
-            } else {
-                hipLaunchKernelGGL((k_sw_fold<1, false, false, true>), dim3(n_sb), dim3(SW_TILE), 0, s, fa);
-            }
-        } else if (dev) {
-            if (op->dyn) {
-                hipLaunchKernelGGL((k_sw_fold<1, true, true>), dim3(n_sb), dim3(SW_TILE), 0, s, fa);
-            } else {
-                SW_LAUNCH_NW(k_sw_fold, SW_DEV_FOLD, op->nw_t, dim3(n_sb), dim3(SW_TILE), 0, s, fa);
-            }
-        } else if (op->dyn) {
-            hipLaunchKernelGGL((k_sw_fold<1, true>), dim3(n_sb), dim3(SW_TILE), 0, s, fa);
-        } else {
-            SW_LAUNCH_NW(k_sw_fold, SW_HOST, op->nw_t, dim3(n_sb), dim3(SW_TILE), 0, s, fa);
         }
+        sw_dispatch(op->nw_t, op->dyn, dev, op->late, [&](auto inst) {
+            using I = decltype(inst);
+            hipLaunchKernelGGL((k_sw_fold<I::nw, I::dyn, I::dev, I::late>), dim3(n_sb), dim3(SW_TILE), 0, s, fa);
+        });
         FD_TRY(hipGetLastError());
     }
     op->push_seq++;
@@ -1163,33 +1134,27 @@ static SwAdvArgs sw_adv_args(SessionOp* op, int64_t watermark) {
     return a;
 }
 
-// (a dynamic-gap handle runs the NW = 1 instance too: sessions carry their ends, no gap is read)
-int sw_advance(SessionOp* op, int64_t watermark, int64_t prev_watermark) {
-    SwAdvArgs a = sw_adv_args(op, watermark);
-    if (op->late) {
-        a.prev_watermark = prev_watermark;
-        hipLaunchKernelGGL((k_sw_advance<1, false, true>), dim3(op->ks.n_sb), dim3(SW_TILE), 0, op->stream, a);
-        FD_TRY(hipGetLastError());
-        return FW_OK;
-    }
-    SW_LAUNCH_NW(k_sw_advance, SW_HOST, op->nw_t, dim3(op->ks.n_sb), dim3(SW_TILE), 0, op->stream, a);
+// (a dynamic-gap handle runs the static instance: sessions carry their ends, no gap is read)
+static int sw_advance_launch(SessionOp* op, bool dev, const SwAdvArgs& a) {
+    sw_dispatch(op->nw_t, false, dev, op->late, [&](auto inst) {
+        using I = decltype(inst);
+        hipLaunchKernelGGL((k_sw_advance<I::nw, I::dev, I::late>), dim3(op->ks.n_sb), dim3(SW_TILE), 0, op->stream, a);
+    });
     FD_TRY(hipGetLastError());
     return FW_OK;
 }
 
+int sw_advance(SessionOp* op, int64_t watermark, int64_t prev_watermark) {
+    SwAdvArgs a = sw_adv_args(op, watermark);
+    a.prev_watermark = prev_watermark;  // (read by the lateness instances alone)
+    return sw_advance_launch(op, false, a);
+}
+
 int sw_advance_device(SessionOp* op, const int64_t* d_watermark, int64_t watermark) {
     op->wm_dev = true;
-    const SwAdvArgs a = sw_adv_args(op, 0);
-    if (op->late) {
-        hipLaunchKernelGGL(k_sw_raise_late, dim3(1), dim3(1), 0, op->stream, op->ctrl, d_watermark, watermark, op->prev_wm);
-        hipLaunchKernelGGL((k_sw_advance<1, true, true>), dim3(op->ks.n_sb), dim3(SW_TILE), 0, op->stream, a);
-        FD_TRY(hipGetLastError());
-        return FW_OK;
-    }
-    hipLaunchKernelGGL(k_sw_raise, dim3(1), dim3(1), 0, op->stream, op->ctrl, d_watermark, watermark);
-    SW_LAUNCH_NW(k_sw_advance, SW_DEV_ADV, op->nw_t, dim3(op->ks.n_sb), dim3(SW_TILE), 0, op->stream, a);
-    FD_TRY(hipGetLastError());
-    return FW_OK;
+    if (op->late) hipLaunchKernelGGL(k_sw_raise_late, dim3(1), dim3(1), 0, op->stream, op->ctrl, d_watermark, watermark, op->prev_wm);
+    else hipLaunchKernelGGL(k_sw_raise, dim3(1), dim3(1), 0, op->stream, op->ctrl, d_watermark, watermark);
+    return sw_advance_launch(op, true, sw_adv_args(op, 0));
 }
 
 int sw_read_watermark(SessionOp* op, int64_t* watermark) {

@@ -23,10 +23,9 @@ branch, EventTimeTrigger.onElement, cleanupTime; recalled, parity unpinned).  La
 returns those and the timer rows.
 """
 from .. import abi
-from ..runtime.options import gpu_enabled
-from .count_window_operator import StringKeyTable
-from .dynamic_session_window_operator import _AGG, _KEY, _TYPE, MAX_GAP, DynamicSessionWindowOperator
+from .dynamic_session_window_operator import _AGG, _KEY, _TYPE, MAX_GAP, DynamicSessionWindowOperator  # noqa: F401
 from .late_session_window_operator import MAX_LATENESS
+from .session_operator_base import _common_eligibility
 from .windowing import DynamicEventTimeSessionWindows, EventTimeTrigger
 
 
@@ -34,23 +33,12 @@ def is_gpu_eligible(assigner, trigger, aggregation, *, max_gap=MAX_GAP, evictor=
     """WindowOperatorBuilder's seam for dynamic-gap session windows with an allowed lateness.
     ``max_gap``: the largest gap the job's extractor returns; ``conf``: the job configuration
     (``gpu.window-agg.enabled``); None = the GPU operator was chosen."""
-    if conf is not None and not gpu_enabled(conf):
-        return False, "gpu.window-agg.enabled is false"
-    if not isinstance(assigner, DynamicEventTimeSessionWindows):
-        return False, "assigner is not DynamicEventTimeSessionWindows (EventTimeSessionWindows.withDynamicGap)"
-    if not isinstance(trigger, EventTimeTrigger):
-        return False, "trigger is not EventTimeTrigger"
-    if evictor is not None:
-        return False, "session windows with an evictor stay on the reference operator"
-    if allowed_lateness < 0 or allowed_lateness > MAX_LATENESS:
-        return False, "allowedLateness must be in [0, 2^40]"
-    if max_gap <= 0 or max_gap > MAX_GAP:
-        return False, "max_gap must be in (0, 2^40]"
-    if len(aggregation) != 2 or aggregation[0] not in _AGG:
-        return False, "not sum / min / max / count (minBy / maxBy stay on the reference operator)"
-    if aggregation[1] not in _TYPE:
-        return False, f"field type {aggregation[1]} is not LONG / INT / DOUBLE"
-    return True, ""
+    return _common_eligibility(
+        assigner, DynamicEventTimeSessionWindows,
+        "assigner is not DynamicEventTimeSessionWindows (EventTimeSessionWindows.withDynamicGap)",
+        trigger, aggregation, evictor=evictor, conf=conf,
+        lateness_refusal=None if 0 <= allowed_lateness <= MAX_LATENESS else "allowedLateness must be in [0, 2^40]",
+        gap=max_gap, gap_refusal="max_gap must be in (0, 2^40]")
 
 
 class LateDynamicSessionWindowOperator(DynamicSessionWindowOperator):
@@ -68,8 +56,6 @@ class LateDynamicSessionWindowOperator(DynamicSessionWindowOperator):
         t = _TYPE[ftype]
         self.max_gap = max_gap_ms
         self.allowed_lateness = allowed_lateness_ms
-        self.aggregation = aggregation
-        self.key_type = key_type
         # value column 0: the aggregated field; value column 1: the element's gap
         self.cfg = abi.make_config(
             api=abi.API_DATASTREAM, window_kind=abi.WIN_SESSION_DYNAMIC_LATENESS, size_ms=max_gap_ms,
@@ -77,9 +63,7 @@ class LateDynamicSessionWindowOperator(DynamicSessionWindowOperator):
             value_col_types=[t, abi.T_I64], key_hash=_KEY[key_type], late_side_output=late_side_output,
             max_parallelism=max_parallelism, parallelism=parallelism, subtask_index=subtask_index, device=device,
             state_capacity=state_capacity, max_batch_rows=max_batch_rows, output_capacity=output_capacity)
-        self.handle = None
-        self._keys = StringKeyTable()
-        self._device_pushed = False   # a device batch's gaps are checked by the kernel (FW_ERRF_GAP)
+        self._init_common(aggregation, key_type)
 
     def collect(self):
         """The rows in the result buffer, without advancing: after a push, the sessions its late

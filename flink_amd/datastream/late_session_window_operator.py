@@ -23,10 +23,9 @@ recalled, parity unpinned).  Gap g, lateness L, watermark W:
 returns those and the timer rows.
 """
 from .. import abi
-from .session_window_operator import _AGG, _KEY, _TYPE, MAX_GAP, SessionWindowOperator
-from .count_window_operator import StringKeyTable
+from .session_operator_base import _common_eligibility
+from .session_window_operator import _AGG, _KEY, _TYPE, MAX_GAP, SessionWindowOperator  # noqa: F401
 from .windowing import EventTimeSessionWindows, EventTimeTrigger
-from ..runtime.options import gpu_enabled
 
 MAX_LATENESS = 1 << 40
 
@@ -34,23 +33,12 @@ MAX_LATENESS = 1 << 40
 def is_gpu_eligible(assigner, trigger, aggregation, *, evictor=None, allowed_lateness=0, conf=None):
     """WindowOperatorBuilder's seam for session windows with an allowed lateness.  ``conf``: the job
     configuration (``gpu.window-agg.enabled``); None = the GPU operator was chosen."""
-    if conf is not None and not gpu_enabled(conf):
-        return False, "gpu.window-agg.enabled is false"
-    if not isinstance(assigner, EventTimeSessionWindows):
-        return False, "assigner is not EventTimeSessionWindows with a static gap (dynamic gaps with allowedLateness stay on the reference operator)"
-    if not isinstance(trigger, EventTimeTrigger):
-        return False, "trigger is not EventTimeTrigger"
-    if evictor is not None:
-        return False, "session windows with an evictor stay on the reference operator"
-    if allowed_lateness < 0 or allowed_lateness > MAX_LATENESS:
-        return False, "allowedLateness must be in [0, 2^40]"
-    if assigner.gap <= 0 or assigner.gap > MAX_GAP:
-        return False, "session gap must be in (0, 2^40]"
-    if len(aggregation) != 2 or aggregation[0] not in _AGG:
-        return False, "not sum / min / max / count (minBy / maxBy stay on the reference operator)"
-    if aggregation[1] not in _TYPE:
-        return False, f"field type {aggregation[1]} is not LONG / INT / DOUBLE"
-    return True, ""
+    return _common_eligibility(
+        assigner, EventTimeSessionWindows,
+        "assigner is not EventTimeSessionWindows with a static gap (dynamic gaps with allowedLateness stay on the reference operator)",
+        trigger, aggregation, evictor=evictor, conf=conf,
+        lateness_refusal=None if 0 <= allowed_lateness <= MAX_LATENESS else "allowedLateness must be in [0, 2^40]",
+        gap=getattr(assigner, "gap", 0), gap_refusal="session gap must be in (0, 2^40]")
 
 
 class LateSessionWindowOperator(SessionWindowOperator):
@@ -68,16 +56,13 @@ class LateSessionWindowOperator(SessionWindowOperator):
         t = _TYPE[ftype]
         self.gap = gap_ms
         self.allowed_lateness = allowed_lateness_ms
-        self.aggregation = aggregation
-        self.key_type = key_type
         self.cfg = abi.make_config(
             api=abi.API_DATASTREAM, window_kind=abi.WIN_SESSION_LATENESS, size_ms=gap_ms, allowed_lateness_ms=allowed_lateness_ms,
             aggs=[(_AGG[fn], 0, t)], count_star_index=-1, value_col_types=[t], key_hash=_KEY[key_type],
             late_side_output=late_side_output, max_parallelism=max_parallelism, parallelism=parallelism,
             subtask_index=subtask_index, device=device, state_capacity=state_capacity, max_batch_rows=max_batch_rows,
             output_capacity=output_capacity)
-        self.handle = None
-        self._keys = StringKeyTable()
+        self._init_common(aggregation, key_type)
 
     def collect(self):
         """The rows in the result buffer, without advancing: after a push, the sessions its late
