@@ -94,6 +94,7 @@ def lib():
         "fw_host_next_trigger_watermark": (i64, [i64, i64]),
         "fw_host_time_op": (i32, [P(abi.fw_config), i32, i64, P(i64)]),
         "fw_host_count_step": (i32, [P(abi.fw_config), i64, P(i64), P(i32), P(i32), P(i64), P(i32)]),
+        "fw_host_count_record_fold": (i32, [P(abi.fw_config), i64, i64, i64, i64, P(i64), P(i64)]),
         "fw_host_session_add": (i32, [P(abi.fw_config), i64, i64, i64, P(i64), P(i64), P(i64), P(i32), i32, P(i32)]),
         "fw_host_session_add_late": (i32, [P(abi.fw_config), i64, i64, i64, P(i64), P(i64), P(i64), P(i32), i32, P(i32), P(i32)]),
         "fw_host_session_add_gap": (i32, [P(abi.fw_config), i64, i64, i64, i64, P(i64), P(i64), P(i64), P(i32), i32, P(i32)]),
@@ -129,7 +130,7 @@ EXPORTED = ["fw_create", "fw_destroy", "fw_last_error", "fw_abi_version", "fw_de
             "fw_assign_key_groups", "fw_partition_by_dest", "fw_partition_packed", "fw_partition_packed_spill", "fw_partition_packed_spill_dn", "fw_partition_workspace_bytes",
             "fw_valve_local", "fw_valve_select",
             "fw_generate", "fw_host_key_group", "fw_host_assign_key_groups", "fw_host_window_start",
-            "fw_host_next_trigger_watermark", "fw_host_time_op", "fw_host_count_step", "fw_host_session_add", "fw_host_session_add_late", "fw_host_session_add_gap", "fw_host_session_add_gap_late", "fw_host_sql_session_words",
+            "fw_host_next_trigger_watermark", "fw_host_time_op", "fw_host_count_step", "fw_host_count_record_fold", "fw_host_session_add", "fw_host_session_add_late", "fw_host_session_add_gap", "fw_host_session_add_gap_late", "fw_host_sql_session_words",
             "fw_host_sql_session_add", "fw_host_sql_session_result", "fw_late_records", "fw_first_element_events",
             "fw_push_device_key_rows", "fw_key_row_images", "fw_host_key_row_image_lengths", "fw_host_key_row_images",
             "fw_host_key_row_image_hash"]

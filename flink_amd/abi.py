@@ -29,6 +29,7 @@ WIN_SESSION = 4  # DataStream EventTimeSessionWindows.withGap: size_ms carries t
 WIN_SESSION_DYNAMIC = 5  # ... withDynamicGap: value column 1 carries each element's gap, size_ms the largest allowed
 WIN_SESSION_LATENESS = 6  # ... withGap and allowedLateness >= 0: fired sessions are retained and re-fire on late elements
 WIN_SESSION_DYNAMIC_LATENESS = 7  # ... withDynamicGap and allowedLateness >= 0: both of the above
+WIN_COUNT_RECORD = 8  # DataStream countWindow emitting whole records: sum / min / max on a record's field, minBy / maxBy
 # fw_agg_kind
 AGG_COUNT_STAR = 0
 AGG_COUNT = 1
@@ -271,6 +272,8 @@ def set_shift_zone(c, zone):
 def result_columns(cfg):
     """Result value columns of an operator: one per aggregate, or (LOCAL phase) the local
     accumulator fields -- COUNT(*) / COUNT / SUM / MIN / MAX: one, AVG: sum and count."""
+    if cfg.window_kind == WIN_COUNT_RECORD:  # values[0] the aggregate, values[1] the record's arrival ordinal
+        return 2
     if cfg.agg_phase != PHASE_LOCAL:
         return cfg.n_aggs
     return sum(2 if cfg.aggs[i].kind == AGG_AVG else 1 for i in range(cfg.n_aggs))

@@ -139,7 +139,7 @@ static std::atomic<int64_t> g_mg_path[2];
 
 struct fw_handle {
     fw_config cfg;
-    CountOp cw;  // FW_WIN_COUNT: the count-window state (cw.on); the time-window members below stay unused
+    CountOp cw;  // FW_WIN_COUNT / FW_WIN_COUNT_RECORD (cw.rec): the count-window state (cw.on); the time-window members below stay unused
     SessionOp sw;  // FW_WIN_SESSION: the session-window state (sw.on), likewise
     hipStream_t stream = nullptr;
     WinDesc win{};
@@ -527,7 +527,7 @@ int validate_and_plan(fw_handle* h) {
     if (c.parallelism < 1 || c.parallelism > c.max_parallelism) return fail(FW_E_INVALID, "parallelism out of range");
     if (c.subtask_index < 0 || c.subtask_index >= c.parallelism) return fail(FW_E_INVALID, "subtask_index out of range");
     if (c.key_hash < FW_KEYHASH_LONG || c.key_hash > FW_KEYHASH_KEYROW) return fail(FW_E_INVALID, "bad key_hash");
-    if (c.window_kind == FW_WIN_COUNT) {  // count windows: a plan of their own (fw_count.hip)
+    if (c.window_kind == FW_WIN_COUNT || c.window_kind == FW_WIN_COUNT_RECORD) {  // count windows: a plan of their own (fw_count.hip)
         int rc = cw_plan(c, &h->cw);
         if (rc) return rc;
         h->ks = h->cw.ks;
@@ -1357,6 +1357,11 @@ extern "C" {
 // fw_push_device_packed_segments; fw_advance_device likewise): a session handle has them iff its
 // configuration has parallelism > 1 -- only such a handle has an exchange in front of it.  One of
 // parallelism 1 refuses them as ever, and so does every count handle.
+// A record count handle (FW_WIN_COUNT_RECORD) has no key-group checkpoint and no exchange path yet: a
+// restored key group's records would have to be re-numbered under fresh ordinals.
+#define CW_REFUSE_RECORD(h, name)                                                                                       \
+    if ((h)->cw.on && (h)->cw.rec)                                                                                      \
+        return fail(FW_E_INVALID, name ": not for record count windows (FW_WIN_COUNT_RECORD: retained records are not re-numbered)")
 #define CW_REFUSE_EXCHANGE(h, name)                                              \
     if ((h)->cw.on) return fail(FW_E_INVALID, name ": not for count windows");   \
     if ((h)->sw.on && (h)->cfg.parallelism <= 1) return fail(FW_E_INVALID, name ": not for session windows")
@@ -1761,6 +1766,7 @@ int fw_push_device_packed_segments(fw_handle* h, int32_t n_segs, int64_t seg_len
 // refusing them.  Only a count handle of parallelism > 1 has an exchange in front of it.
 #define CW_ONLY_EXCHANGE(h, name)                                                                                  \
     if ((h)->sw.on) return fail(FW_E_INVALID, name ": not for session windows (count windows only)");              \
+    CW_REFUSE_RECORD(h, name);                                                                                     \
     if (!(h)->cw.on) return fail(FW_E_INVALID, name ": not for time windows (count windows only)");                \
     if ((h)->cfg.parallelism <= 1)                                                                                 \
         return fail(FW_E_INVALID, name ": a count handle of parallelism 1 has no keyBy exchange in front of it")
@@ -1887,7 +1893,9 @@ struct FoldedOut {
     int64_t out_cap;
 };
 static FoldedOut folded_out(fw_handle* h) {
-    if (h->cw.on) return {h->cw.out_key, h->cw.out_ws, h->cw.out_we, {h->cw.out_val}, 1, h->cw.out_ord, h->cw.out_null, false, h->cw.out_cap};
+    if (h->cw.on)  // (a record handle: values[1] is the ordinal of the record each row is built from)
+        return {h->cw.out_key, h->cw.out_ws, h->cw.out_we, {h->cw.out_val, h->cw.out_rord}, h->cw.rec ? 2 : 1, h->cw.out_ord, h->cw.out_null,
+                false, h->cw.out_cap};
     FoldedOut w{h->sw.out_key, h->sw.out_ws, h->sw.out_we, {}, h->sw.n_out, nullptr, h->sw.out_null, h->sw.d.sql != 0, h->sw.out_cap};
     for (int g = 0; g < w.n_val; g++) w.val[g] = h->sw.out_val[g];
     return w;
@@ -2209,15 +2217,22 @@ int fw_results_ready(fw_handle* h, fw_result* out) {
 
 int fw_first_element_events(fw_handle* h, fw_ordinal_events* out) {
     if (!h || !out) return fail(FW_E_INVALID, "null argument");
-    CW_REFUSE(h, "fw_first_element_events");
+    const bool rec = h->cw.on && h->cw.rec;  // a record count handle's events: the ordinals its ring slots hold
+    if (!rec) {
+        CW_REFUSE(h, "fw_first_element_events");
+    }
     memset(out, 0, sizeof *out);
-    if (!h->ordev_cap) return fail(FW_E_STATE, "the operator does not track first elements (ds_first_ordinals = 0)");
+    const int64_t* ordev = rec ? h->cw.ordev : h->ordev;
+    const int64_t ordev_cap = rec ? h->cw.ordev_cap : h->ordev_cap;
+    if (!ordev_cap) return fail(FW_E_STATE, "the operator does not track first elements (ds_first_ordinals = 0)");
     Ctrl c;
     int rc = read_ctrl(h, &c);
-    if (rc) return rc;
-    const int64_t n = std::min<int64_t>(c.n_ordev, h->ordev_cap);
+    // (a record count handle: an overflow stays readable -- the events that fit, FW_ERRF_ORDEV in fw_get_stats;
+    // fw_results keeps failing on the error bit)
+    if (rc && !(rec && c.error == ERR_ORDEV)) return rc;
+    const int64_t n = std::min<int64_t>(c.n_ordev, ordev_cap);
     std::vector<int64_t> raw((size_t)n);
-    if (n) HIP_TRY(hipMemcpy(raw.data(), h->ordev, (size_t)n * 8, hipMemcpyDeviceToHost));
+    if (n) HIP_TRY(hipMemcpy(raw.data(), ordev, (size_t)n * 8, hipMemcpyDeviceToHost));
     const int64_t zero = 0;
     HIP_TRY(hipMemcpy(&h->ctrl->n_ordev, &zero, 8, hipMemcpyHostToDevice));
     h->ev_retain.clear();
@@ -2801,6 +2816,7 @@ static const uint64_t KG_MAGIC = 0x464c4b574b473033ull;  // "FLKWKG03"
 
 int fw_snapshot_key_group(fw_handle* h, int32_t key_group, void* buf, int64_t capacity, int64_t* size) {
     if (!h || !size) return fail(FW_E_INVALID, "null argument");
+    CW_REFUSE_RECORD(h, "fw_snapshot_key_group");
     if (h->cw.on) {
         if (key_group < 0) return fail(FW_E_INVALID, "key group %d is not owned by this subtask", key_group);
         h->cw.watermark = h->host_cur;
@@ -2850,6 +2866,7 @@ int fw_snapshot_key_group(fw_handle* h, int32_t key_group, void* buf, int64_t ca
 
 int fw_restore_key_group(fw_handle* h, const void* buf, int64_t size) {
     if (!h || !buf) return fail(FW_E_INVALID, "null argument");
+    CW_REFUSE_RECORD(h, "fw_restore_key_group");
     if (h->cw.on) return cw_restore(&h->cw, true, buf, size);
     if (h->sw.on) {
         // (lateness: the blob's watermark must be the handle's, which is Ctrl::cur once advanced from the device)
@@ -3629,13 +3646,31 @@ int fw_host_time_op(const fw_config* cfg, int32_t what, int64_t x, int64_t* out)
 int fw_host_count_step(const fw_config* cfg, int64_t index, int64_t* slice, int32_t* ring_slot, int32_t* fires,
                        int64_t* window_start, int32_t* n_slices) {
     if (!cfg || !slice || !ring_slot || !fires || !window_start || !n_slices) return fail(FW_E_INVALID, "null argument");
-    if (cfg->window_kind != FW_WIN_COUNT) return fail(FW_E_INVALID, "fw_host_count_step needs a FW_WIN_COUNT configuration");
+    if (cfg->window_kind != FW_WIN_COUNT && cfg->window_kind != FW_WIN_COUNT_RECORD)
+        return fail(FW_E_INVALID, "fw_host_count_step needs a FW_WIN_COUNT configuration (or FW_WIN_COUNT_RECORD)");
     if (index < 0) return fail(FW_E_INVALID, "negative element index");
     fw_handle h;
     h.cfg = *cfg;
     const int rc = validate_and_plan(&h);
     if (rc) return rc;
     count_step(h.cw.d, index, slice, ring_slot, fires, window_start, n_slices);
+    return FW_OK;
+}
+
+int fw_host_count_record_fold(const fw_config* cfg, int64_t a_val, int64_t a_ord, int64_t b_val, int64_t b_ord, int64_t* out_val,
+                              int64_t* out_ord) {
+    if (!cfg || !out_val || !out_ord) return fail(FW_E_INVALID, "null argument");
+    if (cfg->window_kind != FW_WIN_COUNT_RECORD) return fail(FW_E_INVALID, "fw_host_count_record_fold needs a FW_WIN_COUNT_RECORD configuration");
+    fw_handle h;
+    h.cfg = *cfg;
+    const int rc = validate_and_plan(&h);
+    if (rc) return rc;
+    const CountOp& w = h.cw;
+    uint64_t v, o;
+    count_record_fold(w.d.op, w.mode, w.vtype == FW_T_F64, (uint64_t)a_val, (uint64_t)a_ord, (uint64_t)b_val, (uint64_t)b_ord, &v, &o);
+    if (w.vtype == FW_T_I32 && w.d.op == CW_ADD_I) v = (uint64_t)(int64_t)(int32_t)(uint32_t)v;  // as a result row carries it
+    *out_val = (int64_t)v;
+    *out_ord = (int64_t)o;
     return FW_OK;
 }
 

@@ -64,6 +64,30 @@ FW_HD uint64_t count_fold(int32_t op, uint64_t a, uint64_t b) {
     }
 }
 
+// ---- record-shaped count windows (FW_WIN_COUNT_RECORD): every partial aggregate travels with the
+// arrival ordinal of one element.  Value words stay raw here (a DOUBLE is compared through dkey, never
+// stored as one), so a NaN keeps its payload and the fold is the reducer's own:
+//   CR_FIRST     sum / min / max (SumAggregator, ComparableAggregator byAggregate = false): value1 with
+//                the field set -- the ordinal is the older side's; min / max keep the older field only
+//                when it is strictly extremal (isExtremal), else take the newer one's
+//   CR_BY_FIRST  minBy / maxBy(field, first = true): the pair with the extremal field, ties to the older
+//   CR_BY_LAST   minBy / maxBy(field, first = false): ties to the newer
+enum CountRecMode : int32_t { CR_FIRST = 0, CR_BY_FIRST = 1, CR_BY_LAST = 2 };
+
+FW_HD void count_record_fold(int32_t op, int32_t mode, bool dbl, uint64_t av, uint64_t ao, uint64_t bv, uint64_t bo,
+                             uint64_t* ov, uint64_t* oo) {
+    if (op == CW_ADD_I || op == CW_ADD_F) {
+        *ov = count_fold(op, av, bv);
+        *oo = ao;
+        return;
+    }
+    const int64_t ka = dbl ? dkey(av) : (int64_t)av, kb = dbl ? dkey(bv) : (int64_t)bv;
+    const bool a_strict = op == CW_MIN ? ka < kb : ka > kb;
+    const bool keep_a = a_strict || (mode == CR_BY_FIRST && ka == kb);
+    *ov = keep_a ? av : bv;
+    *oo = (mode == CR_FIRST || keep_a) ? ao : bo;
+}
+
 // the table's own slot hash of a key inside its superbucket (not a Flink-visible hash)
 FW_HD uint32_t count_slot_hash(int64_t key, uint32_t mask) { return (uint32_t)mix64((uint64_t)key) & mask; }
 
@@ -71,7 +95,8 @@ constexpr int CW_TILE = FD_TILE;                    // rows per tile = threads p
 constexpr int64_t CW_CLAIMED = INT64_MIN;           // count word of an entry claimed in the running tile
 
 // Per-handle state of a count operator.  The key table is open addressed, partitioned by
-// superbucket: entry e of superbucket sb is table[(sb * cap_e + e) * pwe ..]: key, count, ring[R].
+// superbucket: entry e of superbucket sb is table[(sb * cap_e + e) * pwe ..]: key, count, ring[R]; a
+// record handle (rec) adds ord[R], the ordinal beside each ring slot's aggregate.
 // count == 0 marks an empty slot (a key enters the table with its first element).
 struct CountOp {
     bool on = false;
@@ -81,7 +106,10 @@ struct CountOp {
     int32_t is_count = 0;   // COUNT_STAR: every element counts 1, no value column is read
     int32_t val_col = 0;    // value column the aggregate reads
     int32_t cap_e = 0;      // table slots per superbucket (power of two)
-    int32_t pwe = 0;        // words per entry: 2 + R
+    int32_t pwe = 0;        // words per entry: 2 + R (rec: 2 + 2R)
+    int32_t rec = 0;        // FW_WIN_COUNT_RECORD
+    int32_t mode = 0;       // rec: CountRecMode
+    int32_t agg_sig = 0;    // rec: aggregate kind << 8 | flags (the snapshot fingerprint's part)
     int64_t out_cap = 0;
     hipStream_t stream = nullptr;  // the handle's
     Ctrl* ctrl = nullptr;          // the handle's control block: out_count[0], fired, live_entries, error
@@ -94,11 +122,14 @@ struct CountOp {
     uint64_t* out_val = nullptr;
     int64_t* out_ord = nullptr;
     uint32_t* out_null = nullptr;  // zeros
+    uint64_t* out_rord = nullptr;  // rec: the ordinal of the record each result row is built from
+    int64_t* ordev = nullptr;      // rec: retain / release events (ORDEV_RELEASE | ordinal) since the last read
+    int64_t ordev_cap = 0;         // 2 * max_batch_rows: a row appends at most a release and a retain
     int64_t push_seq = 0;
     int64_t watermark = INT64_MIN;
 };
 
-// validation + plan of a FW_WIN_COUNT configuration; no device call
+// validation + plan of a FW_WIN_COUNT / FW_WIN_COUNT_RECORD configuration; no device call
 int cw_plan(const fw_config& c, CountOp* op);
 int cw_allocate(CountOp* op, hipStream_t stream, Ctrl* ctrl);
 void cw_free(CountOp* op);

@@ -5,12 +5,16 @@
 //   k_cw_fold     one workgroup per superbucket walks its segment in arrival order, a tile at a time
 // No workgroup waits on another: the only cross-workgroup traffic is counters (atomic adds).
 // Behind the N > 1 keyBy exchange (cw_push_segments) the partition is fd_partition_segments over the
-// padded receive buffer and the fold the strided instance k_cw_fold<true>; buffer position order is
+// padded receive buffer and the fold the strided instance k_cw_fold<true, false>; buffer position order is
 // the arrival order.
+// A record handle (FW_WIN_COUNT_RECORD) launches k_cw_fold<false, true>: the same body with an ordinal
+// beside every value word -- in the scan, the fire loop and the write-back -- and the retain / release
+// events of the ordinals the ring holds.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
 #include <cstring>
+#include <type_traits>
 #include <vector>
 
 #include "fw_count.h"
@@ -36,14 +40,34 @@ struct CwFoldArgs {
     int64_t ord_base;  // push_seq << 32 | row offset of this launch within its call
     int32_t stride;    // the device form (DEV): key and value word of row r at key[r * stride], val[r * stride]
 };
+// the record instance (REC) takes these on top; the other instances keep CwFoldArgs as their whole argument
+struct CwRecFoldArgs : CwFoldArgs {
+    int32_t mode;  // CountRecMode
+    uint64_t* out_rord;
+    int64_t* ordev;
+    int64_t ordev_cap;
+};
+template <bool REC>
+using CwArgs = std::conditional_t<REC, CwRecFoldArgs, CwFoldArgs>;
+
+// what the record instance keeps in LDS on top of the one body's; the other instances hold nothing
+template <bool REC>
+struct CwRecLds {};
+template <>
+struct CwRecLds<true> {
+    uint32_t n_ev;  // the tile's retain / release events
+    unsigned long long ev_base;
+};
 
 // DEV: the device form, behind the N > 1 keyBy exchange (cw_push_segments): perm / seg name the live
 // rows fd_partition_segments selected from a padded receive buffer -- a padding row is in no segment,
 // so it is never read -- and a row's words are strided (1: columns, row_words: packed rows).  Everything
 // else is the one body; the instance without DEV is the one a direct push launches.
+// REC: the record instance.  A value word stays raw (count_record_fold compares a DOUBLE through dkey),
+// a row's ordinal is ord_base + its row index, a ring slot's ordinal lies R words behind its value.
 #define CW_AT(row) (DEV ? (size_t)(row) * (size_t)a.stride : (row))
-template <bool DEV>
-__global__ __launch_bounds__(CW_TILE) void k_cw_fold(CwFoldArgs a) {
+template <bool DEV, bool REC>
+__global__ __launch_bounds__(CW_TILE) void k_cw_fold(CwArgs<REC> a) {
     __shared__ uint64_t sk[CW_TILE];     // sorted keys
     __shared__ uint32_t sp[CW_TILE];     // their positions in the tile (arrival order)
     __shared__ uint64_t pv[CW_TILE];     // by position: value word, row index
@@ -56,6 +80,9 @@ __global__ __launch_bounds__(CW_TILE) void k_cw_fold(CwFoldArgs a) {
     __shared__ int32_t hlen[CW_TILE];
     __shared__ uint32_t n_fire, n_new;
     __shared__ unsigned long long fire_base;
+    __shared__ CwRecLds<REC> rl;
+    // REC: the ordinal beside sv[].  pv[] is dead once the scan has taken its values, so it holds them.
+    [[maybe_unused]] uint64_t(&so)[CW_TILE] = pv;
 
     const int t = threadIdx.x;
     const CountDesc& d = a.d;
@@ -63,7 +90,8 @@ __global__ __launch_bounds__(CW_TILE) void k_cw_fold(CwFoldArgs a) {
     const uint32_t mask = (uint32_t)a.cap_e - 1u;
     const int64_t seg0 = a.seg[blockIdx.x], seg1 = a.seg[blockIdx.x + 1];
     uint64_t* tab = a.table + (size_t)blockIdx.x * a.cap_e * pwe;
-    const bool dbl_cmp = a.vtype == FW_T_F64 && (op == CW_MIN || op == CW_MAX);
+    const bool dbl_cmp = !REC && a.vtype == FW_T_F64 && (op == CW_MIN || op == CW_MAX);
+    [[maybe_unused]] const bool dbl = a.vtype == FW_T_F64;
 
     for (int64_t base = seg0; base < seg1; base += CW_TILE) {
         const int nt = (int)(seg1 - base < CW_TILE ? seg1 - base : CW_TILE);
@@ -71,6 +99,7 @@ __global__ __launch_bounds__(CW_TILE) void k_cw_fold(CwFoldArgs a) {
         if (t == 0) {
             n_fire = 0;
             n_new = 0;
+            if constexpr (REC) rl.n_ev = 0;
         }
         if (t < nt) {
             const uint32_t row = a.perm[base + t];
@@ -151,18 +180,31 @@ __global__ __launch_bounds__(CW_TILE) void k_cw_fold(CwFoldArgs a) {
             sv[t] = valid ? pv[sp[t]] : 0;
             sf[t] = (!valid || rank == 0 || idx - sl * d.g == 0) ? 1u : 0u;
         }
+        if constexpr (REC) {
+            __syncthreads();  // every pv[] read above is done
+            if (t < n2) so[t] = valid ? (uint64_t)a.ord_base + prow[sp[t]] : 0;
+        }
         __syncthreads();
         for (int dd = 1; dd < n2; dd <<= 1) {
             const bool take = t < n2 && t >= dd && !sf[t];
             uint64_t ov = 0;
+            [[maybe_unused]] uint64_t oo = 0;
             uint32_t of = 0;
             if (take) {
                 ov = sv[t - dd];
                 of = sf[t - dd];
+                if constexpr (REC) oo = so[t - dd];
             }
             __syncthreads();
             if (take) {
-                sv[t] = count_fold(op, ov, sv[t]);
+                if constexpr (REC) {
+                    uint64_t rv, ro;
+                    count_record_fold(op, a.mode, dbl, ov, oo, sv[t], so[t], &rv, &ro);
+                    sv[t] = rv;
+                    so[t] = ro;
+                } else {
+                    sv[t] = count_fold(op, ov, sv[t]);
+                }
                 sf[t] = of;
             }
             __syncthreads();
@@ -172,6 +214,7 @@ __global__ __launch_bounds__(CW_TILE) void k_cw_fold(CwFoldArgs a) {
         // the tile, the tile's own from the scan (the last row of slice j of this key run)
         const bool fire = live && fires;
         uint64_t acc = 0;
+        [[maybe_unused]] uint64_t acc_o = 0;  // (acc_o: REC, the ordinal of the record the row is built from)
         uint32_t loc = 0;
         if (fire) {
             bool first = true;
@@ -180,13 +223,32 @@ __global__ __launch_bounds__(CW_TILE) void k_cw_fold(CwFoldArgs a) {
                 int rj = rs - k % R;
                 if (rj < 0) rj += R;
                 uint64_t part;
+                [[maybe_unused]] uint64_t part_o = 0;
                 if (j < s0k) {
                     part = tab[(size_t)slot * pwe + 2 + rj];
+                    if constexpr (REC) part_o = tab[(size_t)slot * pwe + 2 + R + rj];
                 } else {
-                    part = sv[hi + (int)((j + 1) * d.g - 1 - cnt0)];
-                    if (j == s0k && partial0) part = count_fold(op, tab[(size_t)slot * pwe + 2 + rj], part);
+                    const int at = hi + (int)((j + 1) * d.g - 1 - cnt0);
+                    part = sv[at];
+                    if constexpr (REC) {
+                        part_o = so[at];
+                        if (j == s0k && partial0)
+                            count_record_fold(op, a.mode, dbl, tab[(size_t)slot * pwe + 2 + rj], tab[(size_t)slot * pwe + 2 + R + rj],
+                                              part, part_o, &part, &part_o);
+                    } else {
+                        if (j == s0k && partial0) part = count_fold(op, tab[(size_t)slot * pwe + 2 + rj], part);
+                    }
                 }
-                acc = first ? part : count_fold(op, acc, part);
+                if constexpr (REC) {
+                    if (first) {
+                        acc = part;
+                        acc_o = part_o;
+                    } else {
+                        count_record_fold(op, a.mode, dbl, acc, acc_o, part, part_o, &acc, &acc_o);
+                    }
+                } else {
+                    acc = first ? part : count_fold(op, acc, part);
+                }
                 first = false;
             }
             loc = atomicAdd(&n_fire, 1u);
@@ -211,6 +273,7 @@ __global__ __launch_bounds__(CW_TILE) void k_cw_fold(CwFoldArgs a) {
                 a.out_ws[o] = ws;
                 a.out_we[o] = idx + 1;
                 a.out_ord[o] = a.ord_base + (int64_t)prow[sp[t]];
+                if constexpr (REC) a.out_rord[o] = acc_o;
             } else {
                 atomicOr(&a.ctrl->error, ERR_OUTPUT);
             }
@@ -218,16 +281,56 @@ __global__ __launch_bounds__(CW_TILE) void k_cw_fold(CwFoldArgs a) {
 
         // ---- write back (every ring read of the fires is behind the barriers above): the last row
         // of each (key, slice) run stores the slice, unless a later slice of the tile took its slot
+        [[maybe_unused]] int64_t ev[2] = {0, 0};  // REC: this row's events
+        [[maybe_unused]] uint32_t n_ev = 0;
         if (live) {
             const int len = hlen[hi];
             const int64_t s_last = (int64_t)udiv((uint64_t)(cnt0 + len - 1), d.g_div);
             const bool slice_end = rank == len - 1 || idx + 1 == (sl + 1) * d.g;
             if (slice_end && sl + R > s_last) {
                 uint64_t part = sv[t];
-                if (sl == s0k && partial0) part = count_fold(op, tab[(size_t)slot * pwe + 2 + rs], part);
+                if constexpr (REC) {
+                    uint64_t part_o = so[t];
+                    const uint64_t old_o = tab[(size_t)slot * pwe + 2 + R + rs];
+                    if (sl == s0k && partial0)
+                        count_record_fold(op, a.mode, dbl, tab[(size_t)slot * pwe + 2 + rs], old_o, part, part_o, &part, &part_o);
+                    tab[(size_t)slot * pwe + 2 + R + rs] = part_o;
+                    // What the slot held before the tile, from the counts alone: the key's slices then
+                    // were [max(0, q - R + 1), q] with q = (cnt0 - 1) / g, each in its own slot, so slot rs
+                    // held the one slice of them congruent to rs -- this slice begun earlier, or an older
+                    // one this store evicts -- unless that slice would lie below 0.
+                    bool held = false;
+                    if (cnt0 > 0) {
+                        const uint64_t q = udiv((uint64_t)(cnt0 - 1), d.g_div);
+                        int back = (int)(q - udiv(q, d.r_div) * (uint64_t)R) - rs;
+                        if (back < 0) back += R;
+                        held = (int64_t)q - back >= 0;
+                    }
+                    if (!held) {
+                        ev[0] = (int64_t)part_o;
+                        n_ev = 1;
+                    } else if (old_o != part_o) {
+                        ev[0] = ORDEV_RELEASE | (int64_t)old_o;
+                        ev[1] = (int64_t)part_o;
+                        n_ev = 2;
+                    }
+                } else {
+                    if (sl == s0k && partial0) part = count_fold(op, tab[(size_t)slot * pwe + 2 + rs], part);
+                }
                 tab[(size_t)slot * pwe + 2 + rs] = part;
             }
             if (rank == len - 1) tab[(size_t)slot * pwe + 1] = (uint64_t)(cnt0 + len);
+        }
+        if constexpr (REC) {  // one claim of the event buffer per tile
+            const uint32_t at = n_ev ? atomicAdd(&rl.n_ev, n_ev) : 0u;
+            __syncthreads();
+            if (t == 0 && rl.n_ev) rl.ev_base = atomicAdd((unsigned long long*)&a.ctrl->n_ordev, (unsigned long long)rl.n_ev);
+            __syncthreads();
+            for (uint32_t i = 0; i < n_ev; i++) {
+                const unsigned long long o = rl.ev_base + at + i;
+                if (o < (unsigned long long)a.ordev_cap) a.ordev[o] = ev[i];
+                else atomicOr(&a.ctrl->error, ERR_ORDEV);
+            }
         }
         __threadfence_block();
         __syncthreads();
@@ -246,16 +349,31 @@ int64_t cw_gcd(int64_t a, int64_t b) {
 }  // namespace
 
 int cw_plan(const fw_config& c, CountOp* op) {
-    if (c.api != FW_API_DATASTREAM) return set_error(FW_E_INVALID, "FW_WIN_COUNT (countWindow) is a DataStream window: api must be FW_API_DATASTREAM");
+    const bool rec = c.window_kind == FW_WIN_COUNT_RECORD;
+    if (c.api != FW_API_DATASTREAM)
+        return set_error(FW_E_INVALID, "%s (countWindow) is a DataStream window: api must be FW_API_DATASTREAM",
+                         rec ? "FW_WIN_COUNT_RECORD" : "FW_WIN_COUNT");
     if (c.n_aggs != 1) return set_error(FW_E_INVALID, "count windows take one aggregation (n_aggs == 1), got %d", c.n_aggs);
     const fw_agg_desc& g = c.aggs[0];
-    if (g.kind == FW_AGG_MINBY || g.kind == FW_AGG_MAXBY)
-        return set_error(FW_E_INVALID, "count windows: minBy / maxBy run on the reference operator");
-    if (g.kind != FW_AGG_SUM && g.kind != FW_AGG_MIN && g.kind != FW_AGG_MAX && g.kind != FW_AGG_COUNT_STAR)
-        return set_error(FW_E_INVALID, "count windows: aggregate kind %d is not sum / min / max / count", g.kind);
+    const bool by = g.kind == FW_AGG_MINBY || g.kind == FW_AGG_MAXBY;
+    if (rec) {
+        if (g.kind == FW_AGG_COUNT_STAR)
+            return set_error(FW_E_INVALID, "record count windows: aggs[0].kind FW_AGG_COUNT_STAR has no record-shaped form (DataStream has no such count)");
+        if (g.kind != FW_AGG_SUM && g.kind != FW_AGG_MIN && g.kind != FW_AGG_MAX && !by)
+            return set_error(FW_E_INVALID, "record count windows: aggs[0].kind %d is not sum / min / max / minBy / maxBy", g.kind);
+        if (g.flags & ~FW_AGGF_LAST) return set_error(FW_E_INVALID, "record count windows: bad aggs[0].flags %d", g.flags);
+        if (g.flags && !by)
+            return set_error(FW_E_INVALID, "record count windows: aggs[0].flags FW_AGGF_LAST is the tie rule of minBy / maxBy only");
+        if (!c.ds_first_ordinals)
+            return set_error(FW_E_INVALID, "record count windows name their records by arrival ordinal (ds_first_ordinals must be 1)");
+    } else {
+        if (by) return set_error(FW_E_INVALID, "count windows: minBy / maxBy run on the reference operator");
+        if (g.kind != FW_AGG_SUM && g.kind != FW_AGG_MIN && g.kind != FW_AGG_MAX && g.kind != FW_AGG_COUNT_STAR)
+            return set_error(FW_E_INVALID, "count windows: aggregate kind %d is not sum / min / max / count", g.kind);
+        if (g.flags) return set_error(FW_E_INVALID, "count windows: bad aggregate flags %d", g.flags);
+    }
     if (g.type != FW_T_I64 && g.type != FW_T_I32 && g.type != FW_T_F64)
         return set_error(FW_E_INVALID, "count windows: bad aggregate type %d", g.type);
-    if (g.flags) return set_error(FW_E_INVALID, "count windows: bad aggregate flags %d", g.flags);
     op->is_count = g.kind == FW_AGG_COUNT_STAR;
     if (!op->is_count) {
         if (g.input_col < 0 || g.input_col >= c.n_value_cols) return set_error(FW_E_INVALID, "count windows: bad input_col");
@@ -272,7 +390,7 @@ int cw_plan(const fw_config& c, CountOp* op) {
     if (c.offset_ms != 0) return set_error(FW_E_INVALID, "count windows have no offset (offset_ms must be 0)");
     if (c.allowed_lateness_ms != 0) return set_error(FW_E_INVALID, "count windows have no lateness (allowed_lateness_ms must be 0)");
     if (c.late_side_output) return set_error(FW_E_INVALID, "count windows have no late elements (late_side_output must be 0)");
-    if (c.ds_first_ordinals) return set_error(FW_E_INVALID, "count windows are (key, aggregate) shaped (ds_first_ordinals must be 0)");
+    if (c.ds_first_ordinals && !rec) return set_error(FW_E_INVALID, "count windows are (key, aggregate) shaped (ds_first_ordinals must be 0)");
     if (c.nullable_cols) return set_error(FW_E_INVALID, "count windows take no NULL inputs (nullable_cols must be 0)");
     if (c.tz_n != 0) return set_error(FW_E_INVALID, "count windows have no time zone (tz_n must be 0)");
     if (c.agg_phase != FW_PHASE_ONE) return set_error(FW_E_INVALID, "count windows are one-phase (agg_phase must be FW_PHASE_ONE)");
@@ -291,10 +409,17 @@ int cw_plan(const fw_config& c, CountOp* op) {
     d.slide_div = make_udiv((uint64_t)slide);
     d.r_div = make_udiv((uint64_t)d.R);
     const bool f = g.type == FW_T_F64;
-    d.op = op->is_count ? CW_ADD_I : g.kind == FW_AGG_SUM ? (f ? CW_ADD_F : CW_ADD_I) : g.kind == FW_AGG_MIN ? CW_MIN : CW_MAX;
+    d.op = op->is_count             ? CW_ADD_I
+           : g.kind == FW_AGG_SUM ? (f ? CW_ADD_F : CW_ADD_I)
+           : g.kind == FW_AGG_MIN || g.kind == FW_AGG_MINBY ? CW_MIN
+                                                            : CW_MAX;
     op->vtype = g.type;
     op->val_col = op->is_count ? 0 : g.input_col;
-    op->pwe = 2 + d.R;
+    op->rec = rec;
+    op->mode = !by ? CR_FIRST : (g.flags & FW_AGGF_LAST) ? CR_BY_LAST : CR_BY_FIRST;
+    op->agg_sig = rec ? (g.kind << 8 | g.flags) : 0;
+    op->pwe = rec ? 2 + 2 * d.R : 2 + d.R;
+    op->ordev_cap = rec ? 2 * c.max_batch_rows : 0;
 
     KeySpace& ks = op->ks;
     const int rc = fd_plan_keyspace(c, "count windows", &ks, &op->part);
@@ -325,6 +450,10 @@ int cw_allocate(CountOp* op, hipStream_t stream, Ctrl* ctrl) {
     if ((rc = fd_dalloc(&op->out_ord, oc))) return rc;
     if ((rc = fd_dalloc(&op->out_null, oc))) return rc;
     FD_TRY(hipMemsetAsync(op->out_null, 0, oc * 4, stream));
+    if (op->rec) {
+        if ((rc = fd_dalloc(&op->out_rord, oc))) return rc;
+        if ((rc = fd_dalloc(&op->ordev, (size_t)op->ordev_cap))) return rc;
+    }
     return FW_OK;
 }
 
@@ -337,6 +466,8 @@ void cw_free(CountOp* op) {
     hipFree(op->out_val);
     hipFree(op->out_ord);
     hipFree(op->out_null);
+    hipFree(op->out_rord);
+    hipFree(op->ordev);
 }
 
 // the folds of one call: n rows at d_key[i * stride], d_val[i * stride], split into launches of
@@ -346,6 +477,8 @@ static int cw_fold_call(CountOp* op, int64_t n, const int64_t* d_key, const int3
                         const int64_t* d_seg_counts, int64_t seg_len) {
     if (n >= (1ll << 32) || op->push_seq >= (1ll << 30))
         return set_error(FW_E_INVALID, "arrival ordinals need < 2^32 rows per call and < 2^30 calls");
+    if (op->rec && (d_seg_counts || n > op->part.cap_rows))  // the event buffers hold one push of max_batch_rows rows
+        return set_error(FW_E_INVALID, "record count windows: a push takes at most max_batch_rows (%lld) rows, as columns", (long long)op->part.cap_rows);
     hipStream_t s = op->stream;
     const int64_t cap_rows = op->part.cap_rows;
     for (int64_t o = 0; o < n; o += cap_rows) {
@@ -354,7 +487,7 @@ static int cw_fold_call(CountOp* op, int64_t n, const int64_t* d_key, const int3
                                                             d_khash ? d_khash + o : nullptr, d_seg_counts, seg_len, o)
                                     : fd_partition(op->part, op->ks, op->ctrl, s, m, d_key + o, d_khash ? d_khash + o : nullptr);
         if (rc) return rc;
-        CwFoldArgs fa{};
+        CwRecFoldArgs fa{};
         fa.key = d_key + o * stride;
         fa.val = op->is_count ? nullptr : d_val + o * stride;
         fa.perm = op->part.perm;
@@ -374,8 +507,13 @@ static int cw_fold_call(CountOp* op, int64_t n, const int64_t* d_key, const int3
         fa.out_cap = op->out_cap;
         fa.ord_base = (op->push_seq << 32) + o;
         fa.stride = stride;
-        if (d_seg_counts) hipLaunchKernelGGL(k_cw_fold<true>, dim3(op->ks.n_sb), dim3(CW_TILE), 0, s, fa);
-        else hipLaunchKernelGGL(k_cw_fold<false>, dim3(op->ks.n_sb), dim3(CW_TILE), 0, s, fa);
+        fa.mode = op->mode;
+        fa.out_rord = op->out_rord;
+        fa.ordev = op->ordev;
+        fa.ordev_cap = op->ordev_cap;
+        if (op->rec) hipLaunchKernelGGL((k_cw_fold<false, true>), dim3(op->ks.n_sb), dim3(CW_TILE), 0, s, fa);
+        else if (d_seg_counts) hipLaunchKernelGGL((k_cw_fold<true, false>), dim3(op->ks.n_sb), dim3(CW_TILE), 0, s, (const CwFoldArgs&)fa);
+        else hipLaunchKernelGGL((k_cw_fold<false, false>), dim3(op->ks.n_sb), dim3(CW_TILE), 0, s, (const CwFoldArgs&)fa);
         FD_TRY(hipGetLastError());
     }
     op->push_seq++;
@@ -406,6 +544,9 @@ struct CwHeader {
 };
 const uint64_t CW_MAGIC = 0x464c4b5743573031ull;     // "FLKWCW01"
 const uint64_t CW_KG_MAGIC = 0x464c4b57434b3031ull;  // "FLKWCK01"
+// a record handle's blob: entries carry ord[R] behind ring[R], CwHeader::reserved the aggregate kind and
+// tie flag (CountOp::agg_sig), so a blob crosses neither to FW_WIN_COUNT nor between tie rules
+const uint64_t CW_REC_MAGIC = 0x464c4b5743523031ull;  // "FLKWCR01"
 }  // namespace
 
 int cw_snapshot(CountOp* op, int32_t key_group, void* buf, int64_t capacity, int64_t* size) {
@@ -437,8 +578,8 @@ int cw_snapshot(CountOp* op, int32_t key_group, void* buf, int64_t capacity, int
     *size = need;
     if (!buf) return FW_OK;
     if (capacity < need) return set_error(FW_E_INVALID, "snapshot buffer too small (%lld < %lld)", (long long)capacity, (long long)need);
-    CwHeader hd{key_group >= 0 ? CW_KG_MAGIC : CW_MAGIC, op->push_seq, watermark, op->d.size, op->d.slide, op->d.op, op->vtype,
-                ks.hash_kind, ks.max_p, op->d.R, key_group, L, 0, n};
+    CwHeader hd{op->rec ? CW_REC_MAGIC : key_group >= 0 ? CW_KG_MAGIC : CW_MAGIC, op->push_seq, watermark, op->d.size, op->d.slide, op->d.op,
+                op->vtype, ks.hash_kind, ks.max_p, op->d.R, key_group, L, op->agg_sig, n};
     memcpy(buf, &hd, sizeof hd);
     if (!ent.empty()) memcpy((char*)buf + sizeof hd, ent.data(), ent.size() * 8);
     return FW_OK;
@@ -450,7 +591,10 @@ int cw_restore(CountOp* op, bool key_group, const void* buf, int64_t size) {
     memcpy(&hd, buf, sizeof hd);
     const KeySpace& ks = op->ks;
     const int L = ks.sb_per_kg_log2, pwe = op->pwe, bw = pwe + 1;
-    if (hd.magic != (key_group ? CW_KG_MAGIC : CW_MAGIC)) return set_error(FW_E_INVALID, "not a count-window %ssnapshot", key_group ? "key-group " : "");
+    if (op->rec && hd.magic != CW_REC_MAGIC) return set_error(FW_E_INVALID, "not a record count-window snapshot (FW_WIN_COUNT_RECORD)");
+    if (!op->rec && hd.magic != (key_group ? CW_KG_MAGIC : CW_MAGIC)) return set_error(FW_E_INVALID, "not a count-window %ssnapshot", key_group ? "key-group " : "");
+    if (hd.reserved != op->agg_sig)
+        return set_error(FW_E_INVALID, "record count-window snapshot of another aggregate or tie rule (aggs[0].kind / flags)");
     if (hd.size != op->d.size || hd.slide != op->d.slide || hd.op != op->d.op || hd.vtype != op->vtype || hd.R != op->d.R ||
         hd.hash_kind != ks.hash_kind || hd.max_p != ks.max_p)
         return set_error(FW_E_INVALID, "count-window snapshot of a different operator configuration");
@@ -479,7 +623,7 @@ int cw_restore(CountOp* op, bool key_group, const void* buf, int64_t size) {
             if (q[1] == 0) {
                 q[0] = e[0];
                 q[1] = e[1];
-                memcpy(q + 2, e + 3, (size_t)op->d.R * 8);
+                memcpy(q + 2, e + 3, (size_t)(pwe - 2) * 8);
                 break;
             }
             if (q[0] == e[0]) return set_error(FW_E_STATE, "key group %d already holds state for a restored key", kg);
@@ -492,6 +636,7 @@ int cw_restore(CountOp* op, bool key_group, const void* buf, int64_t size) {
     if ((rc = fd_restored_ctrl(op->ctrl, key_group, hd.n, hd.watermark, &c))) return rc;
     op->push_seq = key_group ? std::max(op->push_seq, hd.push_seq) : hd.push_seq;
     if (!key_group) op->watermark = hd.watermark;
+    if (op->rec) c.n_ordev = 0;  // the blob's ring is the state of record: the shim restores its retained records with it
     FD_TRY(hipMemcpy(op->ctrl, &c, sizeof c, hipMemcpyHostToDevice));
     return FW_OK;
 }

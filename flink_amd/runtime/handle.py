@@ -582,6 +582,6 @@ def _snapshot_push_seq(blob):
     count-window and session-window blobs keep it right behind their magic)."""
     import struct
     off = {0x464c4b57494e3033: 8 + 16 + 32 + 8, 0x464c4b574b473033: 8 + 24 + 32 + 8,
-           0x464c4b5743573031: 8, 0x464c4b57434b3031: 8,
+           0x464c4b5743573031: 8, 0x464c4b57434b3031: 8, 0x464c4b5743523031: 8,
            0x464c4b5753573031: 8, 0x464c4b5753473031: 8}.get(struct.unpack_from("<Q", blob, 0)[0])
     return struct.unpack_from("<q", blob, off)[0] if off is not None else 0

@@ -206,7 +206,39 @@ typedef enum {
        another size_ms or lateness.  fw_restore_key_group returns FW_E_STATE unless the blob's
        watermark equals the handle's current watermark (fw_initialize_watermark before the first
        key group sets it). */
-    FW_WIN_SESSION_DYNAMIC_LATENESS = 7
+    FW_WIN_SESSION_DYNAMIC_LATENESS = 7,
+    /* v11 (additive), DataStream only: KeyedStream.countWindow emitting whole records -- sum / min / max
+       on one field of a record with further fields (SumAggregator / ComparableAggregator byAggregate =
+       false: the window's OLDEST element with the aggregated field set) and minBy / maxBy (byAggregate =
+       true: the element with the extremal field itself; ties to the earliest element, to the latest
+       with FW_AGGF_LAST).  Recalled, parity unpinned.  FW_WIN_COUNT is untouched.  The configuration is
+       FW_WIN_COUNT's, validated with the same messages, except: ds_first_ordinals must be 1; the one
+       aggregate is SUM / MIN / MAX / MINBY / MAXBY over I64 / I32 / F64 (COUNT_STAR is refused:
+       DataStream has no record-shaped count); FW_AGGF_LAST is accepted on MINBY / MAXBY only.  A DOUBLE
+       field is compared by Double.compareTo and travels as its bits: a NaN keeps its payload, and MIN /
+       MAX take the newer of two equal fields, as the reducer does.
+       A key's state is its count and, per count slice, the aggregate and one arrival ordinal: the slice's
+       first element (SUM / MIN / MAX) or its extremal element under the tie rule (MINBY / MAXBY).
+       fw_results / fw_results_reset return key, window_start, window_end and values[0] as FW_WIN_COUNT
+       does (MINBY / MAXBY: the extremal field), first_ord = the ordinal of the element that TRIGGERED
+       the fire (sorting by it gives the emission order), and values[1] = the ordinal of the RECORD the
+       output is built from: the window's oldest element, or its extremal one.
+       fw_first_element_events tells the shim which records to keep: a retain when a ring slot takes
+       an ordinal, a release of the one it replaces; slices that come and go inside one push raise no
+       event (their elements are in the caller's batch).  A retain always names a row of the current
+       push and an ordinal is held by at most one slot.  After every push the shim reads the results,
+       applies the retains (copying records out of the batch), resolves values[1] from the retained
+       set or the batch, applies the releases, then drops the batch.  The event buffer holds 2 *
+       max_batch_rows events -- what one push can raise; beyond it FW_ERRF_ORDEV is raised, nothing is
+       written past the buffer and fw_first_element_events returns the events that fit.  A push takes
+       at most max_batch_rows rows.
+       fw_snapshot / fw_restore use a blob of their own whose fingerprint carries the aggregate kind and
+       the tie flag: it restores neither into a FW_WIN_COUNT handle nor under another tie rule.  The
+       shim checkpoints its retained records beside it.  Refused with FW_E_INVALID: everything a
+       FW_WIN_COUNT handle refuses except fw_first_element_events, the two count segment pushes
+       (there is no exchange path yet) and fw_snapshot_key_group / fw_restore_key_group (a restored
+       key group's records would need fresh ordinals). */
+    FW_WIN_COUNT_RECORD = 8
 } fw_window_kind;
 
 typedef enum {
@@ -355,7 +387,9 @@ typedef struct {
                                           v11, FW_WIN_COUNT: always filled -- the arrival ordinal of
                                           the element that TRIGGERED the fire; the device's row order
                                           is unspecified, sorting by first_ord gives the order in
-                                          which the reference emits the rows */
+                                          which the reference emits the rows.
+                                          FW_WIN_COUNT_RECORD: the same; the ordinal of the record the
+                                          row is built from is values[1] */
     /* v5, FW_KEYHASH_KEYROW: row i's key row image is key_row_bytes[i * key_row_stride ..
        + key_row_len[i]) (BinaryRowData.pointTo); key[] holds the handle's internal key ids */
     int32_t* key_row_len;
@@ -912,6 +946,15 @@ int fw_host_time_op(const fw_config* cfg, int32_t what, int64_t x, int64_t* out)
    first element arrives.  Returns FW_E_INVALID for a configuration fw_create would reject. */
 int fw_host_count_step(const fw_config* cfg, int64_t index, int64_t* slice, int32_t* ring_slot, int32_t* fires,
                        int64_t* window_start, int32_t* n_slices);
+/* v11 (additive): the pair fold of a FW_WIN_COUNT_RECORD configuration, as the kernel runs it: two
+   partial aggregates of adjacent runs of one key's elements, each with its ordinal, the OLDER run as
+   (a_val, a_ord).  SUM / MIN / MAX: *out_val the reduce of the two fields (an I32 sum narrowed, a
+   DOUBLE as bits), *out_ord = a_ord.  MINBY / MAXBY: the pair with the extremal field under the tie
+   rule.  Associative, so a window folded as count slices equals the element-by-element reduce.
+   fw_host_count_step accepts a FW_WIN_COUNT_RECORD configuration too.  Returns FW_E_INVALID for any
+   other window kind and for a configuration fw_create would reject. */
+int fw_host_count_record_fold(const fw_config* cfg, int64_t a_val, int64_t a_ord, int64_t b_val, int64_t b_ord, int64_t* out_val,
+                              int64_t* out_ord);
 /* v11 (additive): one element of one key against that key's sessions, as the kernels run it
    (WindowOperator.processElement's merging branch, MergingWindowSet.addWindow, TimeWindow.intersects
    / cover, the late test and the aggregate's fold -- the same routines the device code calls).
