@@ -15,38 +15,21 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
-#include <map>
 #include <string>
 #include <thread>
-#include <unordered_map>
 #include <vector>
 
-#include "fw_count.h"
-#include "fw_session.h"
-#include "fw_internal.h"
+#include "fw_handle.h"
 
 using namespace fw;
+
+// this file's spellings of the library's one error function and one HIP check (fw_folded.h)
+#define fail(...) fw::set_error(__VA_ARGS__)
+#define HIP_TRY(expr) FD_TRY(expr)
 
 namespace {
 
 thread_local std::string g_err;
-
-int fail(int code, const char* fmt, ...) __attribute__((format(printf, 2, 3)));
-int fail(int code, const char* fmt, ...) {
-    char buf[512];
-    va_list ap;
-    va_start(ap, fmt);
-    vsnprintf(buf, sizeof buf, fmt, ap);
-    va_end(ap);
-    g_err = buf;
-    return code;
-}
-
-#define HIP_TRY(expr)                                                                          \
-    do {                                                                                       \
-        hipError_t e_ = (expr);                                                                \
-        if (e_ != hipSuccess) return fail(FW_E_DEVICE, "%s: %s", #expr, hipGetErrorString(e_)); \
-    } while (0)
 
 int64_t gcd64(int64_t a, int64_t b) {
     while (b) {
@@ -120,7 +103,7 @@ struct EvTimer final : KTimer {
 
 }  // namespace
 
-// fw_last_error for the translation units beside this one (fw_count.hip)
+// fw_last_error's text, for every translation unit of the library: returns code
 int fw::set_error(int code, const char* fmt, ...) {
     char buf[512];
     va_list ap;
@@ -136,197 +119,6 @@ static std::atomic<int64_t> g_ig_pack_launches{0};
 // superbuckets the GF_TAG merge variants served on the old path [0] and on the tag path [1], over the
 // handles destroyed so far (fw_merge_path_superbuckets(NULL, .))
 static std::atomic<int64_t> g_mg_path[2];
-
-struct fw_handle {
-    fw_config cfg;
-    CountOp cw;  // FW_WIN_COUNT / FW_WIN_COUNT_RECORD (cw.rec): the count-window state (cw.on); the time-window members below stay unused
-    SessionOp sw;  // FW_WIN_SESSION: the session-window state (sw.on), likewise
-    hipStream_t stream = nullptr;
-    WinDesc win{};
-    KeySpace ks{};
-    WordDesc wd{};
-    AggDesc ad{};
-    int nv = 0;
-    int slot_col[MAX_KCOLS] = {};
-    int nw_t = 1;  // template word count (layout stride)
-    int pwe = 4;   // words per state entry: key, slice (HOP block: block start), flags, accumulator words
-    int n_out = 1; // result value columns (aggregates; LOCAL phase: accumulator fields)
-    int64_t cap_rows = 0;     // rows per partial-buffer slot (= max rows per push piece)
-    int64_t chunk_rows = 0;   // rows per ingest chunk (IG_BLOCK * ig_rpt(nw_t))
-    int64_t max_nch = 0;      // ingest chunks per push piece
-    int cap_e = 1024;
-    bool always_flush = false;
-
-    Ctrl* ctrl = nullptr;
-    uint64_t* parts = nullptr;
-    int32_t narrow = 0;          // compact partial rows (IngestArgs::narrow)
-    int32_t pack = 0;            // PF_PACK run rows (IngestArgs::pack)
-    int64_t* slot_base = nullptr;  // [FW_MAX_PENDING] rank base of each pending push
-    uint8_t* ranks = nullptr;      // [FW_MAX_PENDING][cap_rows] rank bytes of compact rows
-    int64_t cell_cols = 0;       // cell_pad(max_nch): cells per superbucket per slot
-    uint32_t* cells = nullptr;   // [FW_MAX_PENDING][cell_cols / 16][n_sb][16] (cell_index)
-    int32_t* slot_nch = nullptr;  // [FW_MAX_PENDING]
-    // runs (IngestArgs::runs): superbucket-contiguous partial rows; run_rows == 0: off
-    int64_t run_rows = 0;
-    int32_t sub_cap = 0;
-    uint64_t* runs = nullptr;
-    uint8_t* run_ranks = nullptr;
-    uint32_t* run_fill = nullptr;
-    uint32_t* run_ovf = nullptr;
-    int32_t* slot_fmt = nullptr;
-    int64_t* treq = nullptr;
-    int64_t treq_cap = 0;
-    uint64_t* lfire = nullptr;   // DataStream late-fire rows
-    int64_t lfire_cap = 0;
-    int64_t* side = nullptr;     // DataStream late side-output rows
-    int64_t side_cap = 0;
-    int64_t* ordev = nullptr;    // DataStream first-element retain / release events
-    int64_t ordev_cap = 0;
-    std::vector<int64_t> ev_retain, ev_release;  // fw_first_element_events copies
-    int32_t push_seq = 0;        // fw_commit / fw_push_device calls (side-output row ids)
-    std::vector<int64_t> tz_utc, tz_off, tz_bound;  // shift-zone table (host copy)
-    int64_t* d_tz = nullptr;     // device copy: [utc | off | bound]
-    std::vector<int64_t> lr_key, lr_ts, lr_seq, lr_row, lr_val[FW_MAX_COLS];  // fw_late_records copies
-    uint64_t* state = nullptr;
-    int32_t* state_count = nullptr;
-    int64_t* sb_min_timer = nullptr;
-    uint8_t* sb_nar = nullptr;  // HOP block state: superbucket written in the narrow layout
-    int hb_narrow = 2;           // narrowest HOP block layout level (FW_HB_NARROW=0/1: development A/B)
-    int64_t* out_key = nullptr;
-    int64_t* out_we = nullptr;
-    uint64_t* out_val[FW_MAX_AGGS] = {};
-    uint32_t* out_null = nullptr;
-    int64_t out_cap = 0;       // result rows between resets (= overflow region rows)
-    int64_t slab_cap = 0;      // output slab rows per superbucket
-    int32_t* sb_out = nullptr;
-    uint32_t* sb_fired = nullptr;
-    int64_t* chunk_stats = nullptr;
-    Tickets* tickets = nullptr;  // last-workgroup election counters of k_ingest / k_merge_fire
-    int64_t* coff = nullptr;   // compaction offsets [n_sb + 2]
-    int64_t* res_key = nullptr;
-    int64_t* res_ws = nullptr;
-    int64_t* res_we = nullptr;
-    uint64_t* res_val[FW_MAX_AGGS] = {};
-    uint32_t* res_null = nullptr;
-
-    // host-staged ingest (FW_STAGE_BUFS pinned column sets)
-    int64_t stage_cap = 0;
-    int stage_cur = 0;
-    int64_t* h_key[FW_STAGE_BUFS] = {};
-    int64_t* h_ts[FW_STAGE_BUFS] = {};
-    int32_t* h_kh[FW_STAGE_BUFS] = {};
-    int64_t* h_val[FW_STAGE_BUFS][FW_MAX_COLS] = {};
-    uint8_t* h_nul[FW_STAGE_BUFS][FW_MAX_COLS] = {};
-    hipEvent_t stage_ev[FW_STAGE_BUFS] = {};   // H2D from host buffer b done (copy stream)
-    // device staging, one set per host set: batch b+1 crosses PCIe on the copy stream while batch b
-    // is ingested on the operator stream
-    hipStream_t cstream = nullptr;
-    hipEvent_t dstage_free[FW_STAGE_BUFS] = {};  // the ingest that read device buffer b has run (operator stream)
-    int64_t* d_key[FW_STAGE_BUFS] = {};
-    int64_t* d_ts[FW_STAGE_BUFS] = {};
-    int32_t* d_kh[FW_STAGE_BUFS] = {};
-    int64_t* d_val[FW_STAGE_BUFS][FW_MAX_COLS] = {};
-    uint8_t* d_nul[FW_STAGE_BUFS][FW_MAX_COLS] = {};
-    // fw_commit_delta32: the 32-bit delta columns of staging set b, FW_PACK_COLS slices of pack_stride
-    uint32_t* d_pack[FW_STAGE_BUFS] = {};
-    int64_t pack_stride = 0;
-    int64_t reserved = -1;
-
-    // asynchronous result delivery (fw_results_async / fw_results_ready): rows compacted on the
-    // device into one of FW_AR_BUFS device buffers (ard_*), then moved into pinned host buffers
-    // (ar_*); only the row count goes through mapped memory.  Up to FW_AR_BUFS collections are
-    // outstanding; fw_results_ready returns the oldest (ar_q, a FIFO of buffer indices)
-    int64_t* ard_key[FW_AR_BUFS] = {};
-    int64_t* ard_ws[FW_AR_BUFS] = {};
-    int64_t* ard_we[FW_AR_BUFS] = {};
-    uint64_t* ard_val[FW_AR_BUFS][FW_MAX_AGGS] = {};
-    uint32_t* ard_null[FW_AR_BUFS] = {};
-    hipStream_t d2h_stream = nullptr;
-    int64_t* ar_key[FW_AR_BUFS] = {};
-    int64_t* ar_ws[FW_AR_BUFS] = {};
-    int64_t* ar_we[FW_AR_BUFS] = {};
-    uint64_t* ar_val[FW_AR_BUFS][FW_MAX_AGGS] = {};
-    uint32_t* ar_null[FW_AR_BUFS] = {};
-    int64_t* ar_n[FW_AR_BUFS] = {};          // row count (written by the compaction kernel)
-    hipEvent_t ar_ev[FW_AR_BUFS] = {};
-    hipEvent_t ar_dma_ev[FW_AR_BUFS] = {};   // the DMA of buffer b's rows (started early by ar_kick)
-    bool ar_copied[FW_AR_BUFS] = {};         // buffer b's rows are (or are queued to be) in host memory
-    bool ar_inflight[FW_AR_BUFS] = {};       // buffer b's DMA is queued (ar_kick), fw_results_ready waits for it
-    // async result delivery: CU stores of the compacted rows into mapped pinned host memory (1, the
-    // default), or DMA on the D2H stream (FW_AR_KERNEL=0).  Measured round 5 (CFG2 end to end):
-    // the DMA queues behind the next batch's H2D on the copy engine, so fw_results_ready waited
-    // 2.2 ms per step (1.18 G ev/s); the kernel stores run beside that H2D: 1.1 ms (1.64 G ev/s)
-    int ar_kernel = 1;
-    int ar_cur = 0;                 // buffer of the next fw_results_async
-    int ar_q[FW_AR_BUFS] = {};      // outstanding collections, oldest first
-    int ar_qhead = 0, ar_qn = 0;
-    bool ar_empty[FW_AR_BUFS] = {}; // that call had nothing to collect
-
-    // FW_KEYHASH_KEYROW: the key-row intern table, per-push intern output, key-row staging
-    bool keyrow = false;
-    KeyRowTable kr{};
-    int64_t kr_scratch_n = 0;
-    int64_t* d_kid = nullptr;       // interned ids of the push being ingested
-    int32_t* d_khash = nullptr;     // their hashCodes
-    int64_t* h_kro[FW_STAGE_BUFS] = {};         // pinned staging: key row offsets / bytes (fw_reserve)
-    uint8_t* h_krb[FW_STAGE_BUFS] = {};
-    int64_t krb_cap = 0;            // staging bytes per batch
-    int64_t* d_kro[FW_STAGE_BUFS] = {};
-    uint8_t* d_krb[FW_STAGE_BUFS] = {};
-    int32_t* res_kr_len = nullptr;  // result key rows (fw_results)
-    uint64_t* res_kr_img = nullptr;
-    std::vector<int32_t> r_kr_len;
-    std::vector<uint64_t> r_kr_img;
-
-    // host copies of results
-    std::vector<int64_t> r_key, r_ws, r_we;
-    std::vector<uint64_t> r_val[FW_MAX_AGGS];
-    std::vector<uint32_t> r_null;
-
-    int64_t pushes_ub = 0;  // upper bound of device pending_pushes
-    // pending-push mirror: host-mapped word written by each merge launch (MergeArgs::host_mirror)
-    volatile unsigned long long* mirror = nullptr;
-    unsigned long long* d_mirror = nullptr;
-    uint64_t merge_seq = 0;         // merge launches so far
-    uint64_t pushes_total = 0;      // ingest launches so far
-    uint64_t pushes_at_merge[64] = {};  // pushes_total when merge launch (seq % 64) was issued
-    bool reset_pending = false;  // fw_results_reset called: the next merge launch empties the results
-    int64_t host_cur = INT64_MIN;
-    // the device's currentProgress / nextTriggerProgress as the launched merges leave them (mirrored
-    // on the host from the watermarks it launched; merge_finalize applies the same rule), so fw_advance
-    // can tell a watermark that crosses no slice end -- the merge launch would change nothing -- and
-    // skip it (FW_SKIP_IDLE=0: launch every advance)
-    int64_t dev_cur = INT64_MIN;
-    int64_t dev_ntp = INT64_MIN;
-    bool skip_idle = true;
-    KTimer* timer = nullptr;  // non-null while fw_set_profiling is on
-    int ablate = 0;           // FW_ABLATE (development timing builds only; results are wrong)
-    int fold_always = 0;      // FW_FOLD=1 (development A/B): no adaptive fold skip
-    // k_ingest_pack (fw_ingest_pack.h): FW_IG_PACK 0 never, 1 (default) by fw_host_ig_pack_choice (the
-    // last completed push left the LDS fold skipped and valid PF_PACK fields, a flush epoch has been
-    // opened, no fold measurement is due), 2 on every push of an eligible handle (tests)
-    int ig_pack_mode = 1;
-    // k_ingest_pack's geometry (fw_internal.h).  FW_IGP_GEOM=0/1 fixes it (A/B, tests); otherwise (-1) each
-    // launch takes the 256 x 16 geometry when that makes the whole push resident and 512 x 8 does not
-    // (more chunks than igp_res[0], at most igp_res[1]: workgroups per CU x CUs), else 512 x 8, which
-    // is faster at every other size
-    int igp_geom = -1;
-    int igp_last = 0;             // geometry of the last k_ingest_pack launch
-    int64_t igp_res[2] = {0, 0};  // chunks resident at once per geometry
-    uint64_t ig_since_fold = 0;      // pushes since the last one on which k_ingest folded (that one included)
-    uint64_t ig_merges = 0;          // merge launches since the control block was initialised
-    bool mg_tag = false;      // planned: the merge launches its GF_TAG variant (tag path for PF_PACK flushes)
-    bool ig_pack_ok = false;  // planned: the handle's pushes are ones k_ingest_pack serves
-    // ingest mirror: host-mapped word written after each ingest launch (Tickets::ig_mirror)
-    volatile unsigned long long* ig_mirror = nullptr;
-    unsigned long long* d_ig_mirror = nullptr;
-    uint64_t ig_pushes = 0;          // ingest launches since the control block was initialised (Ctrl::push_count)
-    int64_t ig_pack_launches = 0;    // of all launches, the ones k_ingest_pack took
-    int fill_pct = 75;        // superbucket LDS fill target (FW_FILL_PCT: development A/B)
-    unsigned long long* stamps = nullptr;  // [N_STAMPS] merge phase cycles (FW_ABLATE & AB_STAMPS)
-    unsigned long long* kt_dev = nullptr;  // [FW_KT_N][KT_WORDS] in-kernel launch timing
-    int kt_device = 0;                     // fw_set_profiling(FW_PROF_DEVICE) is on
-};
 
 // The aggregate planner: fw_config.aggs -> accumulator words (WordDesc: op, value slot and NULL gate
 // per word, shared words deduplicated) and the aggregates over them (AggDesc: w0, w1, nn, ...).
@@ -1034,22 +826,6 @@ T* mapped(T* host) {
     return hipHostGetDevicePointer(&d, (void*)host, 0) == hipSuccess ? (T*)d : nullptr;
 }
 
-int read_ctrl(fw_handle* h, Ctrl* out) {
-    HIP_TRY(hipMemcpyAsync(out, h->ctrl, sizeof(Ctrl), hipMemcpyDeviceToHost, h->stream));
-    HIP_TRY(hipStreamSynchronize(h->stream));
-    if (out->error) {
-        return fail(FW_E_CAPACITY, "device error (bits 0x%x:%s%s%s%s%s%s%s%s%s)", out->error,
-                    out->error & ERR_CHUNKS ? " partial-buffer" : "", out->error & ERR_STATE ? " state-table" : "",
-                    out->error & ERR_OUTPUT ? " result-buffer" : "", out->error & ERR_TREQ ? " timer-requests" : "",
-                    out->error & ERR_KEYGROUP ? " key-group-not-owned" : "",
-                    out->error & ERR_LATE ? " late-rows (call fw_late_records more often)" : "",
-                    out->error & ERR_ORDEV ? " first-element-events (call fw_first_element_events after each advance)" : "",
-                    out->error & ERR_KEYROW ? " key-rows (table full, or a row over key_row_max_bytes)" : "",
-                    out->error & ERR_GAP ? " session-gap (a row's gap outside (0, size_ms])" : "");
-    }
-    return FW_OK;
-}
-
 // the window description the kernels get: the shift-zone table pointers are the device copy's
 WinDesc device_win(const fw_handle* h) {
     WinDesc w = h->win;
@@ -1133,13 +909,6 @@ int launch_merge(fw_handle* h, int64_t wm, int force) {
         h->dev_cur = wm;
         if (wm >= h->dev_ntp) h->dev_ntp = tz_next_trigger_watermark(h->win.tz, wm, h->win.slice_div);
     }
-    return FW_OK;
-}
-
-int force_flush(fw_handle* h) {
-    int rc = launch_merge(h, INT64_MIN, 1);
-    if (rc) return rc;
-    h->pushes_ub = 0;
     return FW_OK;
 }
 
@@ -1262,8 +1031,40 @@ int push(fw_handle* h, int64_t n, const int64_t* key, const int64_t* ts, const i
     return FW_OK;
 }
 
-// interns n key-row images (device) into the table: d_kid / d_khash hold their ids and hashCodes
-int kr_intern(fw_handle* h, int64_t n, const int64_t* d_off, const uint8_t* d_bytes) {
+int push_key_rows(fw_handle* h, int64_t n, const int64_t* d_off, const uint8_t* d_bytes, const int64_t* ts,
+                  const void* const* vals, const uint8_t* const* nulls) {
+    int rc = kr_intern(h, n, d_off, d_bytes);
+    if (rc) return rc;
+    return push(h, n, h->d_kid, ts, h->d_khash, vals, nulls);
+}
+
+}  // namespace
+
+// ---- the helpers the checkpoint code shares with this file (fw_handle.h)
+int fw::read_ctrl(fw_handle* h, Ctrl* out) {
+    HIP_TRY(hipMemcpyAsync(out, h->ctrl, sizeof(Ctrl), hipMemcpyDeviceToHost, h->stream));
+    HIP_TRY(hipStreamSynchronize(h->stream));
+    if (out->error) {
+        return fail(FW_E_CAPACITY, "device error (bits 0x%x:%s%s%s%s%s%s%s%s%s)", out->error,
+                    out->error & ERR_CHUNKS ? " partial-buffer" : "", out->error & ERR_STATE ? " state-table" : "",
+                    out->error & ERR_OUTPUT ? " result-buffer" : "", out->error & ERR_TREQ ? " timer-requests" : "",
+                    out->error & ERR_KEYGROUP ? " key-group-not-owned" : "",
+                    out->error & ERR_LATE ? " late-rows (call fw_late_records more often)" : "",
+                    out->error & ERR_ORDEV ? " first-element-events (call fw_first_element_events after each advance)" : "",
+                    out->error & ERR_KEYROW ? " key-rows (table full, or a row over key_row_max_bytes)" : "",
+                    out->error & ERR_GAP ? " session-gap (a row's gap outside (0, size_ms])" : "");
+    }
+    return FW_OK;
+}
+
+int fw::force_flush(fw_handle* h) {
+    int rc = launch_merge(h, INT64_MIN, 1);
+    if (rc) return rc;
+    h->pushes_ub = 0;
+    return FW_OK;
+}
+
+int fw::kr_intern(fw_handle* h, int64_t n, const int64_t* d_off, const uint8_t* d_bytes) {
     if (n > h->kr_scratch_n) {
         hipFree(h->d_kid);
         hipFree(h->d_khash);
@@ -1279,92 +1080,8 @@ int kr_intern(fw_handle* h, int64_t n, const int64_t* d_off, const uint8_t* d_by
     return FW_OK;
 }
 
-int push_key_rows(fw_handle* h, int64_t n, const int64_t* d_off, const uint8_t* d_bytes, const int64_t* ts,
-                  const void* const* vals, const uint8_t* const* nulls) {
-    int rc = kr_intern(h, n, d_off, d_bytes);
-    if (rc) return rc;
-    return push(h, n, h->d_kid, ts, h->d_khash, vals, nulls);
-}
-
-// the first n entries of superbucket sb, in the wide layout (key, slice, flags, words) whatever the
-// layout the last write-back chose (HOP block state may be narrow, hb_narrow_words)
-int state_rows_to_host(const fw_handle* h, size_t sb, int64_t n, uint64_t* out) {
-    const int pwe = h->pwe;
-    const uint64_t* src = h->state + sb * h->cap_e * pwe;
-    uint8_t nar = 0;
-    if (h->win.hopb) HIP_TRY(hipMemcpy(&nar, h->sb_nar + sb, 1, hipMemcpyDeviceToHost));
-    if (!nar) {
-        HIP_TRY(hipMemcpy(out, src, (size_t)n * pwe * 8, hipMemcpyDeviceToHost));
-        return FW_OK;
-    }
-    const int nw = h->nw_t, pwn = hb_narrow_words(nw, nar), sbytes = hb_slot_bytes(nar);
-    std::vector<uint64_t> tmp((size_t)n * pwn);
-    HIP_TRY(hipMemcpy(tmp.data(), src, tmp.size() * 8, hipMemcpyDeviceToHost));
-    for (int64_t i = 0; i < n; i++) {
-        const uint8_t* q = (const uint8_t*)(tmp.data() + (size_t)i * pwn);
-        uint64_t* e = out + (size_t)i * pwe;
-        uint32_t bi;
-        uint16_t fl;
-        memcpy(&e[0], q, 8);
-        memcpy(&bi, q + 8, 4);  // block index: block start = index * hb_span + offset
-        memcpy(&fl, q + 12, 2);
-        e[1] = (uint64_t)wadd((int64_t)bi * h->win.hb_span, h->win.offset);
-        e[2] = fl;
-        const uint32_t mask = (uint32_t)fl >> HB_MASK_SHIFT;
-        for (int s = 0; s < HB_R; s++)
-            for (int x = 0; x < nw; x++) {
-                const uint8_t* f = q + HB_HDR_BYTES + sbytes * (s * nw + x);
-                int64_t v;
-                if (sbytes == 4) {
-                    int32_t t;
-                    memcpy(&t, f, 4);
-                    v = t;
-                } else {
-                    int16_t t;
-                    memcpy(&t, f, 2);
-                    v = t;
-                }
-                e[3 + s * nw + x] = ((mask >> s) & 1u) ? (uint64_t)v : x < h->wd.nw ? word_identity(h->wd.op[x]) : 0;
-            }
-    }
-    return FW_OK;
-}
-
-// earliest watermark-visible time of an entry's timers, as a window end (is_fired(x, W) <=> due):
-// the maxTimestamp timer at its window end, a DataStream cleanup timer at cleanupTime + 1
-int64_t entry_timer_end(const fw_handle* h, int64_t slice, uint64_t flags) {
-    if (h->win.hopb) {  // block entry: no window of it is due before its oldest slice with data
-        const uint32_t mask = (uint32_t)flags >> 8;
-        for (int i = 0; i < HB_R; i++)
-            if ((mask >> i) & 1u) return wadd(slice, (int64_t)(i + 1) * h->win.interval);
-        return INT64_MAX;
-    }
-    int64_t m = (flags & F_TIMER) ? slice : INT64_MAX;
-    if (h->win.ds && (flags & F_CLEAN)) m = std::min(m, wadd(ds_cleanup_time(h->win, slice), 1));
-    return m;
-}
-
-}  // namespace
-
 // ======================================================================================
 extern "C" {
-
-// entry points a count handle (FW_WIN_COUNT) or a session handle (FW_WIN_SESSION) does not have
-#define CW_REFUSE(h, name)                                                       \
-    if ((h)->cw.on) return fail(FW_E_INVALID, name ": not for count windows");   \
-    if ((h)->sw.on) return fail(FW_E_INVALID, name ": not for session windows")
-// The push entry points behind the N > 1 keyBy exchange (fw_push_device_segments,
-// fw_push_device_packed_segments; fw_advance_device likewise): a session handle has them iff its
-// configuration has parallelism > 1 -- only such a handle has an exchange in front of it.  One of
-// parallelism 1 refuses them as ever, and so does every count handle.
-// A record count handle (FW_WIN_COUNT_RECORD) has no key-group checkpoint and no exchange path yet: a
-// restored key group's records would have to be re-numbered under fresh ordinals.
-#define CW_REFUSE_RECORD(h, name)                                                                                       \
-    if ((h)->cw.on && (h)->cw.rec)                                                                                      \
-        return fail(FW_E_INVALID, name ": not for record count windows (FW_WIN_COUNT_RECORD: retained records are not re-numbered)")
-#define CW_REFUSE_EXCHANGE(h, name)                                              \
-    if ((h)->cw.on) return fail(FW_E_INVALID, name ": not for count windows");   \
-    if ((h)->sw.on && (h)->cfg.parallelism <= 1) return fail(FW_E_INVALID, name ": not for session windows")
 
 const char* fw_last_error(void) { return g_err.c_str(); }
 int fw_abi_version(void) { return FW_ABI_VERSION; }
@@ -2487,1100 +2204,6 @@ int fw_get_kernel_times(fw_handle* h, fw_kernel_times* out) {
         out->launches[k] = t->n[k];
     }
     return FW_OK;
-}
-
-// Fingerprint of everything that gives the stored words their meaning: API, phase, window kind,
-// size, slice interval, offset, key hashing, maxParallelism and the accumulator word layout (op,
-// value column, NULL gate per word).  A blob is only restored into an operator with the same one.
-static uint64_t semantics_fingerprint(const fw_handle* h) {
-    uint64_t x = 0xcbf29ce484222325ull;
-    auto mix = [&](int64_t v) {
-        for (int b = 0; b < 8; b++) {
-            x ^= (uint64_t)((v >> (8 * b)) & 0xff);
-            x *= 0x100000001b3ull;
-        }
-    };
-    const fw_config& c = h->cfg;
-    mix(c.api);
-    mix(c.agg_phase);
-    mix(h->win.kind);
-    mix(h->win.size);
-    mix(h->win.interval);
-    mix(h->win.offset);
-    mix(h->cfg.key_hash);
-    mix(h->ks.max_p);
-    mix(c.allowed_lateness_ms);
-    mix(c.tz_use_dst);
-    for (size_t i = 0; i < h->tz_utc.size(); i++) {
-        mix(h->tz_utc[i]);
-        mix(h->tz_off[i]);
-    }
-    mix(h->wd.nw);
-    for (int w = 0; w < h->wd.nw; w++) {
-        mix(h->wd.op[w]);
-        mix(h->slot_col[h->wd.col[w]]);
-        mix(h->wd.gate[w]);
-    }
-    return x;
-}
-
-// ---- snapshot: [header][state_count[n_sb]][entries of sb 0][entries of sb 1]...
-struct SnapHeader {
-    uint64_t magic;
-    int32_t version, n_sb, cap_e, pwe;
-    int64_t cur, late_dropped, fired, live;
-    uint64_t semantics;
-    int64_t push_seq;  // arrival ordinals continue after the restore (W_FIRST words stay ordered)
-};
-static const uint64_t SNAP_MAGIC = 0x464c4b57494e3033ull;  // "FLKWIN03"
-
-// ---- key rows in a blob (FW_KEYHASH_KEYROW): the entries carry table ids, which mean nothing to
-// another handle, so a blob also holds the key row of every id its entries use:
-//   [n_keys] then per key [id, hash << 32 | length, image words...]  (uint64 words)
-// and a restore interns the images into its own table and rewrites the entries' keys.
-static int kr_section(fw_handle* h, const uint64_t* entries, int64_t n, int pwe, std::vector<uint64_t>* out) {
-    out->clear();
-    if (!h->keyrow) return FW_OK;
-    Ctrl c;
-    int rc = read_ctrl(h, &c);
-    if (rc) return rc;
-    std::vector<int64_t> ids;
-    ids.reserve((size_t)n);
-    for (int64_t i = 0; i < n; i++) ids.push_back((int64_t)entries[(size_t)i * pwe]);
-    std::sort(ids.begin(), ids.end());
-    ids.erase(std::unique(ids.begin(), ids.end()), ids.end());
-    const int64_t sw = h->kr.stride_words;
-    std::vector<uint64_t> rows;
-    if (!ids.empty()) {
-        if (ids.front() < 0 || ids.back() >= c.kr_next_id) return fail(FW_E_STATE, "state entry with an unknown key row id");
-        rows.resize((size_t)(ids.back() + 1) * sw);
-        HIP_TRY(hipMemcpy(rows.data(), h->kr.arena, rows.size() * 8, hipMemcpyDeviceToHost));
-    }
-    out->push_back((uint64_t)ids.size());
-    for (int64_t id : ids) {
-        const uint64_t* r = rows.data() + (size_t)id * sw;
-        out->push_back((uint64_t)id);
-        out->insert(out->end(), r, r + 1 + ((uint32_t)r[0] >> 3));
-    }
-    return FW_OK;
-}
-
-// a blob's key-row section on the host: the ids it names, their images and offsets; *used = words read
-static int kr_parse_section(const uint64_t* sec, int64_t avail_words, std::vector<int64_t>* old, std::vector<int64_t>* off,
-                            std::vector<uint64_t>* bytes, int64_t* used) {
-    old->clear();
-    off->assign(1, 0);
-    bytes->clear();
-    if (avail_words < 1) return fail(FW_E_INVALID, "key-row section truncated");
-    const int64_t nk = (int64_t)sec[0];
-    int64_t p = 1;
-    for (int64_t k = 0; k < nk; k++) {
-        if (p + 2 > avail_words) return fail(FW_E_INVALID, "key-row section truncated");
-        const int64_t id = (int64_t)sec[p];
-        const int64_t len = (int64_t)(uint32_t)sec[p + 1];
-        if ((len & 7) || p + 2 + len / 8 > avail_words) return fail(FW_E_INVALID, "key-row section truncated");
-        old->push_back(id);
-        bytes->insert(bytes->end(), sec + p + 2, sec + p + 2 + len / 8);
-        off->push_back(off->back() + len);
-        p += 2 + len / 8;
-    }
-    *used = p;
-    return FW_OK;
-}
-
-// interns a blob's key-row section: old id -> this handle's id (and its hash); *used = words read
-static int kr_restore_section(fw_handle* h, const uint64_t* sec, int64_t avail_words, std::vector<std::pair<int64_t, int64_t>>* map,
-                              std::vector<int32_t>* hashes, int64_t* used) {
-    map->clear();
-    hashes->clear();
-    std::vector<int64_t> off, old;
-    std::vector<uint64_t> bytes;
-    if (const int prc = kr_parse_section(sec, avail_words, &old, &off, &bytes, used)) return prc;
-    const int64_t nk = (int64_t)old.size();
-    if (nk == 0) return FW_OK;
-    int64_t* d_off = nullptr;
-    uint8_t* d_bytes = nullptr;
-    int rc;
-    if ((rc = fd_dalloc(&d_off, off.size()))) return rc;
-    if ((rc = fd_dalloc(&d_bytes, std::max<size_t>(bytes.size() * 8, 8)))) { hipFree(d_off); return rc; }
-    HIP_TRY(hipMemcpy(d_off, off.data(), off.size() * 8, hipMemcpyHostToDevice));
-    HIP_TRY(hipMemcpy(d_bytes, bytes.data(), bytes.size() * 8, hipMemcpyHostToDevice));
-    rc = kr_intern(h, nk, d_off, d_bytes);
-    std::vector<int64_t> ids((size_t)nk);
-    hashes->resize((size_t)nk);
-    if (!rc) {
-        HIP_TRY(hipMemcpyAsync(ids.data(), h->d_kid, nk * 8, hipMemcpyDeviceToHost, h->stream));
-        HIP_TRY(hipMemcpyAsync(hashes->data(), h->d_khash, nk * 4, hipMemcpyDeviceToHost, h->stream));
-        Ctrl c;
-        rc = read_ctrl(h, &c);  // syncs; a full table is a device error
-    }
-    hipFree(d_off);
-    hipFree(d_bytes);
-    if (rc) return rc;
-    for (int64_t k = 0; k < nk; k++) map->emplace_back(old[(size_t)k], ids[(size_t)k]);
-    std::sort(map->begin(), map->end());
-    return FW_OK;
-}
-
-static int64_t kr_lookup(const std::vector<std::pair<int64_t, int64_t>>& map, int64_t old, size_t* pos) {
-    auto it = std::lower_bound(map.begin(), map.end(), std::make_pair(old, INT64_MIN));
-    if (it == map.end() || it->first != old) return -1;
-    *pos = (size_t)(it - map.begin());
-    return it->second;
-}
-
-int fw_snapshot(fw_handle* h, void* buf, int64_t capacity, int64_t* size) {
-    if (!h || !size) return fail(FW_E_INVALID, "null argument");
-    if (h->cw.on) {
-        h->cw.watermark = h->host_cur;
-        return cw_snapshot(&h->cw, -1, buf, capacity, size);
-    }
-    if (h->sw.on) {
-        int rc_wm;
-        if (h->sw.wm_dev && (rc_wm = sw_read_watermark(&h->sw, &h->host_cur))) return rc_wm;
-        return sw_snapshot(&h->sw, h->host_cur, -1, buf, capacity, size);
-    }
-    int rc = force_flush(h);  // prepareSnapshotPreBarrier -> windowBuffer.flush()
-    if (rc) return rc;
-    Ctrl c;
-    if ((rc = read_ctrl(h, &c))) return rc;
-    const int nsb = h->ks.n_sb, pwe = h->pwe;
-    std::vector<int32_t> cnt(nsb);
-    HIP_TRY(hipMemcpy(cnt.data(), h->state_count, sizeof(int32_t) * nsb, hipMemcpyDeviceToHost));
-    int64_t total = 0;
-    for (int s = 0; s < nsb; s++) total += cnt[s];
-    std::vector<uint64_t> ent((size_t)total * pwe);
-    {
-        uint64_t* e = ent.data();
-        for (int s = 0; s < nsb; s++) {
-            if (!cnt[s]) continue;
-            if ((rc = state_rows_to_host(h, (size_t)s, cnt[s], e))) return rc;
-            e += (size_t)cnt[s] * pwe;
-        }
-    }
-    std::vector<uint64_t> krs;
-    if ((rc = kr_section(h, ent.data(), total, pwe, &krs))) return rc;
-    const int64_t need = (int64_t)sizeof(SnapHeader) + 4ll * nsb + total * pwe * 8 + (int64_t)krs.size() * 8;
-    *size = need;
-    if (!buf) return FW_OK;
-    if (capacity < need) return fail(FW_E_INVALID, "snapshot buffer too small (%lld < %lld)", (long long)capacity, (long long)need);
-    SnapHeader hd{SNAP_MAGIC, 3, nsb, h->cap_e, pwe, std::max(c.cur, h->host_cur), (int64_t)c.late_dropped, 0, total, semantics_fingerprint(h),
-                  (int64_t)h->push_seq};
-    char* p = (char*)buf;
-    memcpy(p, &hd, sizeof hd);
-    p += sizeof hd;
-    memcpy(p, cnt.data(), 4ll * nsb);
-    p += 4ll * nsb;
-    memcpy(p, ent.data(), ent.size() * 8);
-    p += ent.size() * 8;
-    if (!krs.empty()) memcpy(p, krs.data(), krs.size() * 8);
-    return FW_OK;
-}
-
-int fw_restore(fw_handle* h, const void* buf, int64_t size) {
-    if (!h || !buf) return fail(FW_E_INVALID, "null argument");
-    if (h->cw.on) {
-        const int rc = cw_restore(&h->cw, false, buf, size);
-        if (!rc) h->host_cur = h->cw.watermark;
-        return rc;
-    }
-    if (h->sw.on) return sw_restore(&h->sw, false, buf, size, &h->host_cur);
-    SnapHeader hd;
-    if (size < (int64_t)sizeof hd) return fail(FW_E_INVALID, "snapshot truncated");
-    memcpy(&hd, buf, sizeof hd);
-    const int nsb = h->ks.n_sb, pwe = h->pwe;
-    if (hd.magic != SNAP_MAGIC || hd.n_sb != nsb || hd.pwe != pwe || hd.cap_e != h->cap_e ||
-        hd.semantics != semantics_fingerprint(h))
-        return fail(FW_E_INVALID, "snapshot layout does not match this operator configuration");
-    const int64_t ent_end = (int64_t)sizeof hd + 4ll * nsb + hd.live * pwe * 8;
-    if (size < ent_end) return fail(FW_E_INVALID, "snapshot truncated");
-    const char* p = (const char*)buf + sizeof hd;
-    std::vector<int32_t> cnt(nsb);
-    memcpy(cnt.data(), p, 4ll * nsb);
-    p += 4ll * nsb;
-    std::vector<uint64_t> ent((size_t)hd.live * pwe);
-    memcpy(ent.data(), p, ent.size() * 8);
-    int rc;
-    if (h->keyrow) {  // this handle's ids for the blob's key rows
-        std::vector<uint64_t> sec((size_t)((size - ent_end) / 8));
-        memcpy(sec.data(), (const char*)buf + ent_end, sec.size() * 8);
-        {  // the blob is checked before the handle changes: a blob that fails here leaves it as it was
-            std::vector<int64_t> old, off;
-            std::vector<uint64_t> bytes;
-            int64_t used = 0;
-            if ((rc = kr_parse_section(sec.data(), (int64_t)sec.size(), &old, &off, &bytes, &used))) return rc;
-            if ((int64_t)old.size() > h->kr.cap_ids)
-                return fail(FW_E_CAPACITY, "snapshot holds %lld key rows, the table %lld", (long long)old.size(), (long long)h->kr.cap_ids);
-            for (size_t k = 0; k + 1 < off.size(); k++)
-                if (off[k + 1] - off[k] < 8 || off[k + 1] - off[k] > h->kr.max_len)
-                    return fail(FW_E_INVALID, "snapshot key row of %lld bytes (key_row_max_bytes %d)", (long long)(off[k + 1] - off[k]), (int)h->kr.max_len);
-            std::sort(old.begin(), old.end());
-            for (int64_t i = 0; i < hd.live; i++)
-                if (!std::binary_search(old.begin(), old.end(), (int64_t)ent[(size_t)i * pwe]))
-                    return fail(FW_E_INVALID, "snapshot entry without its key row");
-        }
-        // Everything that holds an id of before the restore goes with it (state, pending pushes, timer
-        // requests, uncollected rows): the table starts empty.  A handle whose table was full restores
-        // like a fresh one, and a device error of before the restore does not fail the interning.
-        HIP_TRY(hipStreamSynchronize(h->stream));
-        Ctrl k;
-        HIP_TRY(hipMemcpy(&k, h->ctrl, sizeof k, hipMemcpyDeviceToHost));
-        k.kr_next_id = k.kr_free_count = k.kr_free_cursor = 0;
-        k.error = 0;
-        HIP_TRY(hipMemcpy(h->ctrl, &k, sizeof k, hipMemcpyHostToDevice));
-        HIP_TRY(hipMemsetAsync(h->kr.slots, 0, sizeof(uint32_t) * h->kr.n_slots, h->stream));
-        std::vector<std::pair<int64_t, int64_t>> map;
-        std::vector<int32_t> hashes;
-        int64_t used = 0;
-        if ((rc = kr_restore_section(h, sec.data(), (int64_t)sec.size(), &map, &hashes, &used))) return rc;
-        for (int64_t i = 0; i < hd.live; i++) {
-            size_t pos;
-            const int64_t id = kr_lookup(map, (int64_t)ent[(size_t)i * pwe], &pos);
-            if (id < 0) return fail(FW_E_INVALID, "snapshot entry without its key row");
-            ent[(size_t)i * pwe] = (uint64_t)id;
-        }
-    }
-    HIP_TRY(hipStreamSynchronize(h->stream));
-    std::vector<int64_t> mins(nsb, INT64_MAX);
-    const uint64_t* e = ent.data();
-    for (int s = 0; s < nsb; s++) {
-        if (!cnt[s]) continue;
-        for (int i = 0; i < cnt[s]; i++)
-            mins[s] = std::min(mins[s], entry_timer_end(h, (int64_t)e[(size_t)i * pwe + 1], e[(size_t)i * pwe + 2]));
-        HIP_TRY(hipMemcpy(h->state + (size_t)s * h->cap_e * pwe, e, (size_t)cnt[s] * pwe * 8, hipMemcpyHostToDevice));
-        e += (size_t)cnt[s] * pwe;
-    }
-    HIP_TRY(hipMemcpy(h->state_count, cnt.data(), 4ll * nsb, hipMemcpyHostToDevice));
-    HIP_TRY(hipMemset(h->sb_nar, 0, (size_t)nsb));  // restored entries are in the wide layout
-    HIP_TRY(hipMemcpy(h->sb_min_timer, mins.data(), 8ll * nsb, hipMemcpyHostToDevice));
-    Ctrl c;
-    HIP_TRY(hipMemcpy(&c, h->ctrl, sizeof c, hipMemcpyDeviceToHost));  // the key-row allocator survives
-    const Ctrl keep = c;
-    HIP_TRY(launch_init_ctrl(h->ctrl, h->stream));
-    h->ig_pushes = 0;  // Ctrl::push_count starts over: so does the host's copy, and the ingest mirror
-    h->ig_since_fold = 0;
-    h->ig_merges = 0;  // (no PF_PACK fields until a push has measured them and a flush has opened an epoch)
-    if (h->ig_mirror) *h->ig_mirror = ~0ull;
-    // the restore drops the pending pushes: with runs, their fill counters, overflow flags and formats
-    // go too (as allocate() starts them), or the next push would add onto the dropped push's fills and
-    // the next flush would fold its stale rows
-    if (h->run_rows) {
-        const size_t n_isb = (size_t)(h->ks.n_sb >> h->ks.pass_log2);
-        HIP_TRY(hipMemsetAsync(h->run_fill, 0, sizeof(uint32_t) * FW_MAX_PENDING * RUN_X * n_isb, h->stream));
-        HIP_TRY(hipMemsetAsync(h->run_ovf, 0, sizeof(uint32_t) * FW_MAX_PENDING * n_isb, h->stream));
-        HIP_TRY(hipMemsetAsync(h->slot_fmt, 0, sizeof(int32_t) * FW_MAX_PENDING, h->stream));
-    }
-    HIP_TRY(hipStreamSynchronize(h->stream));
-    HIP_TRY(hipMemcpy(&c, h->ctrl, sizeof c, hipMemcpyDeviceToHost));
-    // SQL: union-list watermark state (WindowAggOperator.initializeState :183-206).  DataStream:
-    // the WindowOperator keeps no watermark state, its timer service restarts at Long.MIN_VALUE
-    // (InternalTimerServiceImpl.java:72) until the next watermark arrives.
-    c.cur = h->cfg.api == FW_API_SQL ? hd.cur : INT64_MIN;
-    c.ntp = INT64_MIN;
-    c.late_dropped = (uint64_t)hd.late_dropped;
-    c.fired = (uint64_t)hd.fired;
-    c.live_entries = hd.live;
-    c.kr_next_id = keep.kr_next_id;
-    c.kr_free_count = keep.kr_free_count;
-    c.kr_free_cursor = keep.kr_free_cursor;
-    c.kr_epoch = keep.kr_epoch;
-    c.kr_collections = keep.kr_collections;
-    HIP_TRY(hipMemcpy(h->ctrl, &c, sizeof c, hipMemcpyHostToDevice));
-    h->pushes_ub = 0;
-    h->host_cur = c.cur;
-    h->dev_cur = c.cur;
-    h->dev_ntp = INT64_MIN;
-    h->push_seq = std::max<int64_t>(h->push_seq, hd.push_seq);
-    // rows emitted before the restore and not collected go with the rest (a restored operator starts
-    // with none): out_count went with the control block, the next merge launch starts the slabs afresh
-    h->reset_pending = true;
-    return FW_OK;
-}
-
-// ---- key-group-partitioned checkpoint (rescaling) --------------------------------------
-// The heap backend writes keyed state per key group (HeapSnapshotStrategy.java:97 ->
-// AbstractStateTableSnapshot.writeStateInKeyGroup :112) and a rescaled job hands every new
-// subtask the key groups of its computeKeyGroupRangeForOperatorIndex range.  The blob of one key
-// group is therefore independent of this build's superbucket split: entries carry the sub-bucket
-// they came from, and a restoring handle re-routes every key with the same route_key the
-// ingest kernel runs (only a precomputed-hash key cannot be re-hashed; it keeps its sub-bucket
-// bits, which works for any target split not finer than the source's).
-struct KgHeader {
-    uint64_t magic;
-    int32_t version, key_group, pwe, nw, sb_log2, hash_kind;
-    int64_t win_size, win_interval, cur, n;
-    uint64_t semantics;
-    int64_t push_seq;  // arrival ordinals of the restoring handle continue after every restored blob's
-};
-static const uint64_t KG_MAGIC = 0x464c4b574b473033ull;  // "FLKWKG03"
-
-int fw_snapshot_key_group(fw_handle* h, int32_t key_group, void* buf, int64_t capacity, int64_t* size) {
-    if (!h || !size) return fail(FW_E_INVALID, "null argument");
-    CW_REFUSE_RECORD(h, "fw_snapshot_key_group");
-    if (h->cw.on) {
-        if (key_group < 0) return fail(FW_E_INVALID, "key group %d is not owned by this subtask", key_group);
-        h->cw.watermark = h->host_cur;
-        return cw_snapshot(&h->cw, key_group, buf, capacity, size);
-    }
-    if (h->sw.on) {
-        if (key_group < 0) return fail(FW_E_INVALID, "key group %d is not owned by this subtask", key_group);
-        int rc_wm;
-        if (h->sw.wm_dev && (rc_wm = sw_read_watermark(&h->sw, &h->host_cur))) return rc_wm;
-        return sw_snapshot(&h->sw, h->host_cur, key_group, buf, capacity, size);
-    }
-    const KeySpace& ks = h->ks;
-    const int li = key_group - ks.kg_start;
-    if (li < 0 || li >= ks.n_kg) return fail(FW_E_INVALID, "key group %d is not owned by this subtask", key_group);
-    int rc = force_flush(h);  // prepareSnapshotPreBarrier -> windowBuffer.flush()
-    if (rc) return rc;
-    Ctrl c;
-    if ((rc = read_ctrl(h, &c))) return rc;
-    const int L = ks.sb_per_kg_log2, nsub = 1 << L, pwe = h->pwe;
-    std::vector<int32_t> cnt(nsub);
-    HIP_TRY(hipMemcpy(cnt.data(), h->state_count + ((size_t)li << L), sizeof(int32_t) * nsub, hipMemcpyDeviceToHost));
-    int64_t total = 0;
-    for (int q = 0; q < nsub; q++) total += cnt[q];
-    std::vector<uint64_t> ent((size_t)total * pwe);
-    uint64_t* e = ent.data();
-    for (int q = 0; q < nsub; q++) {
-        if (!cnt[q]) continue;
-        const size_t sb = ((size_t)li << L) + q;
-        if ((rc = state_rows_to_host(h, sb, cnt[q], e))) return rc;
-        for (int i = 0; i < cnt[q]; i++) e[(size_t)i * pwe + 2] = (uint32_t)e[(size_t)i * pwe + 2] | ((uint64_t)q << 32);
-        e += (size_t)cnt[q] * pwe;
-    }
-    std::vector<uint64_t> krs;
-    if ((rc = kr_section(h, ent.data(), total, pwe, &krs))) return rc;
-    const int64_t need = (int64_t)sizeof(KgHeader) + total * pwe * 8 + (int64_t)krs.size() * 8;
-    *size = need;
-    if (!buf) return FW_OK;
-    if (capacity < need) return fail(FW_E_INVALID, "snapshot buffer too small (%lld < %lld)", (long long)capacity, (long long)need);
-    KgHeader hd{KG_MAGIC, 3, key_group, pwe, h->wd.nw, L, h->cfg.key_hash, h->win.size, h->win.interval,
-                std::max(c.cur, h->host_cur), total,
-                semantics_fingerprint(h), (int64_t)h->push_seq};
-    memcpy(buf, &hd, sizeof hd);
-    memcpy((char*)buf + sizeof hd, ent.data(), ent.size() * 8);
-    if (!krs.empty()) memcpy((char*)buf + sizeof hd + ent.size() * 8, krs.data(), krs.size() * 8);
-    return FW_OK;
-}
-
-int fw_restore_key_group(fw_handle* h, const void* buf, int64_t size) {
-    if (!h || !buf) return fail(FW_E_INVALID, "null argument");
-    CW_REFUSE_RECORD(h, "fw_restore_key_group");
-    if (h->cw.on) return cw_restore(&h->cw, true, buf, size);
-    if (h->sw.on) {
-        // (lateness: the blob's watermark must be the handle's, which is Ctrl::cur once advanced from the device)
-        int rc_wm = 0;
-        if (h->sw.late && h->sw.wm_dev && (rc_wm = sw_read_watermark(&h->sw, &h->host_cur))) return rc_wm;
-        return sw_restore(&h->sw, true, buf, size, &h->host_cur);
-    }
-    KgHeader hd;
-    if (size < (int64_t)sizeof hd) return fail(FW_E_INVALID, "key-group snapshot truncated");
-    memcpy(&hd, buf, sizeof hd);
-    const KeySpace& ks = h->ks;
-    const int pwe = h->pwe, L = ks.sb_per_kg_log2;
-    if (hd.magic != KG_MAGIC || hd.version != 3) return fail(FW_E_INVALID, "not a key-group snapshot");
-    if (hd.pwe != pwe || hd.nw != h->wd.nw || hd.hash_kind != h->cfg.key_hash || hd.win_size != h->win.size ||
-        hd.win_interval != h->win.interval || hd.semantics != semantics_fingerprint(h))
-        return fail(FW_E_INVALID, "key-group snapshot of a different operator configuration");
-    const int64_t ent_end = (int64_t)sizeof hd + hd.n * pwe * 8;
-    if (size < ent_end) return fail(FW_E_INVALID, "key-group snapshot truncated");
-    const int li = hd.key_group - ks.kg_start;
-    if (li < 0 || li >= ks.n_kg) return fail(FW_E_INVALID, "key group %d is not owned by this subtask", hd.key_group);
-    if (ks.hash_kind == KH_PRE && !h->keyrow && L > hd.sb_log2)
-        return fail(FW_E_INVALID, "precomputed-hash keys cannot be split finer than the snapshot's sub-buckets");
-    const int nsub = 1 << L;
-    std::vector<int32_t> cnt(nsub);
-    HIP_TRY(hipStreamSynchronize(h->stream));
-    HIP_TRY(hipMemcpy(cnt.data(), h->state_count + ((size_t)li << L), sizeof(int32_t) * nsub, hipMemcpyDeviceToHost));
-    for (int q = 0; q < nsub; q++)
-        if (cnt[q] != 0)  // restored twice, or restored after records of this key group arrived
-            return fail(FW_E_STATE, "key group %d already holds state in this subtask", hd.key_group);
-    std::vector<uint64_t> src((size_t)hd.n * pwe);
-    memcpy(src.data(), (const char*)buf + sizeof hd, src.size() * 8);
-    // key rows: this handle's ids, and the hash that routes each (BinaryRowData.hashCode)
-    std::vector<std::pair<int64_t, int64_t>> map;
-    std::vector<int32_t> hashes;
-    if (h->keyrow) {
-        int64_t used = 0;
-        std::vector<uint64_t> sec((size_t)((size - ent_end) / 8));
-        memcpy(sec.data(), (const char*)buf + ent_end, sec.size() * 8);
-        int rc = kr_restore_section(h, sec.data(), (int64_t)sec.size(), &map, &hashes, &used);
-        if (rc) return rc;
-    }
-    // target superbucket of every entry
-    std::vector<std::vector<uint64_t>> per(nsub);
-    for (int64_t i = 0; i < hd.n; i++) {
-        uint64_t* e = src.data() + (size_t)i * pwe;
-        int sb;
-        if (h->keyrow) {
-            size_t pos = 0;
-            const int64_t id = kr_lookup(map, (int64_t)e[0], &pos);
-            if (id < 0) return fail(FW_E_INVALID, "key-group snapshot entry without its key row");
-            e[0] = (uint64_t)id;
-            uint32_t m;
-            sb = route_key(ks, id, hashes[pos], &m);
-            if ((sb >> L) != li) return fail(FW_E_INVALID, "entry key does not belong to key group %d", hd.key_group);
-        } else if (ks.hash_kind == KH_PRE) {
-            sb = (li << L) + (int)((e[2] >> 32) & (uint64_t)(nsub - 1));
-        } else {
-            uint32_t m;
-            sb = route_key(ks, (int64_t)e[0], 0, &m);
-            if ((sb >> L) != li) return fail(FW_E_INVALID, "entry key does not belong to key group %d", hd.key_group);
-        }
-        auto& v = per[sb - (li << L)];
-        v.insert(v.end(), e, e + pwe);
-        v[v.size() - pwe + 2] = (uint32_t)e[2];  // flags without the source sub-bucket
-    }
-    std::vector<int64_t> mins(nsub);
-    HIP_TRY(hipMemcpy(mins.data(), h->sb_min_timer + ((size_t)li << L), sizeof(int64_t) * nsub, hipMemcpyDeviceToHost));
-    for (int q = 0; q < nsub; q++)
-        if (cnt[q] + (int64_t)(per[q].size() / pwe) > h->cap_e)
-            return fail(FW_E_CAPACITY, "restored key group %d exceeds the state table (%lld entries per superbucket)",
-                        hd.key_group, (long long)h->cap_e);
-    int64_t added = 0;
-    for (int q = 0; q < nsub; q++) {
-        const int64_t n = (int64_t)(per[q].size() / pwe);
-        if (!n) continue;
-        const size_t sb = ((size_t)li << L) + q;
-        HIP_TRY(hipMemcpy(h->state + (sb * h->cap_e + cnt[q]) * pwe, per[q].data(), (size_t)n * pwe * 8,
-                          hipMemcpyHostToDevice));
-        HIP_TRY(hipMemset(h->sb_nar + sb, 0, 1));  // (the superbucket held no entries: cnt[q] == 0)
-        for (int64_t i = 0; i < n; i++)
-            mins[q] = std::min(mins[q], entry_timer_end(h, (int64_t)per[q][(size_t)i * pwe + 1], per[q][(size_t)i * pwe + 2]));
-        cnt[q] += (int32_t)n;
-        added += n;
-    }
-    HIP_TRY(hipMemcpy(h->state_count + ((size_t)li << L), cnt.data(), sizeof(int32_t) * nsub, hipMemcpyHostToDevice));
-    HIP_TRY(hipMemcpy(h->sb_min_timer + ((size_t)li << L), mins.data(), sizeof(int64_t) * nsub, hipMemcpyHostToDevice));
-    Ctrl c;
-    int rc = read_ctrl(h, &c);
-    if (rc) return rc;
-    c.live_entries += added;
-    c.ntp = INT64_MIN;  // next trigger recomputed at the next advance
-    h->dev_ntp = INT64_MIN;
-    HIP_TRY(hipMemcpy(h->ctrl, &c, sizeof c, hipMemcpyHostToDevice));
-    h->push_seq = std::max<int64_t>(h->push_seq, hd.push_seq);
-    h->reset_pending = true;  // as fw_restore: uncollected rows of before the restore are dropped
-    return FW_OK;
-}
-
-// ---- heap keyed-state backend key-group format ------------------------------------------
-// The bytes the heap backend writes for one key group of a window-aggregate operator
-// (HeapSnapshotStrategy.java:161-172): writeInt(keyGroup), then per registered state
-// writeShort(stateId) and that state's key-group writer --
-//   window-aggs ValueState (CopyOnWriteStateMapSnapshot.writeState :127-149):
-//       writeInt(n), then per entry namespace (LongSerializer: 8 B big-endian sliceEnd),
-//       key (BinaryRowData: writeInt(len) + bytes), accumulator (RowDataSerializer -> BinaryRowData)
-//   event / processing window-timers queues (KeyGroupPartitioner.java:241-254 with
-//       TimerSerializer.serialize :147-152): writeInt(n), then per timer
-//       writeLong(flipSignBit(ts)), key, namespace
-// The accumulator row holds every aggregate's buffer fields in order (COUNT(*) / COUNT: count
-// BIGINT; SUM / MIN / MAX: value of the aggregate's type, NULL-able; AVG: sum BIGINT|DOUBLE, count
-// BIGINT), the LOCAL phase's output fields.  A timer's timestamp is
-// toEpochMillsForTimer(window - 1) (SlicingWindowTimerServiceImpl.java:43-46).
-namespace {
-
-constexpr int HEAP_MAX_FIELDS = 2 * FW_MAX_AGGS;
-
-struct HeapWriter {
-    std::vector<uint8_t> b;
-    void u8(uint8_t v) { b.push_back(v); }
-    void be32(uint32_t v) { for (int i = 3; i >= 0; i--) b.push_back((uint8_t)(v >> (8 * i))); }
-    void be16(uint16_t v) { b.push_back((uint8_t)(v >> 8)); b.push_back((uint8_t)v); }
-    void be64(uint64_t v) { for (int i = 7; i >= 0; i--) b.push_back((uint8_t)(v >> (8 * i))); }
-    void bytes(const uint8_t* p, size_t n) { b.insert(b.end(), p, p + n); }
-};
-
-struct HeapReader {
-    const uint8_t* p;
-    size_t n, at = 0;
-    bool bad = false;
-    bool need(size_t k) { if (at + k > n) bad = true; return !bad; }
-    uint32_t be32() { if (!need(4)) return 0; uint32_t v = 0; for (int i = 0; i < 4; i++) v = v << 8 | p[at++]; return v; }
-    uint16_t be16() { if (!need(2)) return 0; uint16_t v = (uint16_t)(p[at] << 8 | p[at + 1]); at += 2; return v; }
-    uint64_t be64() { if (!need(8)) return 0; uint64_t v = 0; for (int i = 0; i < 8; i++) v = v << 8 | p[at++]; return v; }
-    const uint8_t* take(size_t k) { if (!need(k)) return nullptr; const uint8_t* q = p + at; at += k; return q; }
-};
-
-// the accumulator row's field types (FW_T_*), in order
-int heap_fields(const fw_handle* h, int32_t* type) {
-    int j = 0;
-    for (int g = 0; g < h->ad.n; g++) {
-        const int k = h->ad.kind[g], t = h->ad.type[g];
-        if (k == FW_AGG_COUNT_STAR || k == FW_AGG_COUNT) type[j++] = FW_T_I64;
-        else if (k == FW_AGG_AVG) { type[j++] = t == FW_T_F64 ? FW_T_F64 : FW_T_I64; type[j++] = FW_T_I64; }
-        else type[j++] = t;
-    }
-    return j;
-}
-
-int heap_bitset_bytes(int arity) { return ((arity + 63 + 8) / 64) * 8; }  // BinaryRowData.calculateBitSetWidthInBytes
-
-// accumulator words -> buffer field values + NULL mask (emit_partial, restated on the host)
-void heap_words_to_fields(const fw_handle* h, const uint64_t* acc, uint64_t* v, uint32_t* nm) {
-    const AggDesc& ad = h->ad;
-    *nm = 0;
-    int j = 0;
-    for (int g = 0; g < ad.n; g++) {
-        const int kind = ad.kind[g], type = ad.type[g];
-        const uint64_t w0 = acc[ad.w0[g]];
-        const bool no_rows = ad.nn[g] >= 0 && acc[ad.nn[g]] == 0;
-        uint64_t x = w0;
-        bool isnull = false;
-        if (kind == FW_AGG_SUM) {
-            x = type == FW_T_I32 ? (uint64_t)(int64_t)(int32_t)(uint32_t)w0 : w0;
-            isnull = no_rows;
-        } else if (kind == FW_AGG_MIN || kind == FW_AGG_MAX) {
-            if (ad.qf[g] >= 0) {  // q_result (fw_kernel_common.h)
-                const uint64_t f = acc[ad.qf[g]];
-                isnull = f == Q_EMPTY;
-                if (isnull) x = 0;
-                else if ((uint32_t)f) x = (f << 32) | (acc[ad.qn[g]] & 0xFFFFFFFFull);
-                else if ((int64_t)w0 != 0) x = dkey_inv((int64_t)w0);
-                else x = acc[ad.qz[g]] != Q_EMPTY ? ((acc[ad.qz[g]] & 1ull) << 63) : 0ull;
-            } else {
-                x = type == FW_T_F64 ? dkey_inv((int64_t)w0) : w0;
-                isnull = no_rows;
-            }
-        } else if (kind == FW_AGG_AVG) {
-            v[j++] = w0;
-            x = acc[ad.w1[g]];
-        }
-        if (isnull) *nm |= 1u << j;
-        v[j++] = isnull ? 0ull : x;
-    }
-}
-
-// buffer field values -> accumulator words (the inverse; a hidden non-NULL count word becomes 1,
-// its only observable property being != 0, and a MIN/MAX(DOUBLE) group is one element of ordinal 0)
-void heap_fields_to_words(const fw_handle* h, const uint64_t* v, uint32_t nm, uint64_t* acc) {
-    const AggDesc& ad = h->ad;
-    const WordDesc& wd = h->wd;
-    for (int w = 0; w < h->nw_t; w++) acc[w] = w < wd.nw ? word_identity(wd.op[w]) : 0;
-    bool set[MAX_WORDS] = {};
-    int j = 0;
-    for (int g = 0; g < ad.n; g++) {
-        const int kind = ad.kind[g], type = ad.type[g];
-        const int w0 = ad.w0[g];
-        if (kind == FW_AGG_COUNT_STAR || kind == FW_AGG_COUNT) {
-            acc[w0] = v[j++];
-            set[w0] = true;
-            continue;
-        }
-        if (kind == FW_AGG_AVG) {
-            acc[w0] = v[j++];
-            acc[ad.w1[g]] = v[j++];
-            set[w0] = set[ad.w1[g]] = true;
-            continue;
-        }
-        const bool isnull = (nm >> j) & 1u;
-        const uint64_t x = v[j++];
-        if (isnull) continue;  // identity words
-        if (ad.qf[g] >= 0) {  // merge_q_groups' re-encoding
-            const bool nan = f64_isnan(x);
-            acc[ad.qf[g]] = nan ? (x >> 32) : 0ull;
-            if (nan) acc[ad.qn[g]] = x & 0xFFFFFFFFull;
-            if (f64_iszero(x)) acc[ad.qz[g]] = x >> 63;
-            if (!nan) acc[w0] = f64_iszero(x) ? 0ull : (uint64_t)dkey(x);
-            continue;
-        }
-        if ((kind == FW_AGG_MIN || kind == FW_AGG_MAX) && type == FW_T_F64) acc[w0] = (uint64_t)dkey(x);
-        else if (type == FW_T_I32) acc[w0] = (uint64_t)(int64_t)(int32_t)(uint32_t)x;
-        else acc[w0] = x;
-        set[w0] = true;
-    }
-    for (int g = 0; g < ad.n; g++) {  // hidden non-NULL counts of SUM / MIN / MAX
-        const int nn = ad.nn[g];
-        if (nn < 0 || set[nn]) continue;
-        int jj = 0;  // field index of aggregate g
-        for (int q = 0; q < g; q++) jj += ad.kind[q] == FW_AGG_AVG ? 2 : 1;
-        if (!((nm >> jj) & 1u)) acc[nn] = 1;
-    }
-}
-
-void heap_write_row(HeapWriter& w, const fw_handle* h, const uint64_t* v, uint32_t nm) {
-    int32_t type[HEAP_MAX_FIELDS];
-    const int n = heap_fields(h, type);
-    const int bs = heap_bitset_bytes(n);
-    w.be32((uint32_t)(bs + 8 * n));
-    std::vector<uint8_t> row((size_t)(bs + 8 * n), 0);  // header byte 0 = RowKind.INSERT
-    for (int j = 0; j < n; j++) {
-        if ((nm >> j) & 1u) {
-            row[(size_t)(j + 8) / 8] |= (uint8_t)(1u << ((j + 8) % 8));
-            continue;
-        }
-        const uint64_t x = type[j] == FW_T_I32 ? (uint32_t)v[j] : v[j];
-        memcpy(row.data() + bs + 8 * j, &x, 8);  // little-endian slot; an INT in its low 4 bytes
-    }
-    w.bytes(row.data(), row.size());
-}
-
-bool heap_read_row(HeapReader& r, const fw_handle* h, uint64_t* v, uint32_t* nm) {
-    int32_t type[HEAP_MAX_FIELDS];
-    const int n = heap_fields(h, type);
-    const int bs = heap_bitset_bytes(n);
-    const uint32_t len = r.be32();
-    if (r.bad || len != (uint32_t)(bs + 8 * n)) return false;
-    const uint8_t* p = r.take(len);
-    if (!p) return false;
-    *nm = 0;
-    for (int j = 0; j < n; j++) {
-        if ((p[(j + 8) / 8] >> ((j + 8) % 8)) & 1u) { *nm |= 1u << j; v[j] = 0; continue; }
-        uint64_t x;
-        memcpy(&x, p + bs + 8 * j, 8);
-        v[j] = type[j] == FW_T_I32 ? (uint64_t)(int64_t)(int32_t)(uint32_t)x : x;
-    }
-    return true;
-}
-
-// the key's BinaryRowData image: BINROW_BIGINT / BINROW_INT keys are the one-field row the key
-// projection writes (8 B header, the value slot); key rows carry their interned image
-int heap_key_kind(const fw_handle* h) {
-    if (h->keyrow) return FW_KEYHASH_KEYROW;
-    const int k = h->cfg.key_hash;
-    return k == FW_KEYHASH_BINROW_BIGINT || k == FW_KEYHASH_BINROW_INT ? k : -1;
-}
-
-int heap_check(const fw_handle* h, const fw_heap_state_ids* ids) {
-    if (!ids) return fail(FW_E_INVALID, "null state ids");
-    if (h->cfg.api != FW_API_SQL || h->cfg.agg_phase == FW_PHASE_LOCAL)
-        return fail(FW_E_INVALID, "the heap key-group format is the SQL window-aggregate operator's keyed state");
-    if (heap_key_kind(h) < 0)
-        return fail(FW_E_INVALID, "the heap key-group format needs SQL key rows (BINROW_BIGINT, BINROW_INT or KEYROW keys)");
-    if (ids->window_state == ids->event_timers || ids->window_state == ids->processing_timers ||
-        ids->event_timers == ids->processing_timers)
-        return fail(FW_E_INVALID, "state ids must differ");
-    return FW_OK;
-}
-
-}  // namespace
-
-int fw_snapshot_key_group_heap(fw_handle* h, int32_t key_group, const fw_heap_state_ids* ids, void* buf,
-                               int64_t capacity, int64_t* size) {
-    if (!h || !size) return fail(FW_E_INVALID, "null argument");
-    CW_REFUSE(h, "fw_snapshot_key_group_heap");
-    int rc = heap_check(h, ids);
-    if (rc) return rc;
-    // the device state of the key group, in this library's own key-group format
-    int64_t n_int = 0;
-    if ((rc = fw_snapshot_key_group(h, key_group, nullptr, 0, &n_int))) return rc;
-    std::vector<uint64_t> blob((size_t)(n_int + 7) / 8);
-    if ((rc = fw_snapshot_key_group(h, key_group, blob.data(), (int64_t)blob.size() * 8, &n_int))) return rc;
-    KgHeader hd;
-    memcpy(&hd, blob.data(), sizeof hd);
-    const int pwe = h->pwe, nw = h->nw_t;
-    const uint64_t* ent = blob.data() + sizeof hd / 8;
-    // key images
-    std::unordered_map<int64_t, std::pair<const uint8_t*, uint32_t>> img;
-    if (h->keyrow) {
-        const uint64_t* sec = ent + (size_t)hd.n * pwe;
-        const int64_t nk = (int64_t)sec[0];
-        size_t p = 1;
-        for (int64_t k = 0; k < nk; k++) {
-            const uint32_t len = (uint32_t)sec[p + 1];
-            img[(int64_t)sec[p]] = {(const uint8_t*)(sec + p + 2), len};
-            p += 2 + len / 8;
-        }
-    }
-    const int kk = heap_key_kind(h);
-    auto write_key = [&](HeapWriter& w, int64_t key) {
-        if (kk == FW_KEYHASH_KEYROW) {
-            const auto& im = img.at(key);
-            w.be32(im.second);
-            w.bytes(im.first, im.second);
-            return;
-        }
-        uint8_t row[16] = {};
-        const uint64_t x = kk == FW_KEYHASH_BINROW_INT ? (uint32_t)key : (uint64_t)key;
-        memcpy(row + 8, &x, 8);
-        w.be32(16);
-        w.bytes(row, 16);
-    };
-    struct St { int64_t key, ns; const uint64_t* acc; };
-    std::vector<St> states;
-    std::vector<std::pair<int64_t, int64_t>> timers;  // (key, window)
-    std::vector<uint64_t> slot_acc;
-    const WinDesc& win = h->win;
-    if (win.hopb) {
-        // block entries -> one (key, sliceEnd) state per slot with data.  Timers: the reference holds
-        // one per unfired slice end with data (AggCombiner.combine step 5) and one at the first
-        // unfired window end whose window holds data (the nextTriggerWindow chain, or a late
-        // record's registration).  A chain timer at an EMPTY window (its predecessor's only data
-        // was in the slice that window expired) is not derivable from the expired state; it fires
-        // without output, and is the one timer the export leaves out.
-        std::unordered_map<int64_t, std::vector<int64_t>> ends;  // key -> slice ends with data
-        for (int64_t i = 0; i < hd.n; i++) {
-            const uint64_t* e = ent + (size_t)i * pwe;
-            const uint32_t mask = (uint32_t)e[2] >> HB_MASK_SHIFT;
-            for (int s = 0; s < HB_R; s++)
-                if ((mask >> s) & 1u) {
-                    const int64_t se = wadd((int64_t)e[1], (int64_t)(s + 1) * win.interval);
-                    states.push_back({(int64_t)e[0], se, e + 3 + s * nw});
-                    ends[(int64_t)e[0]].push_back(se);
-                }
-        }
-        for (auto& kv : ends) {
-            auto& v = kv.second;
-            std::sort(v.begin(), v.end());
-            for (int64_t se : v)
-                if (!win_fired(win, se, hd.cur)) timers.push_back({kv.first, se});
-            if (win_fired(win, v.front(), hd.cur)) {  // some data slice fired: the chain's next window
-                int64_t e1 = v.front();
-                while (win_fired(win, e1, hd.cur)) e1 = wadd(e1, win.interval);
-                const int64_t lo = wsub(e1, win.size);  // window (e1 - size, e1] holds data?
-                const bool data = std::any_of(v.begin(), v.end(), [&](int64_t se) { return se > lo && se <= e1; });
-                if (data && !std::binary_search(v.begin(), v.end(), e1)) timers.push_back({kv.first, e1});
-            }
-        }
-    } else {
-        for (int64_t i = 0; i < hd.n; i++) {
-            const uint64_t* e = ent + (size_t)i * pwe;
-            if (e[2] & F_ACC) states.push_back({(int64_t)e[0], (int64_t)e[1], e + 3});
-            if (e[2] & F_TIMER) timers.push_back({(int64_t)e[0], (int64_t)e[1]});
-        }
-    }
-    std::sort(timers.begin(), timers.end(), [&](const std::pair<int64_t, int64_t>& a, const std::pair<int64_t, int64_t>& b) {
-        return a.second != b.second ? a.second < b.second : a.first < b.first;
-    });
-    HeapWriter w;
-    w.be32((uint32_t)key_group);
-    const int16_t order[3] = {ids->window_state, ids->event_timers, ids->processing_timers};
-    int16_t sorted[3] = {order[0], order[1], order[2]};
-    std::sort(sorted, sorted + 3);
-    for (int16_t sid : sorted) {
-        w.be16((uint16_t)sid);
-        if (sid == ids->window_state) {
-            w.be32((uint32_t)states.size());
-            uint64_t v[HEAP_MAX_FIELDS];
-            uint32_t nm;
-            for (const St& s : states) {
-                w.be64((uint64_t)s.ns);
-                write_key(w, s.key);
-                heap_words_to_fields(h, s.acc, v, &nm);
-                heap_write_row(w, h, v, nm);
-            }
-        } else if (sid == ids->event_timers) {
-            w.be32((uint32_t)timers.size());
-            for (const auto& t : timers) {
-                const int64_t ts = tz_epoch_for_timer(win.tz, wsub(t.second, 1));
-                w.be64((uint64_t)ts ^ (1ull << 63));  // MathUtils.flipSignBit
-                write_key(w, t.first);
-                w.be64((uint64_t)t.second);
-            }
-        } else {
-            w.be32(0);  // event-time operator: no processing-time timers
-        }
-    }
-    *size = (int64_t)w.b.size();
-    if (!buf) return FW_OK;
-    if (capacity < *size) return fail(FW_E_INVALID, "snapshot buffer too small (%lld < %lld)", (long long)capacity, (long long)*size);
-    memcpy(buf, w.b.data(), w.b.size());
-    return FW_OK;
-}
-
-int fw_restore_key_group_heap(fw_handle* h, const void* buf, int64_t size, const fw_heap_state_ids* ids) {
-    if (!h || !buf || size < 0) return fail(FW_E_INVALID, "null argument");
-    CW_REFUSE(h, "fw_restore_key_group_heap");
-    int rc = heap_check(h, ids);
-    if (rc) return rc;
-    HeapReader r{(const uint8_t*)buf, (size_t)size};
-    const int32_t kg = (int32_t)r.be32();
-    const int kk = heap_key_kind(h);
-    // keys: BIGINT / INT values, or key-row images numbered in order of appearance
-    std::vector<std::vector<uint8_t>> images;
-    std::map<std::vector<uint8_t>, int64_t> image_id;
-    auto read_key = [&](int64_t* key) -> bool {
-        const uint32_t len = r.be32();
-        if (r.bad || len > (1u << 24)) return false;
-        const uint8_t* p = r.take(len);
-        if (!p) return false;
-        if (kk == FW_KEYHASH_KEYROW) {
-            if (len % 8) return false;
-            std::vector<uint8_t> im(p, p + len);
-            auto it = image_id.find(im);
-            if (it == image_id.end()) {
-                it = image_id.emplace(im, (int64_t)images.size()).first;
-                images.push_back(im);
-            }
-            *key = it->second;
-            return true;
-        }
-        if (len != 16) return false;
-        for (int i = 0; i < 8; i++)
-            if (p[i]) return false;  // RowKind INSERT, key field not NULL
-        uint64_t x;
-        memcpy(&x, p + 8, 8);
-        *key = kk == FW_KEYHASH_BINROW_INT ? (int64_t)(int32_t)(uint32_t)x : (int64_t)x;
-        return kk == FW_KEYHASH_BINROW_BIGINT || (x >> 32) == 0;
-    };
-    struct Acc { uint64_t v[HEAP_MAX_FIELDS]; uint32_t nm; };
-    std::map<std::pair<int64_t, int64_t>, std::pair<int, int>> ent;  // (key, ns) -> (state index or -1, timer)
-    std::vector<Acc> accs;
-    bool seen[3] = {};
-    while (!r.bad && r.at < r.n) {
-        const int16_t sid = (int16_t)r.be16();
-        const uint32_t n = r.be32();
-        if (r.bad) break;
-        if (sid == ids->window_state && !seen[0]) {
-            seen[0] = true;
-            for (uint32_t i = 0; i < n && !r.bad; i++) {
-                const int64_t ns = (int64_t)r.be64();
-                int64_t key;
-                Acc a;
-                if (!read_key(&key) || !heap_read_row(r, h, a.v, &a.nm)) { r.bad = true; break; }
-                auto& slot = ent.emplace(std::make_pair(key, ns), std::make_pair(-1, 0)).first->second;
-                if (slot.first >= 0) return fail(FW_E_INVALID, "duplicate window state (key, namespace) in key group %d", kg);
-                slot.first = (int)accs.size();
-                accs.push_back(a);
-            }
-        } else if (sid == ids->event_timers && !seen[1]) {
-            seen[1] = true;
-            for (uint32_t i = 0; i < n && !r.bad; i++) {
-                const int64_t ts = (int64_t)(r.be64() ^ (1ull << 63));
-                int64_t key;
-                if (!read_key(&key)) { r.bad = true; break; }
-                const int64_t ns = (int64_t)r.be64();
-                if (ts != tz_epoch_for_timer(h->win.tz, wsub(ns, 1)))
-                    return fail(FW_E_INVALID, "timer %lld of window %lld is not the window's end timer", (long long)ts, (long long)ns);
-                ent.emplace(std::make_pair(key, ns), std::make_pair(-1, 0)).first->second.second = 1;
-            }
-        } else if (sid == ids->processing_timers && !seen[2]) {
-            seen[2] = true;
-            if (n != 0) return fail(FW_E_INVALID, "processing-time timers in an event-time window operator");
-        } else {
-            return fail(FW_E_INVALID, "unexpected state id %d in key group %d", (int)sid, kg);
-        }
-    }
-    if (r.bad) return fail(FW_E_INVALID, "heap key-group data truncated or malformed");
-    // -> this library's key-group blob, restored by fw_restore_key_group
-    const int pwe = h->pwe, nw = h->nw_t;
-    const WinDesc& win = h->win;
-    std::vector<uint64_t> out;
-    int64_t n_out = 0;
-    if (win.hopb) {  // (key, sliceEnd) states -> blocks; timers are arithmetic there
-        std::map<std::pair<int64_t, int64_t>, size_t> blk;  // (key, block start) -> word offset
-        for (const auto& kv : ent) {
-            if (kv.second.first < 0) continue;  // a timer without state fires without output
-            const int64_t key = kv.first.first, se = kv.first.second;
-            const int64_t bs = window_start(wsub(se, 1), win.offset, win.hb_span_div);
-            const int slot = (int)((se - bs) / win.interval) - 1;
-            if (slot < 0 || slot >= HB_R || wadd(bs, (int64_t)(slot + 1) * win.interval) != se)
-                return fail(FW_E_INVALID, "namespace %lld is not a slice end of this window", (long long)se);
-            auto it = blk.find({key, bs});
-            if (it == blk.end()) {
-                it = blk.emplace(std::make_pair(key, bs), out.size()).first;
-                out.resize(out.size() + pwe, 0);
-                uint64_t* e = out.data() + it->second;
-                e[0] = (uint64_t)key;
-                e[1] = (uint64_t)bs;
-                for (int s = 0; s < HB_R; s++)
-                    for (int x = 0; x < nw; x++) e[3 + s * nw + x] = x < h->wd.nw ? word_identity(h->wd.op[x]) : 0;
-                n_out++;
-            }
-            uint64_t* e = out.data() + it->second;
-            e[2] |= (uint64_t)(1u << slot) << HB_MASK_SHIFT;
-            const Acc& a = accs[(size_t)kv.second.first];
-            heap_fields_to_words(h, a.v, a.nm, e + 3 + slot * nw);
-        }
-    } else {
-        for (const auto& kv : ent) {
-            out.resize(out.size() + pwe, 0);
-            uint64_t* e = out.data() + (size_t)n_out * pwe;
-            e[0] = (uint64_t)kv.first.first;
-            e[1] = (uint64_t)kv.first.second;
-            e[2] = (kv.second.first >= 0 ? F_ACC : 0u) | (kv.second.second ? F_TIMER : 0u);
-            if (kv.second.first >= 0) heap_fields_to_words(h, accs[(size_t)kv.second.first].v, accs[(size_t)kv.second.first].nm, e + 3);
-            else
-                for (int x = 0; x < nw; x++) e[3 + x] = x < h->wd.nw ? word_identity(h->wd.op[x]) : 0;
-            n_out++;
-        }
-    }
-    Ctrl c;
-    if ((rc = read_ctrl(h, &c))) return rc;
-    KgHeader hd{KG_MAGIC, 3, kg, pwe, h->wd.nw, h->ks.sb_per_kg_log2, h->cfg.key_hash, h->win.size, h->win.interval,
-                c.cur, n_out, semantics_fingerprint(h), (int64_t)h->push_seq};
-    std::vector<uint64_t> blob(sizeof hd / 8);
-    memcpy(blob.data(), &hd, sizeof hd);
-    blob.insert(blob.end(), out.begin(), out.end());
-    if (h->keyrow) {  // key-row section: [n][id, length, image words]
-        blob.push_back((uint64_t)images.size());
-        for (size_t k = 0; k < images.size(); k++) {
-            blob.push_back((uint64_t)k);
-            blob.push_back((uint64_t)images[k].size());
-            const size_t at = blob.size();
-            blob.resize(at + images[k].size() / 8);
-            memcpy(blob.data() + at, images[k].data(), images[k].size());
-        }
-    }
-    return fw_restore_key_group(h, blob.data(), (int64_t)blob.size() * 8);
-}
-
-// ---- DataStream WindowOperator key-group state ---------------------------------------------
-// A heap-backend savepoint of the DataStream WindowOperator holds, per key group, the
-// "window-contents" reducing state (WindowOperatorBuilder.java:81: namespace TimeWindow, value the
-// reduced record) and the "window-timers" queues (WindowOperator.java:232).  The value is the user's
-// record type -- value1 with the aggregated field set, whose bytes only the operator shim can write
-// -- so the heap bytes are assembled there (flink_amd/datastream/heap_state.py); this pair moves
-// the device side as one fw_ds_window per (key, window) holding state or a timer.
-namespace {
-
-int ds_state_check(const fw_handle* h) {
-    if (h->cfg.api != FW_API_DATASTREAM)
-        return fail(FW_E_INVALID, "DataStream key-group windows are the DataStream WindowOperator's state");
-    // LONG / INT keys are re-routed from the key itself; precomputed-hash keys (interned String keys)
-    // from the hash the shim passes with each restored window (fw_ds_window.key_hash)
-    if (h->cfg.key_hash != FW_KEYHASH_LONG && h->cfg.key_hash != FW_KEYHASH_INT && h->cfg.key_hash != FW_KEYHASH_PRECOMPUTED)
-        return fail(FW_E_INVALID, "DataStream key-group windows need LONG, INT or precomputed-hash keys");
-    if (h->ad.n != 1) return fail(FW_E_INVALID, "DataStream key-group windows hold one aggregated field");
-    return FW_OK;
-}
-
-// the field value of a window from its words (emit_row's DataStream branch, restated on the host)
-uint64_t ds_value_of(const fw_handle* h, const uint64_t* acc) {
-    const AggDesc& ad = h->ad;
-    const uint64_t w0 = acc[ad.w0[0]];
-    switch (ad.kind[0]) {
-        case FW_AGG_SUM: return ad.type[0] == FW_T_I32 ? (uint64_t)(int64_t)(int32_t)(uint32_t)w0 : w0;
-        case FW_AGG_MIN:
-        case FW_AGG_MAX:
-        case FW_AGG_MINBY:
-        case FW_AGG_MAXBY: {
-            uint64_t v = ad.type[0] == FW_T_F64 ? dkey_inv((int64_t)w0) : w0;
-            if (ad.dn_hi[0] >= 0 && f64_isnan(v)) v = (acc[ad.dn_hi[0]] << 32) | (acc[ad.dn_lo[0]] & 0xFFFFFFFFull);
-            return v;
-        }
-        default: return w0;  // counts
-    }
-}
-
-// the words of a window state holding `value` whose first element has ordinal `first` (the state
-// after one element of that value, in its written-back form: NaN bits at ordinal 0)
-void ds_words_of(const fw_handle* h, uint64_t value, int64_t first, uint64_t* acc) {
-    const AggDesc& ad = h->ad;
-    const WordDesc& wd = h->wd;
-    for (int w = 0; w < h->nw_t; w++) acc[w] = w < wd.nw ? word_identity(wd.op[w]) : 0;
-    const int w0 = ad.w0[0];
-    const bool f = ad.type[0] == FW_T_F64;
-    switch (ad.kind[0]) {
-        case FW_AGG_SUM: acc[w0] = ad.type[0] == FW_T_I32 ? (uint64_t)(int64_t)(int32_t)(uint32_t)value : value; break;
-        case FW_AGG_MIN:
-        case FW_AGG_MAX:
-            acc[w0] = f ? (uint64_t)dkey(value) : ad.type[0] == FW_T_I32 ? (uint64_t)(int64_t)(int32_t)(uint32_t)value : value;
-            if (ad.dn_hi[0] >= 0 && f64_isnan(value)) {
-                acc[ad.dn_hi[0]] = value >> 32;
-                acc[ad.dn_lo[0]] = value & 0xFFFFFFFFull;
-            }
-            break;
-        case FW_AGG_MINBY:
-        case FW_AGG_MAXBY:
-            acc[w0] = f ? (uint64_t)dkey(f64_isnan(value) ? 0x7FF8000000000000ull : value)
-                        : ad.type[0] == FW_T_I32 ? (uint64_t)(int64_t)(int32_t)(uint32_t)value : value;
-            acc[ad.by_prev] = (uint64_t)first;  // the restored element is retained
-            break;
-        default: acc[w0] = value; break;
-    }
-    // hidden counts (the sliding window's COUNT(*), a non-NULL count): only != 0 is observable
-    if (ad.count_star_word >= 0 && ad.count_star_word != w0) acc[ad.count_star_word] = 1;
-    if (ad.nn[0] >= 0 && ad.nn[0] != w0) acc[ad.nn[0]] = 1;
-    if (ad.first_word >= 0) acc[ad.first_word] = (uint64_t)first;
-}
-
-}  // namespace
-
-int fw_ds_snapshot_key_group(fw_handle* h, int32_t key_group, fw_ds_window* out, int64_t capacity, int64_t* n) {
-    if (!h || !n) return fail(FW_E_INVALID, "null argument");
-    CW_REFUSE(h, "fw_ds_snapshot_key_group");
-    int rc = ds_state_check(h);
-    if (rc) return rc;
-    int64_t sz = 0;
-    if ((rc = fw_snapshot_key_group(h, key_group, nullptr, 0, &sz))) return rc;  // flushes
-    std::vector<uint64_t> blob((size_t)(sz + 7) / 8);
-    if ((rc = fw_snapshot_key_group(h, key_group, blob.data(), (int64_t)blob.size() * 8, &sz))) return rc;
-    KgHeader hd;
-    memcpy(&hd, blob.data(), sizeof hd);
-    const int pwe = h->pwe;
-    const uint64_t* ent = blob.data() + sizeof hd / 8;
-    int64_t m = 0;
-    for (int64_t i = 0; i < hd.n; i++) {
-        const uint64_t* e = ent + (size_t)i * pwe;
-        const uint32_t f = (uint32_t)e[2];
-        const int32_t fl = ((f & F_ACC) ? FW_DSW_CONTENTS : 0) | ((f & F_TIMER) ? FW_DSW_TRIGGER : 0) |
-                           ((f & F_CLEAN) ? FW_DSW_CLEANUP : 0);
-        if (!fl) continue;
-        if (out && m < capacity) {
-            fw_ds_window& w = out[m];
-            w.key = (int64_t)e[0];
-            w.window_end = (int64_t)e[1];
-            w.value = (f & F_ACC) ? (int64_t)ds_value_of(h, e + 3) : 0;
-            w.first_ord = (f & F_ACC) && h->ad.first_word >= 0 ? (int64_t)e[3 + h->ad.first_word] : -1;
-            w.flags = fl;
-            w.key_hash = 0;
-        }
-        m++;
-    }
-    *n = m;
-    if (out && capacity < m) return fail(FW_E_INVALID, "window buffer too small (%lld < %lld)", (long long)capacity, (long long)m);
-    return FW_OK;
-}
-
-int fw_ds_restore_key_group(fw_handle* h, int32_t key_group, const fw_ds_window* in, int64_t n, int64_t next_push_seq) {
-    if (!h || (n > 0 && !in) || n < 0) return fail(FW_E_INVALID, "null argument");
-    CW_REFUSE(h, "fw_ds_restore_key_group");
-    int rc = ds_state_check(h);
-    if (rc) return rc;
-    const WinDesc& win = h->win;
-    const int pwe = h->pwe;
-    if (key_group < h->ks.kg_start || key_group >= h->ks.kg_start + h->ks.n_kg)
-        return fail(FW_E_INVALID, "key group %d is not owned by this subtask", key_group);
-    std::vector<uint64_t> ent;
-    ent.reserve((size_t)n * pwe);
-    for (int64_t i = 0; i < n; i++) {
-        const fw_ds_window& w = in[i];
-        if (w.flags & ~(FW_DSW_CONTENTS | FW_DSW_TRIGGER | FW_DSW_CLEANUP) || !w.flags)
-            return fail(FW_E_INVALID, "window %lld: bad flags %d", (long long)i, w.flags);
-        // a window of this assigner: start = end - size on the slide grid (SlidingEventTimeWindows
-        // .assignWindows :77-90; tumbling: slide = size)
-        const int64_t st = wsub(w.window_end, win.size);
-        if (window_start(st, win.offset, win.slide_div) != st)
-            return fail(FW_E_INVALID, "window [%lld, %lld) is not a window of this assigner", (long long)st, (long long)w.window_end);
-        if ((w.flags & FW_DSW_CLEANUP) && ds_cleanup_time(win, w.window_end) == INT64_MAX)
-            return fail(FW_E_INVALID, "window %lld has no cleanup time but a cleanup timer", (long long)w.window_end);
-        // precomputed-hash keys (a shim's interned String keys): the window's superbucket comes from
-        // the key's hash, routed as the ingest routes the key's records; the sub-bucket rides in the
-        // high half of the flags word like a key-group blob's (fw_restore_key_group)
-        uint64_t sub = 0;
-        if (h->ks.hash_kind == KH_PRE && !h->keyrow) {
-            uint32_t m;
-            const int sb = route_key(h->ks, w.key, w.key_hash, &m);
-            if ((sb >> h->ks.sb_per_kg_log2) != key_group - h->ks.kg_start)
-                return fail(FW_E_INVALID, "window %lld: key hash %d is not in key group %d", (long long)i, w.key_hash, key_group);
-            sub = (uint64_t)(sb & ((1 << h->ks.sb_per_kg_log2) - 1));
-        }
-        const size_t at = ent.size();
-        ent.resize(at + pwe, 0);
-        uint64_t* e = ent.data() + at;
-        e[0] = (uint64_t)w.key;
-        e[1] = (uint64_t)w.window_end;
-        e[2] = ((w.flags & FW_DSW_CONTENTS) ? F_ACC : 0u) | ((w.flags & FW_DSW_TRIGGER) ? F_TIMER : 0u) |
-               ((w.flags & FW_DSW_CLEANUP) ? F_CLEAN : 0u) | (sub << 32);
-        if (w.flags & FW_DSW_CONTENTS) {
-            if (h->ad.first_word >= 0 && (w.first_ord < 0 || (w.first_ord >> 32) >= next_push_seq))
-                return fail(FW_E_INVALID, "window %lld: first element ordinal not below push %lld", (long long)i,
-                            (long long)next_push_seq);
-            ds_words_of(h, (uint64_t)w.value, w.first_ord, e + 3);
-        } else {
-            for (int x = 0; x < h->nw_t; x++) e[3 + x] = x < h->wd.nw ? word_identity(h->wd.op[x]) : 0;
-        }
-    }
-    Ctrl c;
-    if ((rc = read_ctrl(h, &c))) return rc;
-    KgHeader hd{KG_MAGIC, 3, key_group, pwe, h->wd.nw, h->ks.sb_per_kg_log2, h->cfg.key_hash, win.size, win.interval,
-                c.cur, (int64_t)(ent.size() / pwe), semantics_fingerprint(h), std::max<int64_t>(next_push_seq, 0)};
-    std::vector<uint64_t> blob(sizeof hd / 8);
-    memcpy(blob.data(), &hd, sizeof hd);
-    blob.insert(blob.end(), ent.begin(), ent.end());
-    return fw_restore_key_group(h, blob.data(), (int64_t)blob.size() * 8);
 }
 
 // ---- host-side restatements (the exact code the kernels run), for host partitioners/tests
