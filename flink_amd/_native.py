@@ -53,6 +53,8 @@ def lib():
         "fw_push_device_packed_segments": (i32, [vp, i32, i64, vp, vp, i32]),
         "fw_push_device_count_segments": (i32, [vp, i32, i64, vp, vp, vp, vp]),
         "fw_push_device_count_packed_segments": (i32, [vp, i32, i64, vp, vp, i32]),
+        "fw_push_device_count_record_packed_segments": (i32, [vp, i32, i64, vp, vp, i32]),
+        "fw_count_record_rows": (i32, [vp, vp, i32, i64, P(abi.fw_record_rows)]),
         "fw_partition_packed": (i32, [vp, vp, vp, vp, i32, i64, i32, i32, i32, i64, vp, vp, vp, i64, vp]),
         "fw_partition_packed_spill": (i32, [vp, vp, vp, vp, i32, i64, i32, i32, i32, i64, vp, vp, vp, vp, i64, vp]),
         "fw_partition_packed_spill_dn": (i32, [vp, vp, vp, vp, i32, i64, vp, i32, i32, i32, i64, vp, vp, vp, vp, i64, vp]),
@@ -124,6 +126,7 @@ def lib():
 EXPORTED = ["fw_create", "fw_destroy", "fw_last_error", "fw_abi_version", "fw_device_count", "fw_get_stream", "fw_sync",
             "fw_initialize_watermark", "fw_reserve", "fw_commit", "fw_commit_delta32", "fw_delta32_encode", "fw_push_device", "fw_push_device_segments", "fw_push_device_packed_segments", "fw_advance", "fw_advance_device",
             "fw_push_device_count_segments", "fw_push_device_count_packed_segments",
+            "fw_push_device_count_record_packed_segments", "fw_count_record_rows",
             "fw_flush", "fw_results", "fw_results_reset", "fw_results_async", "fw_results_ready", "fw_results_device", "fw_get_stats", "fw_set_profiling",
             "fw_get_kernel_times", "fw_ingest_pack_launches", "fw_ingest_pack_geometry", "fw_merge_path_superbuckets", "fw_host_ig_pack_choice", "fw_snapshot", "fw_restore", "fw_snapshot_key_group", "fw_restore_key_group",
             "fw_snapshot_key_group_heap", "fw_restore_key_group_heap", "fw_ds_snapshot_key_group", "fw_ds_restore_key_group", "fw_results_device_segments", "fw_key_row_hash", "fw_host_key_row_hash",

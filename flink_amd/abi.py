@@ -163,6 +163,13 @@ class fw_ordinal_events(C.Structure):
                 ("n_release", C.c_int64), ("release", C.POINTER(C.c_int64))]
 
 
+class fw_record_rows(C.Structure):
+    """flinkwin.h fw_count_record_rows: the record fields beside a record push's events and result rows"""
+    _fields_ = [("n_fields", C.c_int64), ("n_ev", C.c_int64), ("ev_ord", C.POINTER(C.c_int64)),
+                ("ev_is_retain", C.POINTER(C.c_uint8)), ("ev_words", C.POINTER(C.c_int64)),
+                ("n_res", C.c_int64), ("res_words", C.POINTER(C.c_int64)), ("res_from_push", C.POINTER(C.c_uint8))]
+
+
 class fw_late_rows(C.Structure):
     _fields_ = [("n", C.c_int64), ("key", C.POINTER(C.c_int64)), ("ts", C.POINTER(C.c_int64)),
                 ("values", C.POINTER(C.c_int64) * FW_MAX_COLS), ("push_seq", C.POINTER(C.c_int64)),

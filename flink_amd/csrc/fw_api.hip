@@ -1519,6 +1519,101 @@ int fw_push_device_count_packed_segments(fw_handle* h, int32_t n_segs, int64_t s
     return cw_push_segments(&h->cw, n_segs, seg_len, d_seg_counts, d_rows, nullptr, (const uint64_t*)d_rows + 2, row_words);
 }
 
+// The record count handle's own exchange entries: the count handle's two above keep refusing it.
+#define CW_ONLY_RECORD_EXCHANGE(h, name)                                                                                   \
+    if ((h)->sw.on) return fail(FW_E_INVALID, name ": not for session windows (record count windows only)");               \
+    if (!(h)->cw.on) return fail(FW_E_INVALID, name ": not for time windows (record count windows only)");                 \
+    if (!(h)->cw.rec)                                                                                                      \
+        return fail(FW_E_INVALID, name ": not for count windows (FW_WIN_COUNT: fw_push_device_count_packed_segments)");     \
+    if ((h)->cfg.parallelism <= 1)                                                                                         \
+        return fail(FW_E_INVALID, name ": a record count handle of parallelism 1 has no keyBy exchange in front of it")
+
+int fw_push_device_count_record_packed_segments(fw_handle* h, int32_t n_segs, int64_t seg_len, const int64_t* d_seg_counts,
+                                                const int64_t* d_rows, int32_t row_words) {
+    if (!h) return fail(FW_E_INVALID, "null handle");
+    CW_ONLY_RECORD_EXCHANGE(h, "fw_push_device_count_record_packed_segments");
+    if (n_segs < 0 || seg_len < 1 || (n_segs > 0 && !d_seg_counts)) return fail(FW_E_INVALID, "bad segments");
+    if (row_words != 2 + h->cfg.n_value_cols)
+        return fail(FW_E_INVALID, "fw_push_device_count_record_packed_segments: row_words %d != 2 + value columns (%d record fields)",
+                    row_words, h->cfg.n_value_cols);
+    if (h->cfg.key_hash == FW_KEYHASH_PRECOMPUTED)
+        return fail(FW_E_INVALID, "fw_push_device_count_record_packed_segments: packed rows carry no key-hash column");
+    if (seg_len > h->cfg.max_batch_rows)  // (keeps n_segs * seg_len in range below)
+        return fail(FW_E_INVALID, "fw_push_device_count_record_packed_segments: seg_len = %lld exceeds max_batch_rows (%lld)",
+                    (long long)seg_len, (long long)h->cfg.max_batch_rows);
+    if (n_segs == 0) return FW_OK;
+    if (!d_rows) return fail(FW_E_INVALID, "null rows");
+    // (key, unread word, the record's fields): the aggregated field is word 2 + input_col
+    return cw_push_record_segments(&h->cw, n_segs, seg_len, d_seg_counts, d_rows, row_words);
+}
+
+int fw_count_record_rows(fw_handle* h, const int64_t* d_rows, int32_t row_words, int64_t n_rows, fw_record_rows* out) {
+    if (!h || !out) return fail(FW_E_INVALID, "null argument");
+    CW_ONLY_RECORD_EXCHANGE(h, "fw_count_record_rows");
+    memset(out, 0, sizeof *out);
+    CountOp& w = h->cw;
+    const int32_t F = h->cfg.n_value_cols;
+    if (row_words != 2 + F)
+        return fail(FW_E_INVALID, "fw_count_record_rows: row_words %d != 2 + value columns (%d record fields)", row_words, F);
+    if (n_rows < 0 || n_rows >= (1ll << 32) || (n_rows > 0 && !d_rows)) return fail(FW_E_INVALID, "fw_count_record_rows: bad rows");
+    if (w.push_seq == 0) return fail(FW_E_STATE, "fw_count_record_rows without a push");
+    int rc = cw_record_rows(&w, d_rows, row_words, n_rows, F);
+    if (rc) return rc;
+    Ctrl c;
+    memset(&c, 0, sizeof c);
+    rc = read_ctrl(h, &c);  // the one host wait: behind the push and the gather
+    if (rc && c.error != ERR_ORDEV) return rc;  // (an event overflow stays readable, as in fw_first_element_events)
+    const int64_t n_ev = std::min<int64_t>(c.n_ordev, w.ordev_cap);
+    const int64_t n_res = std::min<int64_t>((int64_t)c.out_count[0], w.out_cap);
+    h->rr_ord.resize((size_t)n_ev);
+    h->rr_rord.resize((size_t)n_res);
+    if (n_ev) HIP_TRY(hipMemcpy(h->rr_ord.data(), w.ordev, (size_t)n_ev * 8, hipMemcpyDeviceToHost));
+    if (n_res) HIP_TRY(hipMemcpy(h->rr_rord.data(), w.out_rord, (size_t)n_res * 8, hipMemcpyDeviceToHost));
+    const uint64_t seq = (uint64_t)(w.push_seq - 1);
+    h->rr_is_retain.assign((size_t)n_ev, 0);
+    h->rr_from_push.assign((size_t)n_res, 0);
+    for (int64_t i = 0; i < n_ev; i++) {  // nothing is consumed before every named row is known to lie in the buffer
+        const int64_t e = h->rr_ord[i];
+        if (e & ORDEV_RELEASE) continue;
+        h->rr_is_retain[i] = 1;
+        if (((uint64_t)e >> 32) != seq)
+            return fail(FW_E_INVALID, "fw_count_record_rows: a retain event names push %lld, not the last push %lld (call it after every push)",
+                        (long long)((uint64_t)e >> 32), (long long)seq);
+        if ((e & 0xffffffffll) >= n_rows)
+            return fail(FW_E_INVALID, "fw_count_record_rows: a retain event names row %lld of the push, n_rows is %lld",
+                        (long long)(e & 0xffffffffll), (long long)n_rows);
+    }
+    for (int64_t i = 0; i < n_res; i++) {
+        const uint64_t o = (uint64_t)h->rr_rord[i];
+        if ((o >> 32) != seq) continue;
+        h->rr_from_push[i] = 1;
+        if ((int64_t)(o & 0xffffffffull) >= n_rows)
+            return fail(FW_E_INVALID, "fw_count_record_rows: a result names row %lld of the push, n_rows is %lld",
+                        (long long)(o & 0xffffffffull), (long long)n_rows);
+    }
+    h->rr_ev_words.resize((size_t)n_ev * F);
+    h->rr_res_words.resize((size_t)n_res * F);
+    if (n_ev) HIP_TRY(hipMemcpy(h->rr_ev_words.data(), w.g_ev, (size_t)n_ev * F * 8, hipMemcpyDeviceToHost));
+    if (n_res) HIP_TRY(hipMemcpy(h->rr_res_words.data(), w.g_res, (size_t)n_res * F * 8, hipMemcpyDeviceToHost));
+    const int64_t zero = 0;
+    HIP_TRY(hipMemcpy(&h->ctrl->n_ordev, &zero, 8, hipMemcpyHostToDevice));
+    for (int64_t i = 0; i < n_ev; i++) {
+        h->rr_ord[i] &= ~ORDEV_RELEASE;
+        if (!h->rr_is_retain[i]) memset(h->rr_ev_words.data() + (size_t)i * F, 0, (size_t)F * 8);
+    }
+    for (int64_t i = 0; i < n_res; i++)
+        if (!h->rr_from_push[i]) memset(h->rr_res_words.data() + (size_t)i * F, 0, (size_t)F * 8);
+    out->n_fields = F;
+    out->n_ev = n_ev;
+    out->ev_ord = h->rr_ord.data();
+    out->ev_is_retain = h->rr_is_retain.data();
+    out->ev_words = h->rr_ev_words.data();
+    out->n_res = n_res;
+    out->res_words = h->rr_res_words.data();
+    out->res_from_push = h->rr_from_push.data();
+    return FW_OK;
+}
+
 int fw_advance(fw_handle* h, int64_t watermark) {
     if (!h) return fail(FW_E_INVALID, "null handle");
     if (h->cw.on) {  // CountTrigger.onEventTime: CONTINUE -- the watermark is recorded, nothing fires

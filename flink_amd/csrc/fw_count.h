@@ -125,6 +125,8 @@ struct CountOp {
     uint64_t* out_rord = nullptr;  // rec: the ordinal of the record each result row is built from
     int64_t* ordev = nullptr;      // rec: retain / release events (ORDEV_RELEASE | ordinal) since the last read
     int64_t ordev_cap = 0;         // 2 * max_batch_rows: a row appends at most a release and a retain
+    uint64_t* g_ev = nullptr;      // rec, behind the exchange: the gathered record words, [ordev_cap][F] beside ordev and
+    uint64_t* g_res = nullptr;     // [out_cap][F] beside the result rows (allocated by the first cw_record_rows)
     int64_t push_seq = 0;
     int64_t watermark = INT64_MIN;
 };
@@ -142,6 +144,13 @@ int cw_push(CountOp* op, int64_t n, const int64_t* d_key, const int32_t* d_khash
 // fired row's ordinal is push_seq << 32 | the triggering element's position in the buffer.
 int cw_push_segments(CountOp* op, int32_t n_segs, int64_t seg_len, const int64_t* d_seg_counts, const int64_t* d_key,
                      const int32_t* d_khash, const uint64_t* d_val, int32_t stride);
+// A record handle's push behind the exchange: packed rows (key, unread word, the record's F fields), the
+// aggregated one at word 2 + val_col; one launch (k_cw_fold<true, true>), at most max_batch_rows rows.
+int cw_push_record_segments(CountOp* op, int32_t n_segs, int64_t seg_len, const int64_t* d_seg_counts, const int64_t* d_rows,
+                            int32_t row_words);
+// launches k_cw_gather_rec over the last push's buffer: g_ev / g_res take the F payload words of the rows
+// its retain events and the unread result rows name (stream-ordered; the caller reads Ctrl behind it)
+int cw_record_rows(CountOp* op, const int64_t* d_rows, int32_t row_words, int64_t n_rows, int32_t F);
 int cw_snapshot(CountOp* op, int32_t key_group, void* buf, int64_t capacity, int64_t* size);
 int cw_restore(CountOp* op, bool key_group, const void* buf, int64_t size);
 

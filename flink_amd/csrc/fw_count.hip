@@ -9,7 +9,9 @@
 // the arrival order.
 // A record handle (FW_WIN_COUNT_RECORD) launches k_cw_fold<false, true>: the same body with an ordinal
 // beside every value word -- in the scan, the fire loop and the write-back -- and the retain / release
-// events of the ordinals the ring holds.
+// events of the ordinals the ring holds.  Behind the exchange (cw_push_record_segments) it is
+// k_cw_fold<true, true>, and k_cw_gather_rec copies the record rows the events and results name out of
+// the receive buffer (cw_record_rows), so the buffer itself never crosses to the host.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -337,6 +339,43 @@ __global__ __launch_bounds__(CW_TILE) void k_cw_fold(CwArgs<REC> a) {
     }
 }
 
+// The payload words (words 2 .. 2 + F of a packed row) of the rows a record push's events and results
+// name, gathered beside the event list and the result list: event i's words at ev_words[i * F ..],
+// result j's at res_words[j * F ..].  A release event and an ordinal of another push (or one whose
+// position is not below n_rows: the host refuses the call) get no words.  The counts are read from
+// Ctrl here, so the host launches without knowing them; the loop is bounded by the two capacities.
+struct CwGatherArgs {
+    const Ctrl* ctrl;
+    const int64_t* ordev;
+    int64_t ordev_cap;
+    const uint64_t* out_rord;
+    int64_t out_cap;
+    const uint64_t* rows;
+    int32_t row_words, F;
+    int64_t n_rows;
+    uint64_t seq;  // push_seq of the push the buffer belongs to
+    uint64_t* ev_words;
+    uint64_t* res_words;
+};
+constexpr int CW_GATHER_THREADS = 256;
+__global__ __launch_bounds__(CW_GATHER_THREADS) void k_cw_gather_rec(CwGatherArgs a) {
+    const unsigned long long n_ordev = a.ctrl->n_ordev, n_out = a.ctrl->out_count[0];
+    const int64_t n_ev = (int64_t)(n_ordev < (unsigned long long)a.ordev_cap ? n_ordev : (unsigned long long)a.ordev_cap);
+    const int64_t n_res = (int64_t)(n_out < (unsigned long long)a.out_cap ? n_out : (unsigned long long)a.out_cap);
+    const int64_t total = a.ordev_cap + a.out_cap;
+    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (int64_t)gridDim.x * blockDim.x) {
+        const bool is_ev = i < a.ordev_cap;
+        const int64_t j = is_ev ? i : i - a.ordev_cap;
+        if (j >= (is_ev ? n_ev : n_res)) continue;
+        const uint64_t o = is_ev ? (uint64_t)a.ordev[j] : a.out_rord[j];  // (a release has its top bit set: no push_seq matches)
+        const uint64_t pos = o & 0xffffffffull;
+        if ((o >> 32) != a.seq || pos >= (uint64_t)a.n_rows) continue;
+        const uint64_t* src = a.rows + (size_t)pos * (size_t)a.row_words + 2;
+        uint64_t* dst = (is_ev ? a.ev_words : a.res_words) + (size_t)j * (size_t)a.F;
+        for (int f = 0; f < a.F; f++) dst[f] = src[f];
+    }
+}
+
 int64_t cw_gcd(int64_t a, int64_t b) {
     while (b) {
         const int64_t t = a % b;
@@ -468,16 +507,19 @@ void cw_free(CountOp* op) {
     hipFree(op->out_null);
     hipFree(op->out_rord);
     hipFree(op->ordev);
+    hipFree(op->g_ev);
+    hipFree(op->g_res);
 }
 
 // the folds of one call: n rows at d_key[i * stride], d_val[i * stride], split into launches of
 // part.cap_rows rows by position.  d_seg_counts: the rows are a padded buffer of segments of seg_len
 // rows and the fold is the device form; else a direct push (stride 1)
+// (rec_segments: a record handle's padded buffer, cw_push_record_segments -- one launch)
 static int cw_fold_call(CountOp* op, int64_t n, const int64_t* d_key, const int32_t* d_khash, const uint64_t* d_val, int32_t stride,
-                        const int64_t* d_seg_counts, int64_t seg_len) {
+                        const int64_t* d_seg_counts, int64_t seg_len, bool rec_segments = false) {
     if (n >= (1ll << 32) || op->push_seq >= (1ll << 30))
         return set_error(FW_E_INVALID, "arrival ordinals need < 2^32 rows per call and < 2^30 calls");
-    if (op->rec && (d_seg_counts || n > op->part.cap_rows))  // the event buffers hold one push of max_batch_rows rows
+    if (op->rec && !rec_segments && (d_seg_counts || n > op->part.cap_rows))  // the event buffers hold one push of max_batch_rows rows
         return set_error(FW_E_INVALID, "record count windows: a push takes at most max_batch_rows (%lld) rows, as columns", (long long)op->part.cap_rows);
     hipStream_t s = op->stream;
     const int64_t cap_rows = op->part.cap_rows;
@@ -511,7 +553,8 @@ static int cw_fold_call(CountOp* op, int64_t n, const int64_t* d_key, const int3
         fa.out_rord = op->out_rord;
         fa.ordev = op->ordev;
         fa.ordev_cap = op->ordev_cap;
-        if (op->rec) hipLaunchKernelGGL((k_cw_fold<false, true>), dim3(op->ks.n_sb), dim3(CW_TILE), 0, s, fa);
+        if (op->rec && d_seg_counts) hipLaunchKernelGGL((k_cw_fold<true, true>), dim3(op->ks.n_sb), dim3(CW_TILE), 0, s, fa);
+        else if (op->rec) hipLaunchKernelGGL((k_cw_fold<false, true>), dim3(op->ks.n_sb), dim3(CW_TILE), 0, s, fa);
         else if (d_seg_counts) hipLaunchKernelGGL((k_cw_fold<true, false>), dim3(op->ks.n_sb), dim3(CW_TILE), 0, s, (const CwFoldArgs&)fa);
         else hipLaunchKernelGGL((k_cw_fold<false, false>), dim3(op->ks.n_sb), dim3(CW_TILE), 0, s, (const CwFoldArgs&)fa);
         FD_TRY(hipGetLastError());
@@ -527,6 +570,43 @@ int cw_push(CountOp* op, int64_t n, const int64_t* d_key, const int32_t* d_khash
 int cw_push_segments(CountOp* op, int32_t n_segs, int64_t seg_len, const int64_t* d_seg_counts, const int64_t* d_key,
                      const int32_t* d_khash, const uint64_t* d_val, int32_t stride) {
     return cw_fold_call(op, (int64_t)n_segs * seg_len, d_key, d_khash, d_val, stride, d_seg_counts, seg_len);
+}
+
+int cw_push_record_segments(CountOp* op, int32_t n_segs, int64_t seg_len, const int64_t* d_seg_counts, const int64_t* d_rows,
+                            int32_t row_words) {
+    const int64_t n = (int64_t)n_segs * seg_len;
+    // one call is one launch: the event buffer holds what one push of max_batch_rows rows can raise,
+    // and a retain must name a row of the current call
+    if (n > op->part.cap_rows)
+        return set_error(FW_E_INVALID, "fw_push_device_count_record_packed_segments: n_segs * seg_len = %lld exceeds max_batch_rows (%lld)",
+                         (long long)n, (long long)op->part.cap_rows);
+    return cw_fold_call(op, n, d_rows, nullptr, (const uint64_t*)d_rows + 2 + op->val_col, row_words, d_seg_counts, seg_len, true);
+}
+
+int cw_record_rows(CountOp* op, const int64_t* d_rows, int32_t row_words, int64_t n_rows, int32_t F) {
+    int rc;
+    if (!op->g_ev) {  // the first call of a handle behind an exchange; a handle pushed directly never pays
+        if ((rc = fd_dalloc(&op->g_ev, (size_t)op->ordev_cap * F))) return rc;
+        if ((rc = fd_dalloc(&op->g_res, (size_t)op->out_cap * F))) return rc;
+    }
+    CwGatherArgs ga{};
+    ga.ctrl = op->ctrl;
+    ga.ordev = op->ordev;
+    ga.ordev_cap = op->ordev_cap;
+    ga.out_rord = op->out_rord;
+    ga.out_cap = op->out_cap;
+    ga.rows = (const uint64_t*)d_rows;
+    ga.row_words = row_words;
+    ga.F = F;
+    ga.n_rows = n_rows;
+    ga.seq = (uint64_t)(op->push_seq - 1);
+    ga.ev_words = op->g_ev;
+    ga.res_words = op->g_res;
+    const int64_t total = op->ordev_cap + op->out_cap;
+    const int64_t blocks = std::min<int64_t>((total + CW_GATHER_THREADS - 1) / CW_GATHER_THREADS, 1024);
+    hipLaunchKernelGGL(k_cw_gather_rec, dim3((unsigned)blocks), dim3(CW_GATHER_THREADS), 0, op->stream, ga);
+    FD_TRY(hipGetLastError());
+    return FW_OK;
 }
 
 // ---- checkpoint: the library's own blob.  Entries are (key, count, key group << 32 | sub-bucket,

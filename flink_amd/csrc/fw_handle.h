@@ -55,6 +55,8 @@ struct fw_handle {
     int64_t* ordev = nullptr;    // DataStream first-element retain / release events
     int64_t ordev_cap = 0;
     std::vector<int64_t> ev_retain, ev_release;  // fw_first_element_events copies
+    std::vector<int64_t> rr_ord, rr_rord, rr_ev_words, rr_res_words;  // fw_count_record_rows copies (rr_rord: the result rows' values[1])
+    std::vector<uint8_t> rr_is_retain, rr_from_push;
     int32_t push_seq = 0;        // fw_commit / fw_push_device calls (side-output row ids)
     std::vector<int64_t> tz_utc, tz_off, tz_bound;  // shift-zone table (host copy)
     int64_t* d_tz = nullptr;     // device copy: [utc | off | bound]
@@ -220,8 +222,9 @@ int kr_intern(fw_handle* h, int64_t n, const int64_t* d_off, const uint8_t* d_by
 // fw_push_device_packed_segments; fw_advance_device likewise): a session handle has them iff its
 // configuration has parallelism > 1 -- only such a handle has an exchange in front of it.  One of
 // parallelism 1 refuses them as ever, and so does every count handle.
-// A record count handle (FW_WIN_COUNT_RECORD) has no key-group checkpoint and no exchange path yet: a
-// restored key group's records would have to be re-numbered under fresh ordinals.
+// A record count handle (FW_WIN_COUNT_RECORD) has no key-group checkpoint -- a restored key group's
+// records would have to be re-numbered under fresh ordinals -- and an exchange entry of its own
+// (fw_push_device_count_record_packed_segments): the count handle's two segment pushes stay refused.
 #define CW_REFUSE_RECORD(h, name)                                                                                       \
     if ((h)->cw.on && (h)->cw.rec)                                                                                      \
         return fw::set_error(FW_E_INVALID, name ": not for record count windows (FW_WIN_COUNT_RECORD: retained records are not re-numbered)")

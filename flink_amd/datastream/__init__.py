@@ -18,3 +18,4 @@ from .late_dynamic_session_window_operator import LateDynamicSessionWindowOperat
 from .late_dynamic_session_window_operator import is_gpu_eligible as is_late_dynamic_session_window_gpu_eligible  # noqa: F401
 from .session_exchange import SessionExchangeStep  # noqa: F401
 from .count_exchange import CountExchangeStep  # noqa: F401
+from .record_count_exchange import RecordCountExchangeStep  # noqa: F401

@@ -260,6 +260,34 @@ class WindowAggHandle:
         self.push_seq += 1
         self._end_read(cur)
 
+    def push_device_count_record_packed_segments(self, seg_counts, rows, row_words):
+        """A record count-window handle (FW_WIN_COUNT_RECORD) of parallelism > 1: the packed padded
+        exchange receive buffer, rows of (key, unread word, the record's F fields).  One launch: at
+        most max_batch_rows rows.  count_record_rows() follows, before ``rows`` is reused."""
+        p = seg_counts.numel()
+        if p == 0 or rows.numel() == 0:
+            return
+        cur = self._begin_read(rows.device)
+        check(lib().fw_push_device_count_record_packed_segments(self._h, p, rows.numel() // (p * row_words),
+                                                                seg_counts.data_ptr(), rows.data_ptr(), int(row_words)))
+        self.push_seq += 1
+        self._end_read(cur)
+
+    def count_record_rows(self, rows, row_words, n_rows=None):
+        """fw_count_record_rows over the buffer of the last push_device_count_record_packed_segments:
+        the retain / release events (consumed) and, beside them and beside the rows results() returns
+        next, the record fields gathered on the device.  Returns a dict: ev_ord, ev_is_retain,
+        ev_words [n_ev, F], res_words [n_res, F], res_from_push.  Waits for the device once."""
+        r = abi.fw_record_rows()
+        n = rows.numel() // row_words if n_rows is None else int(n_rows)
+        check(lib().fw_count_record_rows(self._h, rows.data_ptr(), int(row_words), n, C.byref(r)))
+        f = int(r.n_fields)
+        return {"ev_ord": _np_view(r.ev_ord, r.n_ev, np.int64).copy(),
+                "ev_is_retain": _np_view(r.ev_is_retain, r.n_ev, np.uint8).astype(bool),
+                "ev_words": _np_view(r.ev_words, r.n_ev * f, np.int64).copy().reshape(r.n_ev, f),
+                "res_words": _np_view(r.res_words, r.n_res * f, np.int64).copy().reshape(r.n_res, f),
+                "res_from_push": _np_view(r.res_from_push, r.n_res, np.uint8).astype(bool)}
+
     # ---- progress / output
     def advance(self, wm):
         check(lib().fw_advance(self._h, int(wm)))

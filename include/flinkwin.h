@@ -236,8 +236,11 @@ typedef enum {
        the tie flag: it restores neither into a FW_WIN_COUNT handle nor under another tie rule.  The
        shim checkpoints its retained records beside it.  Refused with FW_E_INVALID: everything a
        FW_WIN_COUNT handle refuses except fw_first_element_events, the two count segment pushes
-       (there is no exchange path yet) and fw_snapshot_key_group / fw_restore_key_group (a restored
-       key group's records would need fresh ordinals). */
+       (the kind's exchange entry is fw_push_device_count_record_packed_segments, below: packed rows
+       only) and fw_snapshot_key_group / fw_restore_key_group (a restored key group's records would
+       need fresh ordinals).  Not behind the exchange: a SoA segment entry (one value column cannot
+       carry the record's other fields), FW_KEYHASH_PRECOMPUTED keys (STRING keys among them) and
+       record fields that are not 8-byte LONG / INT / DOUBLE words. */
     FW_WIN_COUNT_RECORD = 8
 } fw_window_kind;
 
@@ -529,6 +532,50 @@ int fw_push_device_count_segments(fw_handle* h, int32_t n_segs, int64_t seg_len,
                                   const int64_t* d_key, const int32_t* d_key_hash, const void* d_value);
 int fw_push_device_count_packed_segments(fw_handle* h, int32_t n_segs, int64_t seg_len, const int64_t* d_seg_counts,
                                          const int64_t* d_rows, int32_t row_words);
+
+/* v11 (additive: new symbols), record count windows (FW_WIN_COUNT_RECORD) behind the N > 1 keyBy
+   exchange.  For a record handle of parallelism > 1 only: every other handle, and a record handle of
+   parallelism 1, return FW_E_INVALID with a message naming the call.
+   The record is the tuple of the handle's value columns: F = n_value_cols fields (1 <= F <=
+   FW_MAX_COLS), each an 8-byte LONG / INT / DOUBLE word; the aggregated field is column
+   aggs[0].input_col.  A packed row is (key, unread word, field 0 .. field F - 1): row_words must be
+   2 + F, word 1 is never read, the aggregate reads word 2 + input_col.  Not for
+   FW_KEYHASH_PRECOMPUTED (packed rows carry no hash).
+   fw_push_device_count_record_packed_segments: the buffer, arrival order, padding, foreign rows,
+   push_seq and FW_ERRF_STATE / FW_ERRF_OUTPUT / FW_ERRF_ORDEV as on
+   fw_push_device_count_packed_segments and a direct record push; first_ord and values[1] are
+   push_seq << 32 | buffer position (segment * seg_len + index).  One call is one launch:
+   n_segs * seg_len > max_batch_rows is FW_E_INVALID (the event buffer holds what one push of
+   max_batch_rows rows can raise, and a retain names a row of the current call).
+   fw_count_record_rows: the record rows the shim needs, gathered on the device from the buffer of the
+   LAST push (d_rows, row_words as pushed, n_rows = n_segs * seg_len) -- the buffer itself never crosses
+   to the host.  Call it after every push, before the buffer is reused, and BEFORE fw_results /
+   fw_results_reset: it reads the result rows since the last fw_results_reset, and res_words[j * F ..]
+   belong to row j of the fw_results call that follows (no push in between).  It returns
+     ev_ord[n_ev], ev_is_retain[n_ev]   the retain / release events since the last read, in the device's
+                                        order, as ordinals; consumed, as by fw_first_element_events
+     ev_words[n_ev * F]                 a retain's record fields (a release: zeros)
+     res_from_push[n_res]               1 iff result row j's values[1] names a row of this push
+     res_words[n_res * F]               that row's record fields (else zeros: the record is one the
+                                        shim retained earlier)
+   The shim's order is unchanged: results, retains, resolve values[1], releases.  One host wait.  A
+   retain or a result naming a position >= n_rows of this push is FW_E_INVALID and nothing is read out
+   of bounds or consumed; a retain of an earlier push (events left unread) is FW_E_INVALID too.  Host
+   arrays owned by the handle, valid until the next call.  The device keeps F words per event and per
+   result row for this (2 * max_batch_rows + output_capacity rows), allocated by the first call. */
+typedef struct {
+    int64_t n_fields; /* F */
+    int64_t n_ev;
+    int64_t* ev_ord;
+    uint8_t* ev_is_retain;
+    int64_t* ev_words;
+    int64_t n_res;
+    int64_t* res_words;
+    uint8_t* res_from_push;
+} fw_record_rows;
+int fw_push_device_count_record_packed_segments(fw_handle* h, int32_t n_segs, int64_t seg_len, const int64_t* d_seg_counts,
+                                                const int64_t* d_rows, int32_t row_words);
+int fw_count_record_rows(fw_handle* h, const int64_t* d_rows, int32_t row_words, int64_t n_rows, fw_record_rows* out);
 
 /* ---- progress / output --------------------------------------------------------------- */
 /* Late side output of a DataStream operator with late_side_output (WindowOperator.sideOutput,
