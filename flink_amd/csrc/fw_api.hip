@@ -5,7 +5,8 @@
 // HBM slice-state table that replaces HeapKeyedStateBackend for this operator
 // (FR/runtime/state/heap/HeapKeyedStateBackend.java:85) together with its timers
 // (InternalTimerServiceImpl), and the result buffer.  Calls are asynchronous on the handle's
-// stream except where a host value is needed (results, stats, snapshot).
+// stream except where a host value is needed (results, stats, snapshot).  This file plans, allocates,
+// pushes, advances and reports; fw_results.hip delivers the rows, fw_checkpoint.hip the state.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -587,43 +588,6 @@ int validate_and_plan(fw_handle* h) {
     return FW_OK;
 }
 
-// queues the DMA of async result buffer b's n rows into its pinned host buffers on the D2H stream
-int ar_enqueue_copy(fw_handle* h, int b, int64_t n) {
-    hipStream_t ds = h->d2h_stream;
-    HIP_TRY(hipMemcpyAsync(h->ar_key[b], h->ard_key[b], (size_t)n * 8, hipMemcpyDeviceToHost, ds));
-    HIP_TRY(hipMemcpyAsync(h->ar_ws[b], h->ard_ws[b], (size_t)n * 8, hipMemcpyDeviceToHost, ds));
-    HIP_TRY(hipMemcpyAsync(h->ar_we[b], h->ard_we[b], (size_t)n * 8, hipMemcpyDeviceToHost, ds));
-    HIP_TRY(hipMemcpyAsync(h->ar_null[b], h->ard_null[b], (size_t)n * 4, hipMemcpyDeviceToHost, ds));
-    for (int g = 0; g < h->n_out; g++)
-        HIP_TRY(hipMemcpyAsync(h->ar_val[b][g], h->ard_val[b][g], (size_t)n * 8, hipMemcpyDeviceToHost, ds));
-    HIP_TRY(hipEventRecord(h->ar_dma_ev[b], ds));
-    return FW_OK;
-}
-
-// Starts the DMA of the last fw_results_async's rows as soon as its compaction has finished, from
-// the calls a pipelined caller makes between fw_results_async and fw_results_ready (the next batch's
-// fw_commit / push, fw_advance): the copy then runs beside that batch's kernels and
-// fw_results_ready finds it done.  Never blocks; any failure is left for fw_results_ready.
-void ar_kick(fw_handle* h) {
-    if (h->ar_kernel || !h->d2h_stream) return;
-    for (int i = 0; i < h->ar_qn; i++) {  // outstanding collections, oldest first
-        const int b = h->ar_q[(h->ar_qhead + i) % FW_AR_BUFS];
-        if (h->ar_empty[b] || h->ar_copied[b] || h->ar_inflight[b]) continue;
-        if (hipEventQuery(h->ar_ev[b]) != hipSuccess) {  // compaction still queued: try at the next call
-            (void)hipGetLastError();
-            return;
-        }
-        const int64_t n = __atomic_load_n(h->ar_n[b], __ATOMIC_ACQUIRE);
-        if (n <= 0 || n > h->out_cap) continue;
-        if (ar_enqueue_copy(h, b, n) != FW_OK) {
-            (void)hipGetLastError();
-            return;
-        }
-        h->ar_inflight[b] = true;
-    }
-}
-
-
 // the hash kinds whose 256 x 16 instance keeps its rows in registers (the other two spill 4 VGPRs to
 // scratch: tools/regs.sh), which the automatic geometry choice may take
 static bool igp_auto_kind(int hash_kind) { return hash_kind == KH_BINROW_BIGINT || hash_kind == KH_BINROW_INT; }
@@ -717,17 +681,8 @@ int allocate(fw_handle* h) {
     if ((rc = fd_dalloc(&h->sb_min_timer, h->ks.n_sb))) return rc;
     if ((rc = fd_dalloc(&h->sb_nar, h->ks.n_sb))) return rc;
     const size_t orows = (size_t)h->ks.n_sb * h->slab_cap + h->out_cap;
-    if ((rc = fd_dalloc(&h->out_key, orows))) return rc;
-    if ((rc = fd_dalloc(&h->out_we, orows))) return rc;
-    if ((rc = fd_dalloc(&h->out_null, orows))) return rc;
-    for (int g = 0; g < h->n_out; g++)
-        if ((rc = fd_dalloc(&h->out_val[g], orows))) return rc;
-    if ((rc = fd_dalloc(&h->res_key, h->out_cap))) return rc;
-    if ((rc = fd_dalloc(&h->res_ws, h->out_cap))) return rc;
-    if ((rc = fd_dalloc(&h->res_we, h->out_cap))) return rc;
-    if ((rc = fd_dalloc(&h->res_null, h->out_cap))) return rc;
-    for (int g = 0; g < h->n_out; g++)
-        if ((rc = fd_dalloc(&h->res_val[g], h->out_cap))) return rc;
+    if ((rc = cols_alloc_device(&h->out, orows, h->n_out, false))) return rc;  // (window_start is derived at the compaction)
+    if ((rc = cols_alloc_device(&h->res, (size_t)h->out_cap, h->n_out, true))) return rc;
     if ((rc = fd_dalloc(&h->sb_out, h->ks.n_sb + 1))) return rc;  // + the overflow region's rows
     if ((rc = fd_dalloc(&h->sb_fired, h->ks.n_sb))) return rc;
     if ((rc = fd_dalloc(&h->coff, h->ks.n_sb + 2))) return rc;
@@ -793,51 +748,6 @@ int alloc_staging(fw_handle* h) {
     return FW_OK;
 }
 
-// pinned, device-mapped result buffers of fw_results_async
-int alloc_async_results(fw_handle* h) {
-    if (h->ar_n[0]) return FW_OK;
-    const size_t n = (size_t)h->out_cap;
-    int rc;
-    HIP_TRY(hipStreamCreateWithFlags(&h->d2h_stream, hipStreamNonBlocking));
-    for (int b = 0; b < FW_AR_BUFS; b++) {
-        // pinned host buffers: mapped for the kernel delivery, plain for the DMA
-        const unsigned fl = h->ar_kernel ? hipHostMallocMapped : hipHostMallocDefault;
-        HIP_TRY(hipHostMalloc((void**)&h->ar_key[b], n * 8, fl));
-        HIP_TRY(hipHostMalloc((void**)&h->ar_ws[b], n * 8, fl));
-        HIP_TRY(hipHostMalloc((void**)&h->ar_we[b], n * 8, fl));
-        HIP_TRY(hipHostMalloc((void**)&h->ar_null[b], n * 4, fl));
-        for (int g = 0; g < h->n_out; g++) HIP_TRY(hipHostMalloc((void**)&h->ar_val[b][g], n * 8, fl));
-        HIP_TRY(hipHostMalloc((void**)&h->ar_n[b], 8, hipHostMallocMapped | hipHostMallocCoherent));
-        HIP_TRY(hipEventCreateWithFlags(&h->ar_ev[b], hipEventDisableTiming));
-        HIP_TRY(hipEventCreateWithFlags(&h->ar_dma_ev[b], hipEventDisableTiming));
-        if ((rc = fd_dalloc(&h->ard_key[b], n))) return rc;
-        if ((rc = fd_dalloc(&h->ard_ws[b], n))) return rc;
-        if ((rc = fd_dalloc(&h->ard_we[b], n))) return rc;
-        if ((rc = fd_dalloc(&h->ard_null[b], n))) return rc;
-        for (int g = 0; g < h->n_out; g++)
-            if ((rc = fd_dalloc(&h->ard_val[b][g], n))) return rc;
-    }
-    return FW_OK;
-}
-
-template <typename T>
-T* mapped(T* host) {
-    void* d = nullptr;
-    return hipHostGetDevicePointer(&d, (void*)host, 0) == hipSuccess ? (T*)d : nullptr;
-}
-
-// the window description the kernels get: the shift-zone table pointers are the device copy's
-WinDesc device_win(const fw_handle* h) {
-    WinDesc w = h->win;
-    if (h->d_tz) {
-        const size_t n = h->tz_utc.size();
-        w.tz.utc = h->d_tz;
-        w.tz.off = h->d_tz + n;
-        w.tz.bound = h->d_tz + 2 * n;
-    }
-    return w;
-}
-
 MergeArgs merge_args(fw_handle* h, int64_t wm, int force) {
     MergeArgs a{};
     a.ks = h->ks;
@@ -865,10 +775,10 @@ MergeArgs merge_args(fw_handle* h, int64_t wm, int force) {
     a.always_flush = h->always_flush;
     a.local = h->cfg.agg_phase == FW_PHASE_LOCAL;
     a.chunk_rows = (int32_t)h->chunk_rows;
-    a.out_key = h->out_key;
-    a.out_we = h->out_we;
-    for (int g = 0; g < FW_MAX_AGGS; g++) a.out_val[g] = h->out_val[g] ? h->out_val[g] : h->out_val[0];
-    a.out_null = h->out_null;
+    a.out_key = h->out.key;
+    a.out_we = h->out.we;
+    for (int g = 0; g < FW_MAX_AGGS; g++) a.out_val[g] = h->out.val[g] ? h->out.val[g] : h->out.val[0];
+    a.out_null = h->out.null;
     a.out_cap = h->out_cap;
     a.slab_cap = h->slab_cap;
     a.sb_out = h->sb_out;
@@ -899,13 +809,18 @@ MergeArgs merge_args(fw_handle* h, int64_t wm, int force) {
     return a;
 }
 
-int launch_merge(fw_handle* h, int64_t wm, int force) {
-    HIP_TRY(launch_merge_fire(merge_args(h, wm, force), h->stream, h->timer));
+// One merge launch and its bookkeeping.  wm_dev: the watermark is read on the device (fw_advance_device, wm
+// is INT64_MIN); the host mirrors of currentProgress then stay behind the device -- they only ever skip
+// launches, so a stale, lower value skips fewer.
+int launch_merge(fw_handle* h, int64_t wm, int force, const int64_t* wm_dev = nullptr) {
+    MergeArgs a = merge_args(h, wm, force);
+    a.wm_dev = wm_dev;
+    HIP_TRY(launch_merge_fire(a, h->stream, h->timer));
     h->pushes_at_merge[h->merge_seq % 64] = h->pushes_total;
     h->merge_seq++;
     h->ig_merges++;
     h->reset_pending = false;  // the launch started every output slab (and the overflow) afresh
-    if (!force && wm > h->dev_cur) {  // merge_finalize's advanceProgress bookkeeping, mirrored
+    if (!wm_dev && !force && wm > h->dev_cur) {  // merge_finalize's advanceProgress bookkeeping, mirrored
         h->dev_cur = wm;
         if (wm >= h->dev_ntp) h->dev_ntp = tz_next_trigger_watermark(h->win.tz, wm, h->win.slice_div);
     }
@@ -1031,6 +946,14 @@ int push(fw_handle* h, int64_t n, const int64_t* key, const int64_t* ts, const i
     return FW_OK;
 }
 
+// key rows no state / partial / timer request / unread result holds any more are collected behind a merge
+int kr_collect(fw_handle* h) {
+    HIP_TRY(launch_kr_collect(h->kr, h->ctrl, h->state, h->state_count, h->sb_nar, h->nw_t, h->ks.n_sb, h->cap_e, h->pwe,
+                              2 + h->nw_t, h->parts, h->cap_rows, h->treq, h->out.key, h->sb_out, h->slab_cap,
+                              h->treq_cap, h->out_cap, h->stream));
+    return FW_OK;
+}
+
 int push_key_rows(fw_handle* h, int64_t n, const int64_t* d_off, const uint8_t* d_bytes, const int64_t* ts,
                   const void* const* vals, const uint8_t* const* nulls) {
     int rc = kr_intern(h, n, d_off, d_bytes);
@@ -1055,6 +978,24 @@ int fw::read_ctrl(fw_handle* h, Ctrl* out) {
                     out->error & ERR_GAP ? " session-gap (a row's gap outside (0, size_ms])" : "");
     }
     return FW_OK;
+}
+
+WinDesc fw::device_win(const fw_handle* h) {
+    WinDesc w = h->win;
+    if (h->d_tz) {
+        const size_t n = h->tz_utc.size();
+        w.tz.utc = h->d_tz;
+        w.tz.off = h->d_tz + n;
+        w.tz.bound = h->d_tz + 2 * n;
+    }
+    return w;
+}
+
+int fw::check_row_words(const fw_handle* h, int32_t row_words, const char* name) {
+    const int32_t F = h->cfg.n_value_cols;
+    if (row_words == 2 + F) return FW_OK;
+    if (!name) return fail(FW_E_INVALID, "row_words %d != 2 + value columns", row_words);
+    return fail(FW_E_INVALID, "%s: row_words %d != 2 + value columns (%d record fields)", name, row_words, F);
 }
 
 int fw::force_flush(fw_handle* h) {
@@ -1175,15 +1116,8 @@ int fw_destroy(fw_handle* h) {
     hipFree(h->state_count);
     hipFree(h->sb_min_timer);
     hipFree(h->sb_nar);
-    hipFree(h->out_key);
-    hipFree(h->out_we);
-    hipFree(h->out_null);
-    for (int g = 0; g < FW_MAX_AGGS; g++) hipFree(h->out_val[g]);
-    for (int g = 0; g < FW_MAX_AGGS; g++) hipFree(h->res_val[g]);
-    hipFree(h->res_key);
-    hipFree(h->res_ws);
-    hipFree(h->res_we);
-    hipFree(h->res_null);
+    cols_free(&h->out, false);
+    cols_free(&h->res, false);
     hipFree(h->sb_out);
     hipFree(h->sb_fired);
     hipFree(h->coff);
@@ -1214,19 +1148,11 @@ int fw_destroy(fw_handle* h) {
     }
     if (h->d2h_stream) hipStreamSynchronize(h->d2h_stream);  // an early DMA (ar_kick) may still be reading the buffers
     for (int b = 0; b < FW_AR_BUFS; b++) {
-        hipHostFree(h->ar_key[b]);
-        hipHostFree(h->ar_ws[b]);
-        hipHostFree(h->ar_we[b]);
-        hipHostFree(h->ar_null[b]);
-        for (int g = 0; g < FW_MAX_AGGS; g++) hipHostFree(h->ar_val[b][g]);
+        cols_free(&h->ar[b], true);
         hipHostFree(h->ar_n[b]);
         if (h->ar_ev[b]) hipEventDestroy(h->ar_ev[b]);
         if (h->ar_dma_ev[b]) hipEventDestroy(h->ar_dma_ev[b]);
-        hipFree(h->ard_key[b]);
-        hipFree(h->ard_ws[b]);
-        hipFree(h->ard_we[b]);
-        hipFree(h->ard_null[b]);
-        for (int g = 0; g < FW_MAX_AGGS; g++) hipFree(h->ard_val[b][g]);
+        cols_free(&h->ard[b], false);
     }
     if (h->d2h_stream) hipStreamDestroy(h->d2h_stream);
     if (h->cstream) hipStreamDestroy(h->cstream);
@@ -1380,6 +1306,36 @@ static int commit_impl(fw_handle* h, int64_t n, uint32_t packed, const int64_t* 
     return rc;
 }
 
+// ---- the push entry points' argument checks: each returns FW_OK or the refusal
+static int check_segments(int32_t n_segs, int64_t seg_len, const int64_t* d_seg_counts) {
+    if (n_segs < 0 || seg_len < 1 || (n_segs > 0 && !d_seg_counts)) return fail(FW_E_INVALID, "bad segments");
+    return FW_OK;
+}
+static int check_key_hash(const fw_handle* h, const int32_t* d_key_hash) {
+    if (h->cfg.key_hash == FW_KEYHASH_PRECOMPUTED && !d_key_hash) return fail(FW_E_INVALID, "key_hash column required");
+    return FW_OK;
+}
+static int fail_value_null(int v) { return fail(FW_E_INVALID, "value column %d is NULL", v); }
+// every value column the plan loads, and the null-flag column of each NULL-able one
+static int check_value_cols(const fw_handle* h, const void* const* d_values, const uint8_t* const* d_nulls) {
+    if (h->nv > 0 && !d_values) return fail(FW_E_INVALID, "value columns required");
+    for (int s = 0; s < h->nv; s++) {
+        const int v = h->slot_col[s];
+        if (!d_values[v]) return fail_value_null(v);
+        if (((h->cfg.nullable_cols >> v) & 1u) && (!d_nulls || !d_nulls[v]))
+            return fail(FW_E_INVALID, "nullable value column %d needs its null-flag column", v);
+    }
+    return FW_OK;
+}
+// a count handle numbers the rows of a segment push by buffer position
+static int check_ordinals(int32_t n_segs, int64_t seg_len) {
+    if (seg_len >= (1ll << 32) || (int64_t)n_segs * seg_len >= (1ll << 32))
+        return fail(FW_E_INVALID, "arrival ordinals need n_segs * seg_len < 2^32 rows per call");
+    return FW_OK;
+}
+#define CHECK(call) \
+    if (int rc_ = (call)) return rc_
+
 int fw_push_device_key_rows(fw_handle* h, int64_t n, const int64_t* d_key_row_offsets, const uint8_t* d_key_row_bytes,
                             const int64_t* d_ts, const void* const* d_values, const uint8_t* const* d_nulls) {
     if (!h) return fail(FW_E_INVALID, "null handle");
@@ -1388,13 +1344,7 @@ int fw_push_device_key_rows(fw_handle* h, int64_t n, const int64_t* d_key_row_of
     if (n < 0) return fail(FW_E_INVALID, "negative n");
     if (n == 0) return FW_OK;
     if (!d_key_row_offsets || !d_key_row_bytes || !d_ts) return fail(FW_E_INVALID, "null key row / ts column");
-    if (h->nv > 0 && !d_values) return fail(FW_E_INVALID, "value columns required");
-    for (int s = 0; s < h->nv; s++) {
-        const int v = h->slot_col[s];
-        if (!d_values[v]) return fail(FW_E_INVALID, "value column %d is NULL", v);
-        if (((h->cfg.nullable_cols >> v) & 1u) && (!d_nulls || !d_nulls[v]))
-            return fail(FW_E_INVALID, "nullable value column %d needs its null-flag column", v);
-    }
+    CHECK(check_value_cols(h, d_values, d_nulls));
     return push_key_rows(h, n, d_key_row_offsets, d_key_row_bytes, d_ts, d_values, d_nulls);
 }
 
@@ -1406,31 +1356,19 @@ int fw_push_device(fw_handle* h, int64_t n, const int64_t* d_key, const int64_t*
     if (n == 0) return FW_OK;
     if (h->cw.on) {  // count windows ignore the ts column (d_ts may be NULL)
         if (!d_key) return fail(FW_E_INVALID, "null key column");
-        if (h->cfg.key_hash == FW_KEYHASH_PRECOMPUTED && !d_key_hash) return fail(FW_E_INVALID, "key_hash column required");
-        if (h->nv > 0 && (!d_values || !d_values[h->slot_col[0]])) return fail(FW_E_INVALID, "value column %d is NULL", h->slot_col[0]);
+        CHECK(check_key_hash(h, d_key_hash));
+        if (h->nv > 0 && (!d_values || !d_values[h->slot_col[0]])) return fail_value_null(h->slot_col[0]);
         return cw_push(&h->cw, n, d_key, d_key_hash, h->nv > 0 ? (const uint64_t*)d_values[h->slot_col[0]] : nullptr);
     }
     if (!d_key || !d_ts) return fail(FW_E_INVALID, "null key/ts column");
     if (h->sw.on) {  // session windows: folded into the state now, under the current watermark
-        if (h->cfg.key_hash == FW_KEYHASH_PRECOMPUTED && !d_key_hash) return fail(FW_E_INVALID, "key_hash column required");
-        if (h->nv > 0 && !d_values) return fail(FW_E_INVALID, "value columns required");
-        for (int s = 0; s < h->nv; s++) {
-            const int v = h->slot_col[s];
-            if (!d_values[v]) return fail(FW_E_INVALID, "value column %d is NULL", v);
-            if (((h->cfg.nullable_cols >> v) & 1u) && (!d_nulls || !d_nulls[v]))
-                return fail(FW_E_INVALID, "nullable value column %d needs its null-flag column", v);
-        }
+        CHECK(check_key_hash(h, d_key_hash));
+        CHECK(check_value_cols(h, d_values, d_nulls));
         return sw_push(&h->sw, h->host_cur, n, d_key, d_ts, d_key_hash, d_values, d_nulls);
     }
     if (h->keyrow) return fail(FW_E_INVALID, "a FW_KEYHASH_KEYROW operator takes key rows (fw_push_device_key_rows)");
-    if (h->cfg.key_hash == FW_KEYHASH_PRECOMPUTED && !d_key_hash) return fail(FW_E_INVALID, "key_hash column required");
-    if (h->nv > 0 && !d_values) return fail(FW_E_INVALID, "value columns required");
-    for (int s = 0; s < h->nv; s++) {
-        const int v = h->slot_col[s];
-        if (!d_values[v]) return fail(FW_E_INVALID, "value column %d is NULL", v);
-        if (((h->cfg.nullable_cols >> v) & 1u) && (!d_nulls || !d_nulls[v]))
-            return fail(FW_E_INVALID, "nullable value column %d needs its null-flag column", v);
-    }
+    CHECK(check_key_hash(h, d_key_hash));
+    CHECK(check_value_cols(h, d_values, d_nulls));
     return push(h, n, d_key, d_ts, d_key_hash, d_values, d_nulls);
 }
 
@@ -1439,19 +1377,13 @@ int fw_push_device_segments(fw_handle* h, int32_t n_segs, int64_t seg_len, const
                             const void* const* d_values, const uint8_t* const* d_nulls) {
     if (!h) return fail(FW_E_INVALID, "null handle");
     CW_REFUSE_EXCHANGE(h, "fw_push_device_segments");
-    if (n_segs < 0 || seg_len < 1 || (n_segs > 0 && !d_seg_counts)) return fail(FW_E_INVALID, "bad segments");
+    CHECK(check_segments(n_segs, seg_len, d_seg_counts));
     if (h->keyrow) return fail(FW_E_INVALID, "a FW_KEYHASH_KEYROW operator takes key rows (fw_push_device_key_rows)");
     const int64_t n = (int64_t)n_segs * seg_len;
     if (n == 0) return FW_OK;
     if (!d_key || !d_ts) return fail(FW_E_INVALID, "null key/ts column");
-    if (h->cfg.key_hash == FW_KEYHASH_PRECOMPUTED && !d_key_hash) return fail(FW_E_INVALID, "key_hash column required");
-    if (h->nv > 0 && !d_values) return fail(FW_E_INVALID, "value columns required");
-    for (int s = 0; s < h->nv; s++) {
-        const int v = h->slot_col[s];
-        if (!d_values[v]) return fail(FW_E_INVALID, "value column %d is NULL", v);
-        if (((h->cfg.nullable_cols >> v) & 1u) && (!d_nulls || !d_nulls[v]))
-            return fail(FW_E_INVALID, "nullable value column %d needs its null-flag column", v);
-    }
+    CHECK(check_key_hash(h, d_key_hash));
+    CHECK(check_value_cols(h, d_values, d_nulls));
     if (h->sw.on) {  // folded now, under Ctrl::cur at this point of the stream
         ar_kick(h);
         return sw_push_segments(&h->sw, n_segs, seg_len, d_seg_counts, d_key, d_ts, 1, d_key_hash, d_values, d_nulls);
@@ -1463,8 +1395,8 @@ int fw_push_device_packed_segments(fw_handle* h, int32_t n_segs, int64_t seg_len
                                    const int64_t* d_rows, int32_t row_words) {
     if (!h) return fail(FW_E_INVALID, "null handle");
     CW_REFUSE_EXCHANGE(h, "fw_push_device_packed_segments");
-    if (n_segs < 0 || seg_len < 1 || (n_segs > 0 && !d_seg_counts)) return fail(FW_E_INVALID, "bad segments");
-    if (row_words != 2 + h->cfg.n_value_cols) return fail(FW_E_INVALID, "row_words %d != 2 + value columns", row_words);
+    CHECK(check_segments(n_segs, seg_len, d_seg_counts));
+    CHECK(check_row_words(h, row_words, nullptr));
     if (h->cfg.key_hash == FW_KEYHASH_PRECOMPUTED || h->keyrow || h->cfg.nullable_cols)
         return fail(FW_E_INVALID, "packed rows carry no key-hash, key-row or null-flag columns");
     const int64_t n = (int64_t)n_segs * seg_len;
@@ -1492,13 +1424,12 @@ int fw_push_device_count_segments(fw_handle* h, int32_t n_segs, int64_t seg_len,
                                   const int64_t* d_key, const int32_t* d_key_hash, const void* d_value) {
     if (!h) return fail(FW_E_INVALID, "null handle");
     CW_ONLY_EXCHANGE(h, "fw_push_device_count_segments");
-    if (n_segs < 0 || seg_len < 1 || (n_segs > 0 && !d_seg_counts)) return fail(FW_E_INVALID, "bad segments");
-    if (seg_len >= (1ll << 32) || (int64_t)n_segs * seg_len >= (1ll << 32))
-        return fail(FW_E_INVALID, "arrival ordinals need n_segs * seg_len < 2^32 rows per call");
+    CHECK(check_segments(n_segs, seg_len, d_seg_counts));
+    CHECK(check_ordinals(n_segs, seg_len));
     if (n_segs == 0) return FW_OK;
     if (!d_key) return fail(FW_E_INVALID, "null key column");
-    if (h->cfg.key_hash == FW_KEYHASH_PRECOMPUTED && !d_key_hash) return fail(FW_E_INVALID, "key_hash column required");
-    if (h->nv > 0 && !d_value) return fail(FW_E_INVALID, "value column %d is NULL", h->slot_col[0]);
+    CHECK(check_key_hash(h, d_key_hash));
+    if (h->nv > 0 && !d_value) return fail_value_null(h->slot_col[0]);
     return cw_push_segments(&h->cw, n_segs, seg_len, d_seg_counts, d_key,
                             h->cfg.key_hash == FW_KEYHASH_PRECOMPUTED ? d_key_hash : nullptr,
                             h->nv > 0 ? (const uint64_t*)d_value : nullptr, 1);
@@ -1508,34 +1439,22 @@ int fw_push_device_count_packed_segments(fw_handle* h, int32_t n_segs, int64_t s
                                          const int64_t* d_rows, int32_t row_words) {
     if (!h) return fail(FW_E_INVALID, "null handle");
     CW_ONLY_EXCHANGE(h, "fw_push_device_count_packed_segments");
-    if (n_segs < 0 || seg_len < 1 || (n_segs > 0 && !d_seg_counts)) return fail(FW_E_INVALID, "bad segments");
-    if (row_words != 2 + h->cfg.n_value_cols) return fail(FW_E_INVALID, "row_words %d != 2 + value columns", row_words);
+    CHECK(check_segments(n_segs, seg_len, d_seg_counts));
+    CHECK(check_row_words(h, row_words, nullptr));
     if (h->cfg.key_hash == FW_KEYHASH_PRECOMPUTED) return fail(FW_E_INVALID, "packed rows carry no key-hash column");
-    if (seg_len >= (1ll << 32) || (int64_t)n_segs * seg_len >= (1ll << 32))
-        return fail(FW_E_INVALID, "arrival ordinals need n_segs * seg_len < 2^32 rows per call");
+    CHECK(check_ordinals(n_segs, seg_len));
     if (n_segs == 0) return FW_OK;
     if (!d_rows) return fail(FW_E_INVALID, "null rows");
     // (key, ts, value): word 1 is not read; a count aggregate reads no value word either
     return cw_push_segments(&h->cw, n_segs, seg_len, d_seg_counts, d_rows, nullptr, (const uint64_t*)d_rows + 2, row_words);
 }
 
-// The record count handle's own exchange entries: the count handle's two above keep refusing it.
-#define CW_ONLY_RECORD_EXCHANGE(h, name)                                                                                   \
-    if ((h)->sw.on) return fail(FW_E_INVALID, name ": not for session windows (record count windows only)");               \
-    if (!(h)->cw.on) return fail(FW_E_INVALID, name ": not for time windows (record count windows only)");                 \
-    if (!(h)->cw.rec)                                                                                                      \
-        return fail(FW_E_INVALID, name ": not for count windows (FW_WIN_COUNT: fw_push_device_count_packed_segments)");     \
-    if ((h)->cfg.parallelism <= 1)                                                                                         \
-        return fail(FW_E_INVALID, name ": a record count handle of parallelism 1 has no keyBy exchange in front of it")
-
 int fw_push_device_count_record_packed_segments(fw_handle* h, int32_t n_segs, int64_t seg_len, const int64_t* d_seg_counts,
                                                 const int64_t* d_rows, int32_t row_words) {
     if (!h) return fail(FW_E_INVALID, "null handle");
     CW_ONLY_RECORD_EXCHANGE(h, "fw_push_device_count_record_packed_segments");
-    if (n_segs < 0 || seg_len < 1 || (n_segs > 0 && !d_seg_counts)) return fail(FW_E_INVALID, "bad segments");
-    if (row_words != 2 + h->cfg.n_value_cols)
-        return fail(FW_E_INVALID, "fw_push_device_count_record_packed_segments: row_words %d != 2 + value columns (%d record fields)",
-                    row_words, h->cfg.n_value_cols);
+    CHECK(check_segments(n_segs, seg_len, d_seg_counts));
+    CHECK(check_row_words(h, row_words, "fw_push_device_count_record_packed_segments"));
     if (h->cfg.key_hash == FW_KEYHASH_PRECOMPUTED)
         return fail(FW_E_INVALID, "fw_push_device_count_record_packed_segments: packed rows carry no key-hash column");
     if (seg_len > h->cfg.max_batch_rows)  // (keeps n_segs * seg_len in range below)
@@ -1545,73 +1464,6 @@ int fw_push_device_count_record_packed_segments(fw_handle* h, int32_t n_segs, in
     if (!d_rows) return fail(FW_E_INVALID, "null rows");
     // (key, unread word, the record's fields): the aggregated field is word 2 + input_col
     return cw_push_record_segments(&h->cw, n_segs, seg_len, d_seg_counts, d_rows, row_words);
-}
-
-int fw_count_record_rows(fw_handle* h, const int64_t* d_rows, int32_t row_words, int64_t n_rows, fw_record_rows* out) {
-    if (!h || !out) return fail(FW_E_INVALID, "null argument");
-    CW_ONLY_RECORD_EXCHANGE(h, "fw_count_record_rows");
-    memset(out, 0, sizeof *out);
-    CountOp& w = h->cw;
-    const int32_t F = h->cfg.n_value_cols;
-    if (row_words != 2 + F)
-        return fail(FW_E_INVALID, "fw_count_record_rows: row_words %d != 2 + value columns (%d record fields)", row_words, F);
-    if (n_rows < 0 || n_rows >= (1ll << 32) || (n_rows > 0 && !d_rows)) return fail(FW_E_INVALID, "fw_count_record_rows: bad rows");
-    if (w.push_seq == 0) return fail(FW_E_STATE, "fw_count_record_rows without a push");
-    int rc = cw_record_rows(&w, d_rows, row_words, n_rows, F);
-    if (rc) return rc;
-    Ctrl c;
-    memset(&c, 0, sizeof c);
-    rc = read_ctrl(h, &c);  // the one host wait: behind the push and the gather
-    if (rc && c.error != ERR_ORDEV) return rc;  // (an event overflow stays readable, as in fw_first_element_events)
-    const int64_t n_ev = std::min<int64_t>(c.n_ordev, w.ordev_cap);
-    const int64_t n_res = std::min<int64_t>((int64_t)c.out_count[0], w.out_cap);
-    h->rr_ord.resize((size_t)n_ev);
-    h->rr_rord.resize((size_t)n_res);
-    if (n_ev) HIP_TRY(hipMemcpy(h->rr_ord.data(), w.ordev, (size_t)n_ev * 8, hipMemcpyDeviceToHost));
-    if (n_res) HIP_TRY(hipMemcpy(h->rr_rord.data(), w.out_rord, (size_t)n_res * 8, hipMemcpyDeviceToHost));
-    const uint64_t seq = (uint64_t)(w.push_seq - 1);
-    h->rr_is_retain.assign((size_t)n_ev, 0);
-    h->rr_from_push.assign((size_t)n_res, 0);
-    for (int64_t i = 0; i < n_ev; i++) {  // nothing is consumed before every named row is known to lie in the buffer
-        const int64_t e = h->rr_ord[i];
-        if (e & ORDEV_RELEASE) continue;
-        h->rr_is_retain[i] = 1;
-        if (((uint64_t)e >> 32) != seq)
-            return fail(FW_E_INVALID, "fw_count_record_rows: a retain event names push %lld, not the last push %lld (call it after every push)",
-                        (long long)((uint64_t)e >> 32), (long long)seq);
-        if ((e & 0xffffffffll) >= n_rows)
-            return fail(FW_E_INVALID, "fw_count_record_rows: a retain event names row %lld of the push, n_rows is %lld",
-                        (long long)(e & 0xffffffffll), (long long)n_rows);
-    }
-    for (int64_t i = 0; i < n_res; i++) {
-        const uint64_t o = (uint64_t)h->rr_rord[i];
-        if ((o >> 32) != seq) continue;
-        h->rr_from_push[i] = 1;
-        if ((int64_t)(o & 0xffffffffull) >= n_rows)
-            return fail(FW_E_INVALID, "fw_count_record_rows: a result names row %lld of the push, n_rows is %lld",
-                        (long long)(o & 0xffffffffull), (long long)n_rows);
-    }
-    h->rr_ev_words.resize((size_t)n_ev * F);
-    h->rr_res_words.resize((size_t)n_res * F);
-    if (n_ev) HIP_TRY(hipMemcpy(h->rr_ev_words.data(), w.g_ev, (size_t)n_ev * F * 8, hipMemcpyDeviceToHost));
-    if (n_res) HIP_TRY(hipMemcpy(h->rr_res_words.data(), w.g_res, (size_t)n_res * F * 8, hipMemcpyDeviceToHost));
-    const int64_t zero = 0;
-    HIP_TRY(hipMemcpy(&h->ctrl->n_ordev, &zero, 8, hipMemcpyHostToDevice));
-    for (int64_t i = 0; i < n_ev; i++) {
-        h->rr_ord[i] &= ~ORDEV_RELEASE;
-        if (!h->rr_is_retain[i]) memset(h->rr_ev_words.data() + (size_t)i * F, 0, (size_t)F * 8);
-    }
-    for (int64_t i = 0; i < n_res; i++)
-        if (!h->rr_from_push[i]) memset(h->rr_res_words.data() + (size_t)i * F, 0, (size_t)F * 8);
-    out->n_fields = F;
-    out->n_ev = n_ev;
-    out->ev_ord = h->rr_ord.data();
-    out->ev_is_retain = h->rr_is_retain.data();
-    out->ev_words = h->rr_ev_words.data();
-    out->n_res = n_res;
-    out->res_words = h->rr_res_words.data();
-    out->res_from_push = h->rr_from_push.data();
-    return FW_OK;
 }
 
 int fw_advance(fw_handle* h, int64_t watermark) {
@@ -1650,10 +1502,7 @@ int fw_advance(fw_handle* h, int64_t watermark) {
     }
     int rc = launch_merge(h, watermark, 0);
     if (rc) return rc;
-    if (h->keyrow)  // key rows no state / partial / timer request / unread result holds any more
-        HIP_TRY(launch_kr_collect(h->kr, h->ctrl, h->state, h->state_count, h->sb_nar, h->nw_t, h->ks.n_sb, h->cap_e, h->pwe,
-                                  2 + h->nw_t, h->parts, h->cap_rows, h->treq, h->out_key, h->sb_out, h->slab_cap,
-                                  h->treq_cap, h->out_cap, h->stream));
+    if (h->keyrow && (rc = kr_collect(h))) return rc;
     if (watermark > h->host_cur) h->host_cur = watermark;
     return FW_OK;
 }
@@ -1672,474 +1521,15 @@ int fw_advance_device(fw_handle* h, const int64_t* d_watermark) {
         HIP_TRY(hipMemcpyAsync(&h->ctrl->cur, d_watermark, sizeof(int64_t), hipMemcpyDeviceToDevice, h->stream));
         return FW_OK;
     }
-    MergeArgs a = merge_args(h, INT64_MIN, 0);
-    a.wm_dev = d_watermark;
-    HIP_TRY(launch_merge_fire(a, h->stream, h->timer));
-    // launch_merge's bookkeeping; the host mirrors of currentProgress stay behind the device (they
-    // only ever skip launches, so a stale, lower value skips fewer)
-    h->pushes_at_merge[h->merge_seq % 64] = h->pushes_total;
-    h->merge_seq++;
-    h->ig_merges++;
-    h->reset_pending = false;
-    if (h->keyrow)
-        HIP_TRY(launch_kr_collect(h->kr, h->ctrl, h->state, h->state_count, h->sb_nar, h->nw_t, h->ks.n_sb, h->cap_e, h->pwe,
-                                  2 + h->nw_t, h->parts, h->cap_rows, h->treq, h->out_key, h->sb_out, h->slab_cap,
-                                  h->treq_cap, h->out_cap, h->stream));
-    return FW_OK;
+    int rc = launch_merge(h, INT64_MIN, 0, d_watermark);
+    if (rc) return rc;
+    return h->keyrow ? kr_collect(h) : FW_OK;
 }
 
 int fw_flush(fw_handle* h) {
     if (!h) return fail(FW_E_INVALID, "null handle");
     if (h->cw.on || h->sw.on) return FW_OK;  // every push is folded into the state when it is pushed
     return force_flush(h);
-}
-
-// a count handle's rows: one per fire, in the device's order; first_ord orders them as the reference emits
-struct FoldedOut {
-    int64_t *key, *ws, *we;
-    uint64_t* val[FW_MAX_AGGS];  // [n_val] value columns (a SQL session handle: one per aggregate)
-    int32_t n_val;
-    int64_t* ord;  // NULL: a session handle's rows carry no ordinal
-    uint32_t* null_mask;
-    bool nulls;    // the null mask is written by the device (a SQL session handle); else zeros
-    int64_t out_cap;
-};
-static FoldedOut folded_out(fw_handle* h) {
-    if (h->cw.on)  // (a record handle: values[1] is the ordinal of the record each row is built from)
-        return {h->cw.out_key, h->cw.out_ws, h->cw.out_we, {h->cw.out_val, h->cw.out_rord}, h->cw.rec ? 2 : 1, h->cw.out_ord, h->cw.out_null,
-                false, h->cw.out_cap};
-    FoldedOut w{h->sw.out_key, h->sw.out_ws, h->sw.out_we, {}, h->sw.n_out, nullptr, h->sw.out_null, h->sw.d.sql != 0, h->sw.out_cap};
-    for (int g = 0; g < w.n_val; g++) w.val[g] = h->sw.out_val[g];
-    return w;
-}
-static int cw_results(fw_handle* h, fw_result* out, int copy_to_host) {
-    const FoldedOut w = folded_out(h);
-    Ctrl c;
-    int rc = read_ctrl(h, &c);
-    if (rc) return rc;
-    const int64_t n = (int64_t)c.out_count[0];
-    if (n > w.out_cap)
-        return fail(FW_E_CAPACITY, "%lld result rows exceed output_capacity %lld (read results more often)", (long long)n,
-                    (long long)w.out_cap);
-    memset(out, 0, sizeof *out);
-    out->n = n;
-    if (!copy_to_host) {
-        out->key = w.key;
-        out->window_start = w.ws;
-        out->window_end = w.we;
-        for (int g = 0; g < w.n_val; g++) out->values[g] = (int64_t*)w.val[g];
-        out->first_ord = w.ord;
-        out->null_mask = w.null_mask;
-        return FW_OK;
-    }
-    h->r_key.resize(n);
-    h->r_ws.resize(n);
-    h->r_we.resize(n);
-    const int ord_at = w.n_val;  // r_val[n_val] holds a count handle's ordinals
-    for (int g = 0; g < w.n_val; g++) h->r_val[g].resize(n);
-    if (w.ord) h->r_val[ord_at].resize(n);
-    h->r_null.assign(n, 0u);
-    if (n) {
-        HIP_TRY(hipMemcpyAsync(h->r_key.data(), w.key, n * 8, hipMemcpyDeviceToHost, h->stream));
-        HIP_TRY(hipMemcpyAsync(h->r_ws.data(), w.ws, n * 8, hipMemcpyDeviceToHost, h->stream));
-        HIP_TRY(hipMemcpyAsync(h->r_we.data(), w.we, n * 8, hipMemcpyDeviceToHost, h->stream));
-        for (int g = 0; g < w.n_val; g++)
-            HIP_TRY(hipMemcpyAsync(h->r_val[g].data(), w.val[g], n * 8, hipMemcpyDeviceToHost, h->stream));
-        if (w.nulls) HIP_TRY(hipMemcpyAsync(h->r_null.data(), w.null_mask, n * 4, hipMemcpyDeviceToHost, h->stream));
-        if (w.ord) HIP_TRY(hipMemcpyAsync(h->r_val[ord_at].data(), w.ord, n * 8, hipMemcpyDeviceToHost, h->stream));
-        HIP_TRY(hipStreamSynchronize(h->stream));
-    }
-    out->key = h->r_key.data();
-    out->window_start = h->r_ws.data();
-    out->window_end = h->r_we.data();
-    for (int g = 0; g < w.n_val; g++) out->values[g] = (int64_t*)h->r_val[g].data();
-    out->first_ord = w.ord ? (int64_t*)h->r_val[ord_at].data() : nullptr;
-    out->null_mask = h->r_null.data();
-    return FW_OK;
-}
-
-int fw_results(fw_handle* h, fw_result* out, int copy_to_host) {
-    if (!h || !out) return fail(FW_E_INVALID, "null argument");
-    if (h->cw.on || h->sw.on) return cw_results(h, out, copy_to_host);
-    if (h->reset_pending) {  // consumed and nothing emitted since
-        Ctrl c;
-        int rc = read_ctrl(h, &c);
-        if (rc) return rc;
-        memset(out, 0, sizeof *out);
-        return FW_OK;
-    }
-    CompactArgs ca{};
-    ca.ctrl = h->ctrl;
-    ca.sb_out = h->sb_out;
-    ca.off = h->coff;
-    ca.n_sb = h->ks.n_sb;
-    ca.n_aggs = h->n_out;
-    ca.slab_cap = h->slab_cap;
-    ca.out_key = h->out_key;
-    ca.win = device_win(h);
-    ca.local_out = h->cfg.agg_phase == FW_PHASE_LOCAL;
-    ca.out_we = h->out_we;
-    ca.out_null = h->out_null;
-    for (int g = 0; g < h->n_out; g++) {
-        ca.out_val[g] = h->out_val[g];
-        ca.res_val[g] = h->res_val[g];
-    }
-    ca.res_key = h->res_key;
-    ca.res_ws = h->res_ws;
-    ca.res_we = h->res_we;
-    ca.res_null = h->res_null;
-    ca.res_cap = h->out_cap;
-    HIP_TRY(launch_compact(ca, h->stream, h->timer));
-    const int32_t krw = h->kr.stride_words - 1;  // image words per result row
-    if (h->keyrow)  // each result row's key row, gathered from the table while its id is held
-        HIP_TRY(launch_kr_result_rows(h->kr, h->res_key, h->coff + h->ks.n_sb + 1, h->out_cap, h->res_kr_len,
-                                      h->res_kr_img, krw, h->stream));
-    Ctrl c;
-    int rc = read_ctrl(h, &c);
-    if (rc) return rc;
-    // (more rows than the result columns hold: the compaction raised ERR_OUTPUT, which failed read_ctrl)
-    int64_t n = 0;  // the rows the compaction copied, <= out_cap
-    HIP_TRY(hipMemcpy(&n, h->coff + h->ks.n_sb + 1, sizeof n, hipMemcpyDeviceToHost));
-    memset(out, 0, sizeof *out);
-    out->n = n;
-    const int na = h->n_out;
-    const int nv = h->ad.first_word >= 0 ? na - 1 : na;  // the last column is value1's ordinal
-    if (!copy_to_host) {
-        out->key = h->res_key;
-        out->window_start = h->res_ws;
-        out->window_end = h->res_we;
-        for (int g = 0; g < nv; g++) out->values[g] = (int64_t*)h->res_val[g];
-        if (nv < na) out->first_ord = (int64_t*)h->res_val[nv];
-        out->null_mask = h->res_null;
-        if (h->keyrow) {
-            out->key_row_len = h->res_kr_len;
-            out->key_row_bytes = (uint8_t*)h->res_kr_img;
-            out->key_row_stride = 8ll * krw;
-        }
-        return FW_OK;
-    }
-    h->r_key.resize(n);
-    h->r_ws.resize(n);
-    h->r_we.resize(n);
-    h->r_null.resize(n);
-    if (n) {
-        HIP_TRY(hipMemcpyAsync(h->r_key.data(), h->res_key, n * 8, hipMemcpyDeviceToHost, h->stream));
-        HIP_TRY(hipMemcpyAsync(h->r_ws.data(), h->res_ws, n * 8, hipMemcpyDeviceToHost, h->stream));
-        HIP_TRY(hipMemcpyAsync(h->r_we.data(), h->res_we, n * 8, hipMemcpyDeviceToHost, h->stream));
-        HIP_TRY(hipMemcpyAsync(h->r_null.data(), h->res_null, n * 4, hipMemcpyDeviceToHost, h->stream));
-    }
-    for (int g = 0; g < na; g++) {
-        h->r_val[g].resize(n);
-        if (n) HIP_TRY(hipMemcpyAsync(h->r_val[g].data(), h->res_val[g], n * 8, hipMemcpyDeviceToHost, h->stream));
-    }
-    if (h->keyrow) {
-        h->r_kr_len.resize(n);
-        h->r_kr_img.resize((size_t)n * krw);
-        if (n) {
-            HIP_TRY(hipMemcpyAsync(h->r_kr_len.data(), h->res_kr_len, n * 4, hipMemcpyDeviceToHost, h->stream));
-            HIP_TRY(hipMemcpyAsync(h->r_kr_img.data(), h->res_kr_img, (size_t)n * krw * 8, hipMemcpyDeviceToHost, h->stream));
-        }
-    }
-    HIP_TRY(hipStreamSynchronize(h->stream));
-    out->key = h->r_key.data();
-    out->window_start = h->r_ws.data();
-    out->window_end = h->r_we.data();
-    for (int g = 0; g < nv; g++) out->values[g] = (int64_t*)h->r_val[g].data();
-    if (nv < na) out->first_ord = (int64_t*)h->r_val[nv].data();
-    out->null_mask = h->r_null.data();
-    if (h->keyrow) {
-        out->key_row_len = h->r_kr_len.data();
-        out->key_row_bytes = (uint8_t*)h->r_kr_img.data();
-        out->key_row_stride = 8ll * krw;
-    }
-    return FW_OK;
-}
-
-int fw_results_async(fw_handle* h) {
-    if (!h) return fail(FW_E_INVALID, "null handle");
-    CW_REFUSE(h, "fw_results_async");
-    if (h->keyrow) return fail(FW_E_INVALID, "key-row operators return their rows through fw_results");
-    int rc = alloc_async_results(h);
-    if (rc) return rc;
-    if (h->ar_qn == FW_AR_BUFS)
-        return fail(FW_E_STATE, "%d result collections outstanding: fw_results_ready first", FW_AR_BUFS);
-    const int b = h->ar_cur;
-    h->ar_cur = (b + 1) % FW_AR_BUFS;
-    h->ar_q[(h->ar_qhead + h->ar_qn) % FW_AR_BUFS] = b;
-    h->ar_qn++;
-    h->ar_empty[b] = h->reset_pending;  // consumed and nothing emitted since
-    h->ar_copied[b] = false;
-    if (h->ar_inflight[b]) {  // an early DMA of this buffer's previous rows: the compaction waits for it
-        HIP_TRY(hipStreamWaitEvent(h->stream, h->ar_dma_ev[b], 0));
-        h->ar_inflight[b] = false;
-    }
-    if (h->ar_empty[b]) return FW_OK;
-    CompactArgs ca{};
-    ca.ctrl = h->ctrl;
-    ca.sb_out = h->sb_out;
-    ca.off = h->coff;
-    ca.n_sb = h->ks.n_sb;
-    ca.n_aggs = h->n_out;
-    ca.slab_cap = h->slab_cap;
-    ca.out_key = h->out_key;
-    ca.win = device_win(h);
-    ca.local_out = h->cfg.agg_phase == FW_PHASE_LOCAL;
-    ca.out_we = h->out_we;
-    ca.out_null = h->out_null;
-    for (int g = 0; g < h->n_out; g++) {
-        ca.out_val[g] = h->out_val[g];
-        ca.res_val[g] = h->ard_val[b][g];
-    }
-    ca.res_key = h->ard_key[b];
-    ca.res_ws = h->ard_ws[b];
-    ca.res_we = h->ard_we[b];
-    ca.res_null = h->ard_null[b];
-    ca.res_cap = h->out_cap;
-    ca.host_n = mapped(h->ar_n[b]);
-    if (!ca.host_n) return fail(FW_E_DEVICE, "mapped result count unavailable");
-    HIP_TRY(launch_compact(ca, h->stream, h->timer));
-    if (h->ar_kernel) {
-        CopyOutArgs co{};
-        co.d_n = h->coff + h->ks.n_sb + 1;
-        co.n_aggs = h->n_out;
-        co.cap = h->out_cap;
-        co.src_key = h->ard_key[b];
-        co.src_ws = h->ard_ws[b];
-        co.src_we = h->ard_we[b];
-        co.src_null = h->ard_null[b];
-        co.dst_key = mapped(h->ar_key[b]);
-        co.dst_ws = mapped(h->ar_ws[b]);
-        co.dst_we = mapped(h->ar_we[b]);
-        co.dst_null = mapped(h->ar_null[b]);
-        for (int g = 0; g < h->n_out; g++) {
-            co.src_val[g] = h->ard_val[b][g];
-            co.dst_val[g] = mapped(h->ar_val[b][g]);
-            if (!co.dst_val[g]) return fail(FW_E_DEVICE, "mapped result buffer unavailable");
-        }
-        if (!co.dst_key || !co.dst_ws || !co.dst_we || !co.dst_null) return fail(FW_E_DEVICE, "mapped result buffer unavailable");
-        HIP_TRY(launch_copy_out(co, h->stream));
-        h->ar_copied[b] = true;  // the rows are in host memory once ar_ev[b] has fired
-    }
-    HIP_TRY(hipEventRecord(h->ar_ev[b], h->stream));
-    h->reset_pending = true;  // the rows are collected: the next merge launch starts the slabs afresh
-    return FW_OK;
-}
-
-int fw_results_device_segments(fw_handle* h, fw_result_segments* out) {
-    if (!h || !out) return fail(FW_E_INVALID, "null argument");
-    CW_REFUSE(h, "fw_results_device_segments");
-    if (h->keyrow) return fail(FW_E_INVALID, "key-row operators return their rows through fw_results");
-    memset(out, 0, sizeof *out);
-    const int na = h->n_out;
-    const int nv = h->ad.first_word >= 0 ? na - 1 : na;
-    out->seg_cap = h->slab_cap;
-    out->counts = h->sb_out;
-    out->cols.n = (int64_t)h->ks.n_sb * h->slab_cap + h->out_cap;
-    out->cols.key = h->out_key;
-    out->cols.window_start = nullptr;  // v10: derived from window_end (flinkwin.h)
-    out->cols.window_end = h->out_we;
-    for (int g = 0; g < nv; g++) out->cols.values[g] = (int64_t*)h->out_val[g];
-    if (nv < na) out->cols.first_ord = (int64_t*)h->out_val[nv];
-    out->cols.null_mask = h->out_null;
-    // consumed and nothing emitted since: no segments (the counts are those of consumed rows)
-    out->n_segments = h->reset_pending ? 0 : (int64_t)h->ks.n_sb + 1;
-    h->reset_pending = true;  // consumed: the next merge launch starts the slabs afresh
-    return FW_OK;
-}
-
-int fw_results_device(fw_handle* h, fw_result* out, int64_t** d_n) {
-    if (!h || !out || !d_n) return fail(FW_E_INVALID, "null argument");
-    CW_REFUSE(h, "fw_results_device");
-    if (h->keyrow) return fail(FW_E_INVALID, "key-row operators return their rows through fw_results");
-    memset(out, 0, sizeof *out);
-    *d_n = h->coff + h->ks.n_sb + 1;
-    if (h->reset_pending) {  // consumed and nothing emitted since: zero rows
-        HIP_TRY(hipMemsetAsync(*d_n, 0, sizeof(int64_t), h->stream));
-    } else {
-        CompactArgs ca{};
-        ca.ctrl = h->ctrl;
-        ca.sb_out = h->sb_out;
-        ca.off = h->coff;
-        ca.n_sb = h->ks.n_sb;
-        ca.n_aggs = h->n_out;
-        ca.slab_cap = h->slab_cap;
-        ca.out_key = h->out_key;
-        ca.win = device_win(h);
-    ca.local_out = h->cfg.agg_phase == FW_PHASE_LOCAL;
-        ca.out_we = h->out_we;
-        ca.out_null = h->out_null;
-        for (int g = 0; g < h->n_out; g++) {
-            ca.out_val[g] = h->out_val[g];
-            ca.res_val[g] = h->res_val[g];
-        }
-        ca.res_key = h->res_key;
-        ca.res_ws = h->res_ws;
-        ca.res_we = h->res_we;
-        ca.res_null = h->res_null;
-        ca.res_cap = h->out_cap;
-        HIP_TRY(launch_compact(ca, h->stream, h->timer));
-        h->reset_pending = true;
-    }
-    const int na = h->n_out;
-    const int nv = h->ad.first_word >= 0 ? na - 1 : na;
-    out->n = h->out_cap;
-    out->key = h->res_key;
-    out->window_start = h->res_ws;
-    out->window_end = h->res_we;
-    for (int g = 0; g < nv; g++) out->values[g] = (int64_t*)h->res_val[g];
-    if (nv < na) out->first_ord = (int64_t*)h->res_val[nv];
-    out->null_mask = h->res_null;
-    return FW_OK;
-}
-
-int fw_results_ready(fw_handle* h, fw_result* out) {
-    if (!h || !out) return fail(FW_E_INVALID, "null argument");
-    CW_REFUSE(h, "fw_results_ready");
-    memset(out, 0, sizeof *out);
-    if (h->ar_qn == 0) return fail(FW_E_STATE, "fw_results_ready without an outstanding fw_results_async");
-    const int b = h->ar_q[h->ar_qhead];  // the oldest outstanding collection
-    h->ar_qhead = (h->ar_qhead + 1) % FW_AR_BUFS;
-    h->ar_qn--;
-    if (h->ar_empty[b]) return FW_OK;
-    HIP_TRY(hipEventSynchronize(h->ar_ev[b]));  // the compaction (long done: it ran a step ago)
-    const int64_t n = __atomic_load_n(h->ar_n[b], __ATOMIC_ACQUIRE);
-    if (n > h->out_cap)
-        return fail(FW_E_CAPACITY, "%lld result rows exceed output_capacity %lld (read results more often)",
-                    (long long)n, (long long)h->out_cap);
-    const int na = h->n_out;
-    const int nv = h->ad.first_word >= 0 ? na - 1 : na;
-    if (n > 0 && !h->ar_copied[b]) {  // the rows by DMA on the D2H stream (no CU time, no operator-stream slot)
-        if (!h->ar_inflight[b]) {  // not started early by ar_kick
-            int rc = ar_enqueue_copy(h, b, n);
-            if (rc) return rc;
-            h->ar_inflight[b] = true;
-        }
-        HIP_TRY(hipEventSynchronize(h->ar_dma_ev[b]));
-        h->ar_copied[b] = true;
-    }
-    out->n = n;
-    out->key = h->ar_key[b];
-    out->window_start = h->ar_ws[b];
-    out->window_end = h->ar_we[b];
-    for (int g = 0; g < nv; g++) out->values[g] = (int64_t*)h->ar_val[b][g];
-    if (nv < na) out->first_ord = (int64_t*)h->ar_val[b][nv];
-    out->null_mask = h->ar_null[b];
-    return FW_OK;
-}
-
-int fw_first_element_events(fw_handle* h, fw_ordinal_events* out) {
-    if (!h || !out) return fail(FW_E_INVALID, "null argument");
-    const bool rec = h->cw.on && h->cw.rec;  // a record count handle's events: the ordinals its ring slots hold
-    if (!rec) {
-        CW_REFUSE(h, "fw_first_element_events");
-    }
-    memset(out, 0, sizeof *out);
-    const int64_t* ordev = rec ? h->cw.ordev : h->ordev;
-    const int64_t ordev_cap = rec ? h->cw.ordev_cap : h->ordev_cap;
-    if (!ordev_cap) return fail(FW_E_STATE, "the operator does not track first elements (ds_first_ordinals = 0)");
-    Ctrl c;
-    int rc = read_ctrl(h, &c);
-    // (a record count handle: an overflow stays readable -- the events that fit, FW_ERRF_ORDEV in fw_get_stats;
-    // fw_results keeps failing on the error bit)
-    if (rc && !(rec && c.error == ERR_ORDEV)) return rc;
-    const int64_t n = std::min<int64_t>(c.n_ordev, ordev_cap);
-    std::vector<int64_t> raw((size_t)n);
-    if (n) HIP_TRY(hipMemcpy(raw.data(), ordev, (size_t)n * 8, hipMemcpyDeviceToHost));
-    const int64_t zero = 0;
-    HIP_TRY(hipMemcpy(&h->ctrl->n_ordev, &zero, 8, hipMemcpyHostToDevice));
-    h->ev_retain.clear();
-    h->ev_release.clear();
-    for (int64_t e : raw) {
-        if (e & ORDEV_RELEASE) h->ev_release.push_back(e & ~ORDEV_RELEASE);
-        else h->ev_retain.push_back(e);
-    }
-    out->n_retain = (int64_t)h->ev_retain.size();
-    out->retain = h->ev_retain.data();
-    out->n_release = (int64_t)h->ev_release.size();
-    out->release = h->ev_release.data();
-    return FW_OK;
-}
-
-// a session handle's late side output: the elements dropped as late since the last call
-static int sw_late_records(fw_handle* h, fw_late_rows* out) {
-    memset(out, 0, sizeof *out);
-    SessionOp& w = h->sw;
-    if (!w.side_cap) return fail(FW_E_STATE, "the operator has no late side output (late_side_output = 0)");
-    Ctrl c;
-    int rc = read_ctrl(h, &c);
-    if (rc) return rc;
-    const int64_t n = std::min<int64_t>(c.n_side, w.side_cap);
-    std::vector<int64_t> raw((size_t)n * SW_SIDE_WORDS);
-    if (n) HIP_TRY(hipMemcpy(raw.data(), w.side, raw.size() * 8, hipMemcpyDeviceToHost));
-    const int64_t zero = 0;
-    HIP_TRY(hipMemcpy(&h->ctrl->n_side, &zero, 8, hipMemcpyHostToDevice));
-    h->lr_key.resize(n);
-    h->lr_ts.resize(n);
-    h->lr_seq.resize(n);
-    h->lr_row.resize(n);
-    for (int v = 0; v < h->cfg.n_value_cols; v++) h->lr_val[v].assign(n, 0);
-    for (int64_t i = 0; i < n; i++) {
-        const int64_t* p = raw.data() + (size_t)i * SW_SIDE_WORDS;
-        h->lr_key[i] = p[0];
-        h->lr_ts[i] = p[1];
-        h->lr_seq[i] = (int64_t)((uint64_t)p[2] >> 32);
-        h->lr_row[i] = p[2] & 0xffffffffll;
-        if (!w.d.is_count) h->lr_val[w.val_col][i] = p[3];  // (a dynamic-gap handle's gap column stays 0: the row is named by push_seq, row)
-    }
-    out->n = n;
-    out->key = h->lr_key.data();
-    out->ts = h->lr_ts.data();
-    out->push_seq = h->lr_seq.data();
-    out->row = h->lr_row.data();
-    for (int v = 0; v < h->cfg.n_value_cols; v++) out->values[v] = h->lr_val[v].data();
-    return FW_OK;
-}
-
-int fw_late_records(fw_handle* h, fw_late_rows* out) {
-    if (!h || !out) return fail(FW_E_INVALID, "null argument");
-    if (h->sw.on) return sw_late_records(h, out);
-    CW_REFUSE(h, "fw_late_records");
-    memset(out, 0, sizeof *out);
-    if (!h->side_cap) return fail(FW_E_STATE, "the operator has no late side output (late_side_output = 0)");
-    Ctrl c;
-    int rc = read_ctrl(h, &c);
-    if (rc) return rc;
-    const int64_t n = std::min<int64_t>(c.n_side, h->side_cap);
-    std::vector<int64_t> raw((size_t)n * SOW);
-    if (n) HIP_TRY(hipMemcpy(raw.data(), h->side, raw.size() * 8, hipMemcpyDeviceToHost));
-    const int64_t zero = 0;
-    HIP_TRY(hipMemcpy(&h->ctrl->n_side, &zero, 8, hipMemcpyHostToDevice));
-    h->lr_key.resize(n);
-    h->lr_ts.resize(n);
-    h->lr_seq.resize(n);
-    h->lr_row.resize(n);
-    for (int v = 0; v < h->cfg.n_value_cols; v++) h->lr_val[v].assign(n, 0);
-    for (int64_t i = 0; i < n; i++) {
-        const int64_t* p = raw.data() + (size_t)i * SOW;
-        h->lr_key[i] = p[0];
-        h->lr_ts[i] = p[1];
-        h->lr_seq[i] = (int64_t)((uint64_t)p[2] >> 32);
-        h->lr_row[i] = p[2] & 0xffffffffll;
-        for (int s = 0; s < h->nv; s++) h->lr_val[h->slot_col[s]][i] = p[3 + s];  // loaded value slots
-    }
-    out->n = n;
-    out->key = h->lr_key.data();
-    out->ts = h->lr_ts.data();
-    out->push_seq = h->lr_seq.data();
-    out->row = h->lr_row.data();
-    for (int v = 0; v < h->cfg.n_value_cols; v++) out->values[v] = h->lr_val[v].data();
-    return FW_OK;
-}
-
-int fw_results_reset(fw_handle* h) {
-    if (!h) return fail(FW_E_INVALID, "null handle");
-    if (h->cw.on || h->sw.on) {  // stream-ordered: rows of pushes issued before the call are consumed, later ones kept
-        HIP_TRY(hipMemsetAsync(&h->ctrl->out_count[0], 0, sizeof(uint64_t), h->stream));
-        return FW_OK;
-    }
-    // no launch: the next merge launch starts every output slab and the overflow region afresh
-    h->reset_pending = true;
-    return FW_OK;
 }
 
 int fw_get_stats(fw_handle* h, fw_stats* out) {

@@ -1,13 +1,45 @@
 // fw_handle.h -- the operator handle behind the C-ABI (include/flinkwin.h), private to the library:
-// fw_api.hip creates, drives and destroys it, fw_checkpoint.hip collects its time-window state and
-// installs restored state.  Also the few helpers of fw_api.hip that the checkpoint code calls and the
-// entry points' refusal macros.
+// fw_api.hip creates, drives and destroys it, fw_results.hip delivers its rows, fw_checkpoint.hip
+// collects its time-window state and installs restored state.  Also the few helpers these host files
+// share and the entry points' refusal macros.  Host translation units only.
 #pragma once
 #include <vector>
 
 #include "fw_count.h"
 #include "fw_session.h"
 #include "fw_internal.h"
+
+namespace fw {
+
+// One set of result columns: pointers only, no ownership.  val[] holds the handle's n_out result columns.
+struct ResultCols {
+    int64_t* key = nullptr;
+    int64_t* ws = nullptr;
+    int64_t* we = nullptr;
+    uint64_t* val[FW_MAX_AGGS] = {};
+    uint32_t* null = nullptr;
+};
+
+// the host copies fw_results returns
+struct ResultVecs {
+    std::vector<int64_t> key, ws, we;
+    std::vector<uint64_t> val[FW_MAX_AGGS];
+    std::vector<uint32_t> null;
+    ResultCols resize(int64_t n, int n_val) {  // n rows of n_val value columns, as a column set
+        key.resize(n);
+        ws.resize(n);
+        we.resize(n);
+        null.resize(n);
+        ResultCols c{key.data(), ws.data(), we.data(), {}, null.data()};
+        for (int g = 0; g < n_val; g++) {
+            val[g].resize(n);
+            c.val[g] = val[g].data();
+        }
+        return c;
+    }
+};
+
+}  // namespace fw
 
 struct fw_handle {
     fw_config cfg;
@@ -66,10 +98,7 @@ struct fw_handle {
     int64_t* sb_min_timer = nullptr;
     uint8_t* sb_nar = nullptr;  // HOP block state: superbucket written in the narrow layout
     int hb_narrow = 2;           // narrowest HOP block layout level (FW_HB_NARROW=0/1: development A/B)
-    int64_t* out_key = nullptr;
-    int64_t* out_we = nullptr;
-    uint64_t* out_val[FW_MAX_AGGS] = {};
-    uint32_t* out_null = nullptr;
+    fw::ResultCols out;        // where the merge writes its rows: a slab per superbucket, then the overflow region (out.ws stays null)
     int64_t out_cap = 0;       // result rows between resets (= overflow region rows)
     int64_t slab_cap = 0;      // output slab rows per superbucket
     int32_t* sb_out = nullptr;
@@ -77,11 +106,7 @@ struct fw_handle {
     int64_t* chunk_stats = nullptr;
     fw::Tickets* tickets = nullptr;  // last-workgroup election counters of k_ingest / k_merge_fire
     int64_t* coff = nullptr;   // compaction offsets [n_sb + 2]
-    int64_t* res_key = nullptr;
-    int64_t* res_ws = nullptr;
-    int64_t* res_we = nullptr;
-    uint64_t* res_val[FW_MAX_AGGS] = {};
-    uint32_t* res_null = nullptr;
+    fw::ResultCols res;        // the compacted rows (fw_results, fw_results_device)
 
     // host-staged ingest (FW_STAGE_BUFS pinned column sets)
     int64_t stage_cap = 0;
@@ -107,20 +132,12 @@ struct fw_handle {
     int64_t reserved = -1;
 
     // asynchronous result delivery (fw_results_async / fw_results_ready): rows compacted on the
-    // device into one of FW_AR_BUFS device buffers (ard_*), then moved into pinned host buffers
-    // (ar_*); only the row count goes through mapped memory.  Up to FW_AR_BUFS collections are
+    // device into one of FW_AR_BUFS device buffers (ard), then moved into pinned host buffers
+    // (ar); only the row count goes through mapped memory.  Up to FW_AR_BUFS collections are
     // outstanding; fw_results_ready returns the oldest (ar_q, a FIFO of buffer indices)
-    int64_t* ard_key[fw::FW_AR_BUFS] = {};
-    int64_t* ard_ws[fw::FW_AR_BUFS] = {};
-    int64_t* ard_we[fw::FW_AR_BUFS] = {};
-    uint64_t* ard_val[fw::FW_AR_BUFS][FW_MAX_AGGS] = {};
-    uint32_t* ard_null[fw::FW_AR_BUFS] = {};
+    fw::ResultCols ard[fw::FW_AR_BUFS];
     hipStream_t d2h_stream = nullptr;
-    int64_t* ar_key[fw::FW_AR_BUFS] = {};
-    int64_t* ar_ws[fw::FW_AR_BUFS] = {};
-    int64_t* ar_we[fw::FW_AR_BUFS] = {};
-    uint64_t* ar_val[fw::FW_AR_BUFS][FW_MAX_AGGS] = {};
-    uint32_t* ar_null[fw::FW_AR_BUFS] = {};
+    fw::ResultCols ar[fw::FW_AR_BUFS];
     int64_t* ar_n[fw::FW_AR_BUFS] = {};          // row count (written by the compaction kernel)
     hipEvent_t ar_ev[fw::FW_AR_BUFS] = {};
     hipEvent_t ar_dma_ev[fw::FW_AR_BUFS] = {};   // the DMA of buffer b's rows (started early by ar_kick)
@@ -152,10 +169,7 @@ struct fw_handle {
     std::vector<int32_t> r_kr_len;
     std::vector<uint64_t> r_kr_img;
 
-    // host copies of results
-    std::vector<int64_t> r_key, r_ws, r_we;
-    std::vector<uint64_t> r_val[FW_MAX_AGGS];
-    std::vector<uint32_t> r_null;
+    fw::ResultVecs r;  // host copies of results
 
     int64_t pushes_ub = 0;  // upper bound of device pending_pushes
     // pending-push mirror: host-mapped word written by each merge launch (MergeArgs::host_mirror)
@@ -211,6 +225,27 @@ int read_ctrl(fw_handle* h, Ctrl* out);
 int force_flush(fw_handle* h);
 // interns n key-row images (device) into the table: d_kid / d_khash hold their ids and hashCodes
 int kr_intern(fw_handle* h, int64_t n, const int64_t* d_off, const uint8_t* d_bytes);
+// the window description the kernels get: the shift-zone table pointers are the device copy's
+WinDesc device_win(const fw_handle* h);
+// a packed row is (key, ts or an unread word, the value columns).  `name`: the entry's name for the record
+// entries' wording, null for the plain one
+int check_row_words(const fw_handle* h, int32_t row_words, const char* name);
+
+// fw_results.hip.  Column sets: `rows` rows of n_val value columns on the device (ws: with a window_start
+// column) or pinned (hipHostMalloc flags); freeing takes every pointer of the set; the copy queues n rows
+// of src into dst (host memory) on a stream
+int cols_alloc_device(ResultCols* c, size_t rows, int n_val, bool ws);
+int cols_alloc_pinned(ResultCols* c, size_t rows, int n_val, unsigned flags);
+void cols_free(ResultCols* c, bool pinned);
+int cols_copy_to_host(const ResultCols& dst, const ResultCols& src, int64_t n, int n_val, hipStream_t s);
+// starts the DMA of a finished fw_results_async early, from the calls made before fw_results_ready; never blocks
+void ar_kick(fw_handle* h);
+
+template <typename T>
+T* mapped(T* host) {
+    void* d = nullptr;
+    return hipHostGetDevicePointer(&d, (void*)host, 0) == hipSuccess ? (T*)d : nullptr;
+}
 
 }  // namespace fw
 
@@ -228,6 +263,15 @@ int kr_intern(fw_handle* h, int64_t n, const int64_t* d_off, const uint8_t* d_by
 #define CW_REFUSE_RECORD(h, name)                                                                                       \
     if ((h)->cw.on && (h)->cw.rec)                                                                                      \
         return fw::set_error(FW_E_INVALID, name ": not for record count windows (FW_WIN_COUNT_RECORD: retained records are not re-numbered)")
+// The record count handle's own exchange entries (fw_push_device_count_record_packed_segments,
+// fw_count_record_rows): the count handle's two segment pushes keep refusing it.
+#define CW_ONLY_RECORD_EXCHANGE(h, name)                                                                                   \
+    if ((h)->sw.on) return fw::set_error(FW_E_INVALID, name ": not for session windows (record count windows only)");      \
+    if (!(h)->cw.on) return fw::set_error(FW_E_INVALID, name ": not for time windows (record count windows only)");        \
+    if (!(h)->cw.rec)                                                                                                      \
+        return fw::set_error(FW_E_INVALID, name ": not for count windows (FW_WIN_COUNT: fw_push_device_count_packed_segments)"); \
+    if ((h)->cfg.parallelism <= 1)                                                                                         \
+        return fw::set_error(FW_E_INVALID, name ": a record count handle of parallelism 1 has no keyBy exchange in front of it")
 #define CW_REFUSE_EXCHANGE(h, name)                                                       \
     if ((h)->cw.on) return fw::set_error(FW_E_INVALID, name ": not for count windows");   \
     if ((h)->sw.on && (h)->cfg.parallelism <= 1) return fw::set_error(FW_E_INVALID, name ": not for session windows")
